@@ -45,6 +45,14 @@ load to reach its steady clock; with 5 warmup frames alone the same build read 0
 0.15 ms per frame; the ranks agree on its length), the tile-rows and frames-in-flight autotunes,
 the counter pass, and a re-settle (--resettle-ms of frames on the timed loop's own streams and
 buffers, renders only).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: scene upload and build, the
+settles, the two autotunes and the counter pass above, the warmup, the N timed steps, and the line. --full adds what
+else the benchmark measures, each with passes of its own: the CPU baseline, the configs under "extra" and the REF
+raster, the roofline with its one-stream kernel time, the warm rebuild and TLAS update times under build_ms, and in
+strips mode the frame latency and the per-phase pass; without it those fields are null or empty. --dump-outputs DIR
+writes the frame the last timed step produced (RGBA8, as float32) to DIR/frame.npy; the scene, camera and lights of a
+config are fixed, so two builds run with the same arguments compare pixel for pixel.
 """
 from __future__ import annotations
 
@@ -116,9 +124,35 @@ def parse(argv=None):
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="minimum wall time of the CPU baseline sample")
     p.add_argument("--save-image", default="", help="write the rank-0 frame as .npy")
     p.add_argument("--extra", default=None,
-                   help="comma list of further configs ('' to skip); default N=1: C1,C2F,C3,C4,C5,REF (+ REF "
+                   help="--full: comma list of further configs ('' to skip); default N=1: C1,C2F,C3,C4,C5,REF (+ REF "
                         "raster); N>1: C4,C5 tiled over the same ranks")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure: the CPU baseline, the --extra configs and the REF raster, the "
+                        "roofline (with its one-stream kernel pass), the warm rebuild and TLAS update times, and in "
+                        "strips mode the frame latency and the per-phase pass. Off: the run sets up, warms up, times "
+                        "the steps and prints the line, those fields null or empty")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed (rank 0's RGBA8 frame) as "
+                        "DIR/frame.npy in float32 (a fixed seeded sample of it when it exceeds 64 MB)")
     return p.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <directory>/<name>.npy in float32 (float64 stays float64), DUMP_LIMIT_BYTES in
+    all. An array over its share of the limit is cut to a fixed sample of its flattened elements (generator seed 0,
+    sorted indices: the same elements for the same shape in every run), so two builds compare element for element."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, arr in arrays.items():
+        x = np.ascontiguousarray(arr)
+        x = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), x)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -183,6 +217,7 @@ class HipBackend:
         self.local = local
         self.device = torch.device("cuda", local)
         self.ctx = None
+        self.full = True  # load() also times warm rebuilds and TLAS updates (main: --full)
 
     def init_pg(self):
         if os.environ.get("RT_BENCH_ONE_DEVICE") == "1":  # rehearsal: RCCL refuses two ranks on one GPU
@@ -202,6 +237,8 @@ class HipBackend:
         self.spec = spec
         first = ([round(self.ctx.blas_info(b).build_ms, 4) for b in range(len(spec.meshes))],
                  round(self.ctx.tlas_info().build_ms, 4))
+        if not self.full:  # a plain run: the first build only (it is the one the timed frames traverse)
+            return first
         # warm rebuilds (a hot reload, D3D12HelloTriangle.cpp:1482-1568): the first build above also
         # pays the kernels' first launch
         blas_w, tlas_w = [[] for _ in spec.meshes], []
@@ -399,7 +436,7 @@ def run_config(*args, **kw):
 def _run_config(be, spec, world: int, rank: int, steps: int, warmup: int, settle_ms: float, strips: bool,
                 pipeline: bool, schedule: str, save_image: str = "", in_flight: int = 0, resettle_ms: float = 0.0,
                 frames_per_gather: int = 1, frames_per_launch: int = 0, loopback: int = 0, latency_frames: int = 20,
-                phase_frames: int = 0, held: dict = None):
+                phase_frames: int = 0, held: dict = None, full: bool = True, dump_dir: str = ""):
     from realtimeraytracing_gradproject_amd import distributed as D
     distributed = world > 1
     W, H = spec.width, spec.height
@@ -581,7 +618,14 @@ def _run_config(be, spec, world: int, rank: int, steps: int, warmup: int, settle
     tmax = float(tmax.item())
     render_ms = e0.elapsed_time(e1) / steps
 
-    if not single:
+    # --dump-outputs: the frame of the last timed step as its caller holds it (strips: assembled on rank 0)
+    if dump_dir and rank == 0:
+        last = (ncall[0] - 1) % rcomm.depth if native else (k - 1) % nslot
+        dump_outputs(dump_dir, {"frame": (frame[last] if strips else local[last][:H]).cpu().numpy()})
+
+    if not single and not full:
+        kernel_ms = None  # a pass of its own (below): --full
+    elif not single:
         # the roofline's kernel time: this rank's render alone, back to back on one stream (untimed
         # for value)
         be.synchronize()
@@ -600,7 +644,7 @@ def _run_config(be, spec, world: int, rank: int, steps: int, warmup: int, settle
     # frame per gather, one frame at a time, host clock from the call to the synchronised drain; rank 0's median
     latency_ms = None
     fpg = rcomm.batch if rcomm is not None else None  # the timed loop's (the latency pass below gathers 1 frame)
-    if strips and latency_frames > 0:
+    if full and strips and latency_frames > 0:
         if rcomm is not None:
             rcomm.set_batch(1)
         lat = []
@@ -622,7 +666,7 @@ def _run_config(be, spec, world: int, rank: int, steps: int, warmup: int, settle
     # timed loop's batching and streams again, with the communicator's timing-event pairs around each render, gather
     # and assembly (rt_comm_set_phase_timing), over the wall clock of the pass
     phases = None
-    if native and phase_frames > 0:
+    if full and native and phase_frames > 0:
         rcomm.set_batch(fpg)
         rcomm.set_phase_timing(True)
         if distributed:
@@ -933,6 +977,7 @@ def main(argv=None) -> int:
 
     from realtimeraytracing_gradproject_amd import scenes
     be = make_backend(local)
+    be.full = a.full
     if distributed or strips:
         if not distributed:
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -951,10 +996,12 @@ def main(argv=None) -> int:
     spec = spec_of(a.config)
     r = run_config(be, spec, world, rank, a.steps, a.warmup, a.settle_ms, strips, not a.no_pipeline, a.schedule,
                    a.save_image, a.in_flight, a.resettle_ms, a.frames_per_gather, a.frames_per_launch, a.loopback,
-                   a.latency_frames, a.phase_frames)
+                   a.latency_frames, a.phase_frames, full=a.full, dump_dir=a.dump_outputs)
 
     extra = []
     names = a.extra if a.extra is not None else ("C4,C5" if distributed else "C1,C2F,C3,C4,C5,REF")
+    if not a.full:  # a plain run times the headline config alone
+        names = ""
     for name in [n for n in names.split(",") if n]:
         es = spec_of(name)
         # at least 50 frames (10 at 4 spp: C5 is ~4.4 ms per frame on one GPU): with the driver's 20 steps a quarter
@@ -978,7 +1025,7 @@ def main(argv=None) -> int:
                           "tile_balance": x["tile_balance"], "phases": x["phases"],
                           "aabb_tests_per_ray_rank0": round(st["aabb_tests"] / rays, 2) if not distributed else None,
                           "node_fetches": int(st["node_fetches"]), "tri_fetches": int(st["tri_fetches"])})
-    if not distributed and (a.extra is None) and isinstance(be, HipBackend):
+    if a.full and not distributed and (a.extra is None) and isinstance(be, HipBackend):
         extra.append(be.raster(scenes.config("REF"), max(5, a.steps // 4), 2))
 
     if rank == 0:
@@ -986,10 +1033,12 @@ def main(argv=None) -> int:
         value = r["rays_step"] * a.steps / r["tmax"] / 1e6
         st = r["stats"]
         cpu = None
-        if not distributed and not a.no_cpu_baseline:
+        if a.full and not distributed and not a.no_cpu_baseline:
             cpu = cpu_baseline(spec, a.cpu_seconds)
-        rf = roofline(spec.name, st, W * r["rows_local"], r["kernel_ms"], a.schedule)
-        if distributed:
+        rf = None
+        if a.full:
+            rf = roofline(spec.name, st, W * r["rows_local"], r["kernel_ms"], a.schedule)
+        if rf and distributed:
             rf["note"] = "rank 0's strip render alone, timed back to back after the timed region"
         out = {
             "metric": "Mrays/sec (primary+shadow) at 1080p",
@@ -998,6 +1047,7 @@ def main(argv=None) -> int:
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": round(r["tmax"] / a.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong" if strips else "weak",
@@ -1021,7 +1071,7 @@ def main(argv=None) -> int:
                        "frames_in_flight": r["in_flight"], "in_flight_ms_rank0": r["in_flight_ms"],
                        # one frame alone on one stream, back to back (this rank's render; at N = 1 without strips
                        # this is SURVEY 8(d)'s frame latency: enqueue -> complete)
-                       "frame_ms_one_stream": round(r["kernel_ms"], 4),
+                       "frame_ms_one_stream": None if r["kernel_ms"] is None else round(r["kernel_ms"], 4),
                        "frame_ms_one_stream_is_latency": not strips,
                        "tile_balance": r["tile_balance"],
                        "settle_ms": a.settle_ms, "resettle_ms": a.resettle_ms},

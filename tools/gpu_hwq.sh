@@ -15,7 +15,7 @@ done
 cd "$R"
 for q in 4 8 4 8; do
   export GPU_MAX_HW_QUEUES=$q
-  timeout -k 10 300 python3 -u bench.py --steps 200 --warmup 20 --no-cpu-baseline --extra C2F,C4 > "$O/bench_${TAG}_q$q.json" 2> "$O/bench_${TAG}_q$q.err" \
+  timeout -k 10 300 python3 -u bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --extra C2F,C4 > "$O/bench_${TAG}_q$q.json" 2> "$O/bench_${TAG}_q$q.err" \
     || { echo "bench q$q failed"; tail -5 "$O/bench_${TAG}_q$q.err"; exit 1; }
   python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print('q$q', d['value'], d['ms_per_step'], d['config'].get('frame_ms_one_stream'), [(e.get('config'), e.get('frame_ms')) for e in d.get('extra', [])])" "$O/bench_${TAG}_q$q.json"
 done

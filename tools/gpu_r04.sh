@@ -15,7 +15,7 @@ for step in ${STEPS:-tests}; do
         > "$O/gputest_${TAG}.log" 2>&1 || { echo "gpu tests failed rc=$?"; tail -40 "$O/gputest_${TAG}.log"; exit 1; }
       tail -3 "$O/gputest_${TAG}.log" ;;
     bench)
-      timeout -k 10 600 python3 bench.py > "$O/bench_${TAG}.json" 2> "$O/bench_${TAG}.err" \
+      timeout -k 10 600 python3 bench.py --full > "$O/bench_${TAG}.json" 2> "$O/bench_${TAG}.err" \
         || { echo "bench failed rc=$?"; tail -20 "$O/bench_${TAG}.err"; exit 1; }
       head -c 1500 "$O/bench_${TAG}.json"; echo ;;
     balance)

@@ -15,7 +15,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -3 "$O/gputest_${TAG}.log"
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout -k 10 600 python3 bench.py > "$O/bench_${TAG}.json" 2> "$O/bench_${TAG}.err" \
+  timeout -k 10 600 python3 bench.py --full > "$O/bench_${TAG}.json" 2> "$O/bench_${TAG}.err" \
     || { echo "bench failed rc=$?"; tail -20 "$O/bench_${TAG}.err"; exit 1; }
   echo "bench ok"
 fi
