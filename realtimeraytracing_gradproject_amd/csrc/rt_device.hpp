@@ -28,6 +28,23 @@
 #ifndef RT_LDS_TOP
 #define RT_LDS_TOP 0        // > 0: the top RT_LDS_TOP BFS nodes of the largest BLAS staged in LDS per packet workgroup
 #endif
+// Stale stack entries of the packet schedule's closest-hit walk are dropped on pop (rt_trace.hip, pop_cull_dead;
+// DESIGN §3.2): 0 keeps the plain pop. The counting (STATS) kernels keep the plain walk, so their counters stay the
+// oracle's packet emulation's, unless RT_POP_CULL_STATS is set (the popcullstats variant of tests/test_gpu_pop_cull.py).
+#ifndef RT_POP_CULL
+#define RT_POP_CULL 1
+#endif
+#ifndef RT_POP_CULL_STATS
+#define RT_POP_CULL_STATS 0
+#endif
+// The BLAS entries are checked too (the popcullblas variant): C2 -3.8 % instead of -1.9 % with the TLAS entries alone,
+// but C4 +1.0 ... +1.6 % and C5 +0.3 ... +0.5 % (the per-push minimum and LDS write where few pops are stale), so off.
+#ifndef RT_POP_CULL_BLAS
+#define RT_POP_CULL_BLAS 0
+#endif
+#ifndef RT_POP_CULL_SLOTS
+#define RT_POP_CULL_SLOTS 8  // stack slots (from the bottom) whose entries are checked: 512 B of LDS each per workgroup
+#endif
 
 namespace rt {
 

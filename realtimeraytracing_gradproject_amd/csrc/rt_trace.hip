@@ -383,6 +383,55 @@ struct PacketRay {
   V3 o[R], d[R], invd[R], noinv[R];
 };
 
+// Pop cull (RT_POP_CULL): the closest-hit walk drops a stack entry on pop when no lane can still take
+// a hit under it. Every pushed entry keeps one float per lane: the lane's entry distance n of the pushed child (the
+// minimum over the pending children of a BLAS entry: conservative for each), +inf where the lane's slab test
+// rejected it. On pop, a lane with n > hit.t * 1.0000004f rejects every box under the entry: nested boxes are exact
+// float min / max unions and the fma is monotone in the plane, so their entry distances are >= n bit for bit and the
+// slab test (n <= min(far, t) * 1.0000004f) fails with the same operations; a lane that did not enter at push time
+// had a larger t then. When that holds for every lane the visit changes no hit record (packet_tri gives a lane a
+// hit only in a triangle whose own slot box it accepted) and the entry is dropped with no node or instance loaded.
+// Dead rays carry t = -inf and fail the test on their own.
+// The floats live in LDS, [stack slot][thread of the workgroup], for the lowest kPopCullSlots slots of the wave's
+// stack (the entries nearest the roots stay pending longest and go stale most often); deeper entries are pushed
+// and popped unchecked. 4 KB per workgroup: 32 one-wave workgroups per CU fit in 128 KB of its 160 KB, so the
+// kernels keep their 8 waves per SIMD. Not combined with the other LDS users (RT_HYBRID_T, RT_LDS_TOP) nor with two
+// rays per lane. The counting kernels keep the plain walk: their counters are the un-culled walk's, an upper bound on
+// the plain kernels' fetches. By default only the TLAS entries (pending instances and TLAS nodes) are checked; the
+// BLAS entries too under RT_POP_CULL_BLAS (measured: rt_device.hpp).
+#if RT_POP_CULL && !RT_HYBRID_T && !RT_LDS_TOP && RT_PACKET_RAYS == 1
+#define RT_POP_CULL_ON 1
+#else
+#define RT_POP_CULL_ON 0
+#endif
+constexpr int kPopCullSlots = RT_POP_CULL_SLOTS;
+constexpr int kPopCullThreads = 128;  // threads of the largest packet workgroup (checked below packet_block)
+#if RT_POP_CULL_ON
+__shared__ float g_pcull[kPopCullSlots][kPopCullThreads];
+#endif
+template <bool ANY_HIT, bool STATS, int R>
+__device__ constexpr bool pop_cull() {
+  return RT_POP_CULL_ON && !ANY_HIT && R == 1 && (!STATS || RT_POP_CULL_STATS);
+}
+// ... and of the BLAS entries among them (RT_POP_CULL_BLAS 0: the TLAS entries alone are checked)
+template <bool ANY_HIT, bool STATS, int R>
+__device__ constexpr bool pop_cull_blas() {
+  return pop_cull<ANY_HIT, STATS, R>() && RT_POP_CULL_BLAS;
+}
+// the entry pushed to `slot` (uniform): this lane's entry distance
+__device__ __forceinline__ void pop_cull_put(int slot, float n) {
+#if RT_POP_CULL_ON
+  if (slot < kPopCullSlots) g_pcull[slot][threadIdx.x] = n;
+#endif
+}
+// true when the entry in `slot` (uniform) is stale for every lane of the wave
+__device__ __forceinline__ bool pop_cull_dead(int slot, const HitRec& h) {
+#if RT_POP_CULL_ON
+  if (slot < kPopCullSlots) return wave_ballot(g_pcull[slot][threadIdx.x] <= h.t * 1.0000004f) == 0;
+#endif
+  return false;
+}
+
 // Triangle leaf for every live ray (uniform triangle, scalar loads). ANY_HIT: a ray that accepts
 // a hit leaves the packet. Branch-free: selects instead of exec-mask regions.
 // own[r]: the lanes whose ray r accepted this triangle's slot box (the node's ballot for the slot). Only they may
@@ -536,7 +585,12 @@ __device__ __forceinline__ bool packet_tlas_node(const RT_CONST char* pool, int 
   // pushed to the spare lane)
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    if ((P >> k) & 1u) stk.put(sp + __builtin_popcount(P >> (k + 1)), cref[k]);
+    if ((P >> k) & 1u) {
+      const int slot = sp + __builtin_popcount(P >> (k + 1));
+      stk.put(slot, cref[k]);
+      // vkey is the lane's |n| (n >= tmin >= 0: n itself up to the sign of a zero), +inf where it rejected child k
+      if (pop_cull<ANY_HIT, STATS, R>()) pop_cull_put(slot, __uint_as_float(vkey[0][k]));
+    }
   sp = __builtin_amdgcn_readfirstlane(sp + __builtin_popcount(P));  // uniform by construction: an SGPR
   next = rb;
   return true;
@@ -806,13 +860,24 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
         // keys elsewhere), lowest slot on ties, and that child's ref (first_inner + slot: internal
         // children sit in the lowest slots), packed as ref << 2 | slot; the lead lane's answer, one
         // readlane, is the packet's
-        uint32_t idx = 0;
+        uint32_t idx = 0, m1 = 0, m2 = 0;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           uint32_t kk[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) kk[k] = key_if_entered(vkey[r][k], ent, k);
-          const uint32_t m = min(min(kk[0], kk[1]), min(kk[2], kk[3]));
+          uint32_t m;
+          if (pop_cull_blas<ANY_HIT, STATS, R>()) {
+            // the lane's smallest and second smallest key (the second of the four is the median of the two pairs'
+            // minima and the smaller of their maxima)
+            const uint32_t lo01 = min(kk[0], kk[1]), hi01 = max(kk[0], kk[1]);
+            const uint32_t lo23 = min(kk[2], kk[3]), hi23 = max(kk[2], kk[3]);
+            m = min(lo01, lo23);
+            asm("v_med3_u32 %0, %1, %2, %3" : "=v"(m2) : "v"(lo01), "v"(lo23), "v"(min(hi01, hi23)));
+            m1 = m;
+          } else {
+            m = min(min(kk[0], kk[1]), min(kk[2], kk[3]));
+          }
           const uint32_t ir = kk[0] == m ? 0u : kk[1] == m ? 1u : kk[2] == m ? 2u : 3u;
           const uint32_t pr = (((uint32_t)ch[5] + ir) << 2) | ir;
           idx = (r == 0 || pl.lead_r == (uint32_t)r) ? pr : idx;
@@ -820,6 +885,12 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
         const uint32_t pk = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)pl.lead_l);
         ib = pk & 3u;
         nref = pk >> 2;
+        // Pop cull: the entry pushed below (two or more entered, so some child stays pending) goes to slot sp with
+        // the lane's smallest key over the pending children, the entered ones but the packet's choice `ib`: the
+        // lane's own smallest where its choice is another child (idx != pk: that child stays pending), else its
+        // second smallest. Unsigned order is float order on |n| and +inf; two keys at least are distances, so the
+        // all-ones keys of the children not entered are never stored.
+        if (pop_cull_blas<ANY_HIT, STATS, R>()) pop_cull_put(sp, __uint_as_float(idx == pk ? m2 : m1));
       }
       if (STATS && (ent & ~(1u << ib)) && sp + 1 > cap)  // never: cap bounds the entries (one per level)
 #pragma unroll
@@ -827,7 +898,14 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
       stk.v = push_entry(stk.v, sp, (uint32_t)ch[7], ent, 1u << ib);
       bref = (int)nref;
     } else {
+      // stale entries go first: t only shrinks, so an entry that fails the check once fails it for each of its
+      // pending slots, and the whole entry is dropped at its first pop
+    pop:
       if (sp == base) return true;
+      if (pop_cull_blas<ANY_HIT, STATS, R>() && pop_cull_dead(sp - 1, hit[0])) {
+        --sp;
+        goto pop;
+      }
       // top entry: its lowest pending slot is next; the entry stays while slots remain
       bref = pop_entry(stk.v, sp);
     }
@@ -919,8 +997,12 @@ __device__ __forceinline__ void packet_walk(const SceneView& sc, const V3* o, co
       if (ANY_HIT && !more) return;
     }
     if (!descend) {
+    pop:
       if (sp == 0) return;
-      ref = stk.get(--sp);
+      --sp;
+      // a stale TLAS entry is not visited: no instance fetch, no ray transform, no BLAS root
+      if (pop_cull<ANY_HIT, STATS, R>() && pop_cull_dead(sp, hit[0])) goto pop;
+      ref = stk.get(sp);
     }
   }
 }
@@ -1546,6 +1628,9 @@ __host__ __device__ constexpr int packet_wy(int ks) { return ks > 1 ? 1 : RT_PAC
 __host__ __device__ constexpr int packet_block(int ks) { return 64 * packet_wx(ks) * packet_wy(ks); }
 static_assert(packet_block(1) <= 64 * kMaxPacketWaves && packet_block(2) <= 64 * kMaxPacketWaves,
               "lane_subtree's LDS stacks: one per wave of a packet workgroup");
+static_assert(packet_block(0) <= kPopCullThreads && packet_block(1) <= kPopCullThreads &&
+                  packet_block(2) <= kPopCullThreads,
+              "the pop cull's LDS rows: one float per thread of a packet workgroup");
 
 // BAL: the launch runs a tile-balance work list or records the waves' times (FrameParams::plan / cost); the plain
 // grid's kernel carries none of it (a 64-bit start time and the slot live across the whole walk cost registers).
