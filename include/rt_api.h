@@ -26,6 +26,8 @@
 extern "C" {
 #endif
 
+/* Still 4: rt_set_triangle_test, rt_host_trace_triangles and the RT_TRIANGLE_TEST_* constants were added without
+ * changing any existing entry point, structure or default (backward compatible additions). */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -103,7 +105,7 @@ enum {
   RT_STAT_PRIMARY_RAYS = 0,
   RT_STAT_SHADOW_RAYS = 1,
   RT_STAT_AABB_TESTS = 2,  /* child-box slab tests (one per valid child of a visited node) */
-  RT_STAT_TRI_TESTS = 3,   /* Moller-Trumbore tests */
+  RT_STAT_TRI_TESTS = 3,   /* ray / triangle tests (Moller-Trumbore, or watertight: rt_set_triangle_test) */
   RT_STAT_INSTANCE_ENTRIES = 4,
   RT_STAT_STACK_OVERFLOWS = 5,
   RT_STAT_PIXELS = 6,
@@ -227,6 +229,25 @@ rt_status rt_tile_balance_info(rt_ctx_t ctx, uint32_t out[RT_BALANCE_INFO_COUNT_
 #define RT_CTX_COUNTERS_V2 5
 rt_status rt_ctx_counters_n(rt_ctx_t ctx, uint64_t* out, uint32_t n);
 rt_status rt_ctx_counters(rt_ctx_t ctx, uint64_t out[RT_CTX_COUNTERS]);
+/* The ray / triangle test of the trace kernels. DXR's fixed-function TraceRay is watertight: no ray passes between
+ * two triangles that share an edge. The default float32 Moller-Trumbore test is not (it stores v0, v1 - v0, v2 - v0,
+ * and v0 + e1 is not v1 in float32: tests/golden/seam_leaks.json pins the gap); it is the pinned, bit-checked path
+ * and stays the default, bit for bit. RT_TRIANGLE_TEST_WATERTIGHT selects the Woop / Benthin / Wald test (JCGT 2013)
+ * on vertex-form triangle records: per BLAS, a ray aimed at an edge whose two triangles hold bit-identical
+ * endpoint positions and lie on opposite sides of it (as the ray sees them) hits one of them. Hit distances and
+ * barycentrics differ from the default's in their last bits, so frames do too. */
+enum { RT_TRIANGLE_TEST_MOLLER_TRUMBORE = 0, RT_TRIANGLE_TEST_WATERTIGHT = 1 };
+/* Applies to every launch issued after the call (rt_dispatch_rays, rt_dispatch_frames, rt_trace_rays, the
+ * rt_render_strips* loop), in both schedules, all shade modes and every spp; any other value: RT_E_INVALID. The
+ * first switch to watertight on a scene waits for all in-flight work and builds the vertex-form records (one
+ * kernel per BLAS), like "a changed layout" in rt_tlas_build's contract; while the mode is on, an rt_tlas_build
+ * that lays the pool out again rebuilds them. Switching back costs nothing, and the records are kept. A watertight
+ * frame launch always takes the packet schedule's plain grid (no tile balance: rt_set_tile_balance has no effect
+ * on it) and renders RT_SHADE_REF through the general kernel; rt_dispatch_frames and rt_render_strips_frames still
+ * render their frames in one launch, each equal to the frame rt_dispatch_rays renders. The environment variable
+ * RT_TRIANGLE_TEST=watertight, read once in rt_create, sets the context's initial value. Replaces: nothing to call
+ * in the reference (DXR's TraceRay is always watertight). */
+rt_status rt_set_triangle_test(rt_ctx_t ctx, int test);
 /* Enables device counters (rt_stats). Costs time: off for timed runs. */
 rt_status rt_set_stats(rt_ctx_t ctx, int enable);
 
@@ -453,6 +474,17 @@ void rt_camera_lookat(const float eye[3], const float center[3], const float up[
  * XMMatrixPerspectiveFovRH(fov_deg, W/H, znear, zfar), inverse(view), inverse(proj)}. */
 void rt_camera_buffer(const float view[16], uint32_t W, uint32_t H, float fov_deg, float znear,
                       float zfar, float cb[64]);
+
+/* rt_trace_rays on the host, by brute force over every triangle of ONE mesh under ONE instance transform: the check
+ * of the trace kernels' triangle tests (it calls the same intersection functions they call) and of the BVH (which
+ * must never cull a triangle the test accepts). vtx / vcount / stride / idx / icount as rt_blas_build (host arrays);
+ * object_to_world: 3x4 row-major, NULL = identity (singular: RT_E_INVALID), with the world-to-object inverse and
+ * the front-face flip derived as rt_tlas_build derives them; rays: n x 8 floats, ray_flags, hits (n x 4 words) and
+ * uv (n x 2 floats, or NULL) as rt_trace_rays, all host memory; the instance index is 0; closest hits follow the
+ * (t, instance, primitive) rule; triangle_test: RT_TRIANGLE_TEST_*. Null or mis-sized arguments: RT_E_INVALID. */
+rt_status rt_host_trace_triangles(const void* vtx, uint32_t vcount, uint32_t stride, const uint32_t* idx,
+                                  uint32_t icount, const float* object_to_world, const float* rays, uint32_t n,
+                                  uint32_t ray_flags, int triangle_test, uint32_t* hits, float* uv);
 
 /* ---- Camera manipulator ------------------------------------------------------------------------
  * nv_helpers_dx12::Manipulator (include/manipulator.h:33-148, src/manipulator.cpp) as plain data the

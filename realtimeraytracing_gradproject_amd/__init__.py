@@ -30,6 +30,7 @@ RT_OK, RT_E_INVALID, RT_E_OOM, RT_E_HIP, RT_E_RCCL, RT_E_UNSUPPORTED, RT_E_IO = 
 RT_HITGROUP_MODEL, RT_HITGROUP_SHADOW, RT_HITGROUP_PLANE = 0, 1, 2
 RT_SHADE_REF, RT_SHADE_LAMBERT_SHADOW, RT_SHADE_PRIMARY = 0, 1, 2
 RT_SCHED_PACKET, RT_SCHED_LANE = 0, 1
+RT_TRIANGLE_TEST_MOLLER_TRUMBORE, RT_TRIANGLE_TEST_WATERTIGHT = 0, 1
 RT_BALANCE_INFO_COUNT = 20
 RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH, RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES = 0x04, 0x10
 RT_RAY_FLAG_CULL_FRONT_FACING_TRIANGLES = 0x20
@@ -106,6 +107,7 @@ SIGNATURES = [
     ("rt_tile_balance_info_n", _I, [_P, _UP, _U32]),
     ("rt_ctx_counters", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("rt_ctx_counters_n", _I, [_P, ctypes.POINTER(ctypes.c_uint64), _U32]),
+    ("rt_set_triangle_test", _I, [_P, _I]),
     ("rt_set_stats", _I, [_P, _I]),
     ("rt_dispatch_rays", _I, [_P, _U32, _U32, _P, _U32, _P, _P, _P]),
     ("rt_dispatch_frames", _I, [_P, _U32, _U32, _U32, _P, _P, ctypes.c_uint64, _P]),
@@ -148,6 +150,7 @@ SIGNATURES = [
     ("rt_plane_vertices", None, [_FP]),
     ("rt_camera_lookat", None, [_FP, _FP, _FP, _FP]),
     ("rt_camera_buffer", None, [_FP, _U32, _U32, ctypes.c_float, ctypes.c_float, ctypes.c_float, _FP]),
+    ("rt_host_trace_triangles", _I, [_P, _U32, _U32, _P, _U32, _P, _P, _U32, _U32, _I, _P, _P]),
     ("rt_manip_init", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_update", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_set_lookat", None, [ctypes.POINTER(rt_manipulator), _FP, _FP, _FP]),
@@ -278,6 +281,34 @@ def camera_buffer(view, width: int, height: int, fov_deg: float = 45.0, znear: f
     out = np.zeros(64, np.float32)
     lib.rt_camera_buffer(_fptr(v), width, height, fov_deg, znear, zfar, _fptr(out))
     return out
+
+
+def host_trace_triangles(vertices, indices, rays, triangle_test: int = RT_TRIANGLE_TEST_MOLLER_TRUMBORE,
+                         object_to_world=None, any_hit: bool = False, cull_back: bool = False,
+                         cull_front: bool = False):
+    """rt_host_trace_triangles: rt_trace_rays on the host, brute force over one mesh under one instance transform
+    (no GPU). vertices: (nv, k >= 3) floats, position first; indices: uint32 triangle list or None; rays: (n, 8)
+    floats (o, tmin, d, tmax); object_to_world: 12 floats (3x4 row-major) or None. Returns (hits (n, 4) uint32:
+    t bits, instance 0, primitive, flag; uv (n, 2) float32)."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    if v.ndim != 2:
+        v = v.reshape(-1, 6)
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    n = r.shape[0]
+    i = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+    x = None if object_to_world is None else _f32(object_to_world, 12)
+    flags = (RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH if any_hit else 0) | \
+        (RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES if cull_back else 0) | \
+        (RT_RAY_FLAG_CULL_FRONT_FACING_TRIANGLES if cull_front else 0)
+    hits = np.zeros((n, 4), np.uint32)
+    uv = np.zeros((n, 2), np.float32)
+    st = lib.rt_host_trace_triangles(v.ctypes.data_as(_P), v.shape[0], v.shape[1] * 4,
+                                     None if i is None else i.ctypes.data_as(_P), 0 if i is None else i.size,
+                                     None if x is None else x.ctypes.data_as(_P), r.ctypes.data_as(_P), n, flags,
+                                     triangle_test, hits.ctypes.data_as(_P), uv.ctypes.data_as(_P))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_trace_triangles")
+    return hits, uv
 
 
 class Manipulator:
@@ -691,6 +722,10 @@ class Context:
 
     def set_schedule(self, schedule: int):
         self._check(self._lib.rt_set_schedule(self._h, schedule), "rt_set_schedule")
+
+    def set_triangle_test(self, mode: int):
+        """rt_set_triangle_test: RT_TRIANGLE_TEST_MOLLER_TRUMBORE (default) or RT_TRIANGLE_TEST_WATERTIGHT."""
+        self._check(self._lib.rt_set_triangle_test(self._h, mode), "rt_set_triangle_test")
 
     def set_tile_rows(self, rows: int):
         """rt_set_tile_rows: 8 (8 x 8 pixel tiles per wave, default) or 4 (8 x 4)."""

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/rt_api.h"
@@ -297,6 +298,13 @@ struct rt_ctx {
   rt::Bvh4Node* pool_nodes = nullptr;
   rt::TriRec* pool_tris = nullptr;
   size_t pool_nodes_cap = 0, pool_tris_cap = 0;
+  // rt_set_triangle_test: the watertight mode's vertex-form records, pooled like pool_tris (the same tri_base).
+  // Built lazily: on the first switch to the mode once a scene pool exists, and by every layout-changing
+  // rt_tlas_build while the mode is on; pool_vtx_gen is the blas_gen they were built for.
+  int tri_test = RT_TRIANGLE_TEST_MOLLER_TRUMBORE;
+  rt::TriVtx* pool_vtx = nullptr;
+  size_t pool_vtx_cap = 0;
+  uint64_t pool_vtx_gen = ~0ull;
   bool tlas_stale = false;  // a BLAS was rebuilt after the last rt_tlas_build
   // raster fallback scratch (grown on demand)
   rt::RasterScratch raster;
@@ -472,6 +480,33 @@ rt_status upload_blas(rt_ctx* c, DeviceBlas& b, const void* vtx, uint32_t vcount
 
 hipStream_t pick_stream(rt_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
 
+// The watertight mode's vertex-form pool for the current pool layout (node_base / tri_base of pool_gen): one
+// k_tri_vertices launch per BLAS on the context stream, into [BLAS 0 | BLAS 1 ..] like pool_tris. The caller has
+// made sure nothing in flight reads the pool (rt_tlas_build's layout change has quiesced; rt_set_triangle_test
+// does so itself); returns once the records are written.
+rt_status build_vertex_pool(rt_ctx* c) {
+  // the BLASes the pool was laid out for (one built since, not yet in any TLAS, has no slots until rt_tlas_build)
+  const size_t nblas = std::min(c->blas.size(), c->tri_base.size());
+  size_t pool_t = 0;
+  for (size_t k = 0; k < nblas; ++k) pool_t += c->blas[k].ntri;
+  if (pool_t > c->pool_vtx_cap) {
+    if (c->pool_vtx) (void)hipFree(c->pool_vtx);
+    c->pool_vtx = nullptr;
+    c->pool_vtx_cap = 0;
+    HIPCHK(c, hipMalloc(&c->pool_vtx, pool_t * sizeof(rt::TriVtx)), "hipMalloc(vertex-form triangle pool)");
+    c->pool_vtx_cap = pool_t;
+  }
+  hipError_t e = hipSuccess;
+  for (size_t k = 0; k < nblas && e == hipSuccess; ++k) {
+    const DeviceBlas& b = c->blas[k];
+    e = rt::blas_vertex_records(b.tris, b.vtx, b.idx, b.ntri, c->pool_vtx + c->tri_base[k], c->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return hip_fail(c, e, "vertex-form triangle pool");
+  c->pool_vtx_gen = c->pool_gen;
+  return RT_OK;
+}
+
 
 }  // namespace
 
@@ -516,6 +551,9 @@ rt_status rt_create(int hip_device, rt_ctx_t* out) {
   if (const char* ev = std::getenv("RT_BALANCE_PRIO")) c->bal_prio = std::strtoul(ev, nullptr, 10) ? 1u : 0u;
   if (const char* ev = std::getenv("RT_BALANCE_FINE")) c->bal_fine = std::strtoul(ev, nullptr, 10) ? 1u : 0u;
   if (const char* ev = std::getenv("RT_BALANCE_FORCED_CAP")) c->bal_forced_cap = (uint32_t)std::strtoul(ev, nullptr, 10);
+  // the context's initial triangle test (rt_set_triangle_test): existing tools run in the watertight mode unchanged
+  if (const char* ev = std::getenv("RT_TRIANGLE_TEST"))
+    if (std::strcmp(ev, "watertight") == 0) c->tri_test = RT_TRIANGLE_TEST_WATERTIGHT;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&c->d_stats, RT_STAT_COUNT * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(c->d_stats, 0, RT_STAT_COUNT * sizeof(unsigned long long)) != hipSuccess) {
@@ -542,6 +580,7 @@ rt_status rt_destroy(rt_ctx_t c) {
   if (c->raster_ev) (void)hipEventDestroy(c->raster_ev);
   if (c->pool_nodes) (void)hipFree(c->pool_nodes);
   if (c->pool_tris) (void)hipFree(c->pool_tris);
+  if (c->pool_vtx) (void)hipFree(c->pool_vtx);
   for (void* p : {(void*)c->raster.clip, (void*)c->raster.slots, (void*)c->raster.tiles, (void*)c->raster.tcount,
                   (void*)c->raster.toffs, (void*)c->raster.bins, (void*)c->raster.bsum, (void*)c->raster.draws})
     if (p) (void)hipFree(p);
@@ -733,6 +772,16 @@ rt_status rt_tlas_build(rt_ctx_t c, const rt_instance* in, uint32_t n, int updat
     }
     c->pool_tlas_cap = slot_cap;
     c->pool_gen = c->blas_gen;
+    // watertight mode: the vertex-form records of the new layout (nothing is in flight here)
+    if (c->tri_test == RT_TRIANGLE_TEST_WATERTIGHT) {
+      const rt_status st = build_vertex_pool(c);
+      if (st != RT_OK) return st;
+    }
+  } else if (c->tri_test == RT_TRIANGLE_TEST_WATERTIGHT && c->pool_vtx_gen != c->pool_gen) {
+    // the mode was switched on while no scene was current (a failed build): the records are still missing
+    HIPCHK(c, quiesce(c), "rt_tlas_build: wait for in-flight work");
+    const rt_status st = build_vertex_pool(c);
+    if (st != RT_OK) return st;
   }
   // the version launches do not read now
   const int w = c->cur >= 0 ? 1 - c->cur : 0;
@@ -896,6 +945,22 @@ rt_status rt_tile_balance_info(rt_ctx_t c, uint32_t out[RT_BALANCE_INFO_COUNT_V1
   return rt_tile_balance_info_n(c, out, RT_BALANCE_INFO_COUNT_V1);
 }
 
+rt_status rt_set_triangle_test(rt_ctx_t c, int test) {
+  if (!c) return RT_E_INVALID;
+  if (test != RT_TRIANGLE_TEST_MOLLER_TRUMBORE && test != RT_TRIANGLE_TEST_WATERTIGHT)
+    return fail(c, RT_E_INVALID, "rt_set_triangle_test: unknown triangle test");
+  if (test == RT_TRIANGLE_TEST_WATERTIGHT && c->cur >= 0 && !c->tlas_stale && c->pool_vtx_gen != c->pool_gen) {
+    // the first switch on this scene: the vertex-form records of the pool's layout (a stale or missing scene gets
+    // them from the rt_tlas_build that must follow anyway)
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, quiesce(c), "rt_set_triangle_test: wait for in-flight work");
+    const rt_status st = build_vertex_pool(c);
+    if (st != RT_OK) return st;
+  }
+  c->tri_test = test;
+  return RT_OK;
+}
+
 rt_status rt_set_stats(rt_ctx_t c, int enable) {
   if (!c) return RT_E_INVALID;
   c->stats_on = enable != 0;
@@ -906,7 +971,10 @@ static rt::SceneView scene_view(rt_ctx* c) {
   rt::SceneView sv;
   const TlasVersion& v = c->ver[c->cur];
   sv.pool_nodes = c->pool_nodes;
-  sv.pool_tris = c->pool_tris;
+  // the launchers pick the watertight instantiations by tri_test; they read the vertex-form pool
+  sv.tri_test = c->tri_test;
+  if (c->tri_test == RT_TRIANGLE_TEST_WATERTIGHT) sv.pool_vtx = c->pool_vtx;
+  else sv.pool_tris = c->pool_tris;
   sv.tlas = v.nodes;
   sv.inst = v.inst;
   sv.tlas_root = (int)v.pool_base;
@@ -1324,7 +1392,8 @@ rt_status dispatch_frame(rt_ctx* c, uint32_t W, uint32_t H, const uint32_t* d_ro
     return fail(c, RT_E_UNSUPPORTED, "tile balance: forced layouts take at most 32768 waves per launch");
   // launches of more waves than the plan kernel holds run the plain grid (they are many rounds of the GPU's wave
   // slots deep: the slowest tile is a small part of them, C5's 518,400 waves)
-  if (c->balance && g.packet && g.plannable && (forced || !c->stats_on) &&
+  // (a watertight launch always takes the plain grid: launch_trace_frame)
+  if (c->balance && g.packet && g.plannable && (forced || !c->stats_on) && !sv.tri_test &&
       (uint64_t)g.waves_per_frame * nframes <= rt::kPlanMaxTiles) {
     const uint32_t ntiles = g.waves_per_frame * nframes;
     hipError_t be;
@@ -1643,6 +1712,108 @@ rt_status rt_trace_rays(rt_ctx_t c, const float* rays, uint32_t n, uint32_t ray_
   if (e != hipSuccess) return hip_fail(c, e, "trace_rays launch");
   HIPCHK(c, note_reader(c->ver[c->cur], s), "rt_trace_rays: record use");
   if (ovf_slot) HIPCHK(c, slot_mark_use(*ovf_slot, s), "overflow stack: record use");
+  return RT_OK;
+}
+
+// Host service: rt_trace_rays by brute force over one mesh under one instance transform, with the intersection
+// functions of rt_device.hpp the kernels call (their host side: the same operations, -ffp-contract=off). Lives
+// here, not in rt_host.cpp, because rt_device.hpp needs the HIP compiler. No context, no GPU call.
+rt_status rt_host_trace_triangles(const void* vtx, uint32_t vcount, uint32_t stride, const uint32_t* idx,
+                                  uint32_t icount, const float* object_to_world, const float* rays, uint32_t n,
+                                  uint32_t ray_flags, int triangle_test, uint32_t* hits, float* uv) {
+  if (!vtx || vcount == 0 || stride < 12 || (stride % 4) || (!rays && n) || (!hits && n)) return RT_E_INVALID;
+  if (triangle_test != RT_TRIANGLE_TEST_MOLLER_TRUMBORE && triangle_test != RT_TRIANGLE_TEST_WATERTIGHT)
+    return RT_E_INVALID;
+  if (ray_flags & ~(uint32_t)(RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH | RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES |
+                              RT_RAY_FLAG_CULL_FRONT_FACING_TRIANGLES))
+    return RT_E_INVALID;
+  const bool cull_back = (ray_flags & RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES) != 0;
+  const bool cull_front = (ray_flags & RT_RAY_FLAG_CULL_FRONT_FACING_TRIANGLES) != 0;
+  if (cull_back && cull_front) return RT_E_INVALID;
+  uint32_t ntri;
+  if (idx) {
+    if (icount == 0 || icount % 3) return RT_E_INVALID;
+    for (uint32_t i = 0; i < icount; ++i)
+      if (idx[i] >= vcount) return RT_E_INVALID;
+    ntri = icount / 3;
+  } else {
+    if (vcount % 3) return RT_E_INVALID;
+    ntri = vcount / 3;
+  }
+  // the instance record rt_tlas_build derives: world-to-object inverse, flip, translate
+  const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  rt::InstanceRec ir;
+  std::memset(&ir, 0, sizeof(ir));
+  if (!fill_instance_xform(object_to_world ? object_to_world : I, ir)) return RT_E_INVALID;
+  const bool any_hit = (ray_flags & RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH) != 0;
+  const float face = (cull_back || cull_front) ? (ir.flip ? -1.0f : 1.0f) * (cull_front ? -1.0f : 1.0f) : 0.0f;
+  const unsigned char* vb = (const unsigned char*)vtx;
+  auto vertex = [&](uint32_t i) {
+    const float* p = (const float*)(vb + (size_t)i * stride);
+    return rt::v3(p[0], p[1], p[2]);
+  };
+  auto trace_range = [&](uint32_t first, uint32_t last) {
+  for (uint32_t i = first; i < last; ++i) {
+    const float* r = rays + (size_t)i * 8;
+    const rt::V3 o = rt::v3(r[0], r[1], r[2]), d = rt::v3(r[4], r[5], r[6]);
+    const float tmin = r[3], tmax = r[7];
+    const rt::V3 ro = rt::inst_point(ir.w2o, ir.translate, o), rd = rt::inst_dir(ir.w2o, ir.translate, d);
+    const rt::WtRay wr = rt::wt_ray(rd);
+    float best_t = tmax, best_u = 0.0f, best_v = 0.0f;
+    uint32_t best_inst = 0xffffffffu, best_prim = 0xffffffffu;
+    bool found = false;
+    for (uint32_t p = 0; p < ntri; ++p) {
+      const rt::V3 A = vertex(idx ? idx[3 * p] : 3 * p), B = vertex(idx ? idx[3 * p + 1] : 3 * p + 1),
+                   C = vertex(idx ? idx[3 * p + 2] : 3 * p + 2);
+      float t, u, v;
+      const bool ok = triangle_test == RT_TRIANGLE_TEST_WATERTIGHT
+                          ? rt::watertight(ro, wr, A, B, C, face, t, u, v)
+                          : rt::moller_trumbore(ro, rd, A, rt::sub(B, A), rt::sub(C, A), face, t, u, v);  // TriRec's e1, e2
+      if (!(ok && t >= tmin)) continue;
+      // the (t, instance, primitive) rule of the walks, with instance 0
+      const bool better = t < best_t || (t == best_t && (0u < best_inst || (0u == best_inst && p < best_prim)));
+      if (!better) continue;
+      best_t = t;
+      best_u = u;
+      best_v = v;
+      best_inst = 0u;
+      best_prim = p;
+      found = true;
+      if (any_hit) break;
+    }
+    uint32_t* h = hits + (size_t)i * 4;
+    std::memcpy(&h[0], found ? &best_t : &tmax, 4);
+    h[1] = found ? best_inst : 0xffffffffu;
+    h[2] = found ? best_prim : 0xffffffffu;
+    h[3] = found ? 1u : 0u;
+    if (uv) {
+      uv[(size_t)i * 2] = found ? best_u : 0.0f;
+      uv[(size_t)i * 2 + 1] = found ? best_v : 0.0f;
+    }
+  }
+  };
+  // rays are independent: large batches are split over a few host threads (each ray's result does not depend on it)
+  const uint64_t work = (uint64_t)n * ntri;
+  const uint32_t hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  const uint32_t nthreads = work < (1ull << 22) ? 1u : std::min<uint32_t>(hw, (n + 63u) / 64u);
+  if (nthreads <= 1) {
+    trace_range(0, n);
+    return RT_OK;
+  }
+  std::vector<std::thread> pool;
+  const uint32_t per = (n + nthreads - 1) / nthreads;
+  uint32_t done = 0;  // rays handed to a thread so far
+  try {
+    pool.reserve(nthreads);
+    for (uint32_t k = 0; k < nthreads && done < n; ++k) {
+      const uint32_t b = std::min(n, done + per);
+      pool.emplace_back(trace_range, done, b);
+      done = b;
+    }
+  } catch (...) {  // no exception crosses the boundary: a thread that could not start leaves its rays to the caller
+  }
+  trace_range(done, n);
+  for (auto& t : pool) t.join();
   return RT_OK;
 }
 

@@ -13,6 +13,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #define RT_HD __host__ __device__ __forceinline__
@@ -96,6 +97,19 @@ struct alignas(16) TriRec {
   uint32_t pad2;
 };
 static_assert(sizeof(TriRec) == 48, "TriRec must be 48 B");
+
+// Vertex-form triangle of the watertight test (RT_TRIANGLE_TEST_WATERTIGHT), 48 B, in the same leaf order as the
+// TriRec of the same slot: the three vertex positions exactly as given (two triangles that share an edge hold
+// bit-identical endpoints, which v0 + e1 does not give back in float32) and the original PrimitiveIndex().
+struct alignas(16) TriVtx {
+  float v0[3];
+  uint32_t prim;
+  float v1[3];
+  uint32_t pad1;
+  float v2[3];
+  uint32_t pad2;
+};
+static_assert(sizeof(TriVtx) == 48, "TriVtx must be 48 B");
 
 // Per-instance record read by the trace kernel (instance desc + InstanceProperties,
 // TopLevelASGenerator.cpp:180-198, Hit.hlsl:19-23).
@@ -239,12 +253,19 @@ RT_HD uint32_t plan_xwords(uint32_t cap, uint32_t wl) { return (plan_groups(cap,
 // planes of a node with no min/max.
 struct SceneView {
   const Bvh4Node* pool_nodes;
-  const TriRec* pool_tris;
+  // the triangle pool of the launch's triangle test: Moller-Trumbore records, or (tri_test 1, the watertight
+  // kernels) the vertex-form records, pooled alike ([BLAS 0 | BLAS 1 ..], the same 48-B slots and tri_base). One
+  // kernel-argument slot: the default kernels' arguments, and so their code, are what they were before the mode
+  union {
+    const TriRec* pool_tris;
+    const TriVtx* pool_vtx;
+  };
   const Bvh4Node* tlas;
   const InstanceRec* inst;
   int stack_cap;       // worst-case entries per lane (exact bound from the trees)
   int packet_cap;      // worst-case entries of the wave-packet stack (TLAS siblings + BLAS levels)
   int lds_cap;         // entries kept in LDS ([entry][lane])
+  int tri_test;        // RT_TRIANGLE_TEST_*: read by the launchers only (it occupies what was padding)
   int* ovf;            // HBM overflow area, [entry - lds_cap][global lane], or null
   uint32_t ovf_lanes;  // lanes of the launch (overflow row pitch)
   float cull_sense;    // culling traces: +1 culls back faces, -1 front faces (DXR ray flags 0x10 / 0x20)
@@ -256,6 +277,7 @@ struct SceneView {
   int lds_n;     // nodes each packet workgroup copies into LDS (0: none)
 #endif
 };
+static_assert(sizeof(void*) != 8 || offsetof(SceneView, ovf) == 48, "tri_test fills the padding before ovf");
 
 // ------------------------------------------------------------------------------------------
 // Scalar float helpers (no contraction; identical to oracle/rt_oracle.c)
@@ -511,6 +533,127 @@ RT_HD bool moller_trumbore_flat(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float face, flo
   // u + v <= 1). min(u, v) >= 0 is u >= 0 and v >= 0 for non-NaN u, v (-0 included); a NaN one (the min returns
   // the other) fails u + v <= 1 anyway (tests/test_acceptance.py).
   return (det != 0.0f) & !culled(det, face) & (__builtin_fminf(u, v) >= 0.0f) & (u + v <= 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------
+// Watertight triangle test (RT_TRIANGLE_TEST_WATERTIGHT): Woop / Benthin / Wald, "Watertight Ray/Triangle
+// Intersection", JCGT 2013, on the vertex-form records (TriVtx). The ray is sheared onto its dominant axis kz
+// (the argmax of |d|, the lowest axis on ties; kx = (kz + 1) % 3, ky = (kx + 1) % 3, swapped when d[kz] < 0), and the
+// three edge functions are evaluated UNFUSED (two rounded products, one rounded difference): the neighbouring
+// triangle visits a shared edge with its endpoints in the other order and gets exactly the negated value, so no ray
+// passes between two triangles whose shared edge has bit-identical endpoints. An edge function that is exactly 0 is
+// decided in double (products of floats are exact there). No fused multiply-add anywhere in the test: the tests
+// restate it in numpy float32, which rounds every operation.
+//
+// The kx / ky swap is not carried out: with the axes left in cyclic order, negating the sheared x of every vertex
+// gives bit for bit the swapped edge functions (products commute, (-m1) - (-m2) rounds as m2 - m1, and a difference
+// of equal values is +0 either way), in float and in the double fallback alike. It costs one sign flip per vertex
+// instead of a select per coordinate, and the per-ray constants keep one layout.
+// ------------------------------------------------------------------------------------------
+struct WtRay {
+  int kz;         // dominant axis of the (object-space) direction
+  uint32_t flip;  // 0x80000000 when d[kz] < 0 (the swap of kx and ky, applied as a sign), else 0
+  float Sx, Sy, Sz;  // d[kx] / d[kz], d[ky] / d[kz], 1 / d[kz] (IEEE quotients; kx, ky in cyclic order)
+  bool ok;        // the direction is finite and not all zero; otherwise the ray hits nothing
+};
+
+// component k of a vector, and the (kx, ky, kz) components for a dominant axis: KZ 0 .. 2 fixed at compile time (the
+// packet leaf's uniform-axis path: a vertex held in SGPRs is read directly), KZ < 0 per lane by selects
+template <int KZ>
+RT_HD void wt_axes(V3 p, int kz, float& x, float& y, float& z) {
+  if (KZ == 0) {
+    x = p.y, y = p.z, z = p.x;
+  } else if (KZ == 1) {
+    x = p.z, y = p.x, z = p.y;
+  } else if (KZ == 2) {
+    x = p.x, y = p.y, z = p.z;
+  } else {
+    const bool k0 = kz == 0, k1 = kz == 1;
+    x = k0 ? p.y : (k1 ? p.z : p.x);
+    y = k0 ? p.z : (k1 ? p.x : p.y);
+    z = k0 ? p.x : (k1 ? p.y : p.z);
+  }
+}
+
+RT_HD WtRay wt_ray(V3 d) {
+  WtRay w;
+  const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+  w.kz = 0;
+  float m = ax;
+  if (ay > m) w.kz = 1, m = ay;
+  if (az > m) w.kz = 2, m = az;
+  const float big = 3.402823466e+38f;
+  w.ok = (ax <= big) & (ay <= big) & (az <= big) & (m > 0.0f);  // a NaN component fails its compare
+  float dx, dy, dz;
+  wt_axes<-1>(d, w.kz, dx, dy, dz);
+  w.flip = __builtin_bit_cast(uint32_t, dz) & 0x80000000u;
+  w.Sx = dx / dz;
+  w.Sy = dy / dz;
+  w.Sz = 1.0f / dz;
+  return w;
+}
+
+// One vertex in the sheared space of the ray: x, y its position across the ray, z its scaled distance along it.
+template <int KZ>
+RT_HD void wt_shear(V3 P, V3 o, const WtRay& w, float& x, float& y, float& z) {
+  float px, py, pz;
+  wt_axes<KZ>(sub(P, o), w.kz, px, py, pz);
+  x = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, px - w.Sx * pz) ^ w.flip);
+  y = py - w.Sy * pz;
+  z = w.Sz * pz;
+}
+
+struct WtTri {
+  float ax, ay, az, bx, by, bz, cx, cy, cz;
+};
+template <int KZ>
+RT_HD WtTri wt_shear_tri(V3 A, V3 B, V3 C, V3 o, const WtRay& w) {
+  WtTri s;
+  wt_shear<KZ>(A, o, w, s.ax, s.ay, s.az);
+  wt_shear<KZ>(B, o, w, s.bx, s.by, s.bz);
+  wt_shear<KZ>(C, o, w, s.cx, s.cy, s.cz);
+  return s;
+}
+
+// a * b - c * d in double from floats (exact products, one rounded difference), rounded to float: the exact sign
+RT_HD float wt_edge_exact(float a, float b, float c, float d) {
+  return (float)((double)a * (double)b - (double)c * (double)d);
+}
+
+// The test on a sheared triangle, without early exits (every lane runs the same instructions, as
+// moller_trumbore_flat). Accepts a point on or inside all three edges with det != 0; u, v are the weights of v1, v2
+// (the project's barycentrics), t is not yet range checked. det has the sign of Moller-Trumbore's determinant (front
+// = clockwise seen from the ray origin = det > 0), so culled() and the instance `flip` apply unchanged.
+RT_HD bool wt_hit(const WtTri& s, const WtRay& w, float face, float& t, float& u, float& v) {
+  float U = s.cx * s.by - s.cy * s.bx;
+  float V = s.ax * s.cy - s.ay * s.cx;
+  float W = s.bx * s.ay - s.by * s.ax;
+  const bool zero = (U == 0.0f) | (V == 0.0f) | (W == 0.0f);
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (__builtin_amdgcn_ballot_w64(zero))  // wave-uniform, rare (a few per million tests)
+#else
+  if (zero)
+#endif
+  {
+    const float Ue = wt_edge_exact(s.cx, s.by, s.cy, s.bx);
+    const float Ve = wt_edge_exact(s.ax, s.cy, s.ay, s.cx);
+    const float We = wt_edge_exact(s.bx, s.ay, s.by, s.ax);
+    U = zero ? Ue : U;
+    V = zero ? Ve : V;
+    W = zero ? We : W;
+  }
+  const bool outside = ((U < 0.0f) | (V < 0.0f) | (W < 0.0f)) & ((U > 0.0f) | (V > 0.0f) | (W > 0.0f));
+  const float det = (U + V) + W;
+  const float inv = mt_rcp(det);
+  t = ((U * s.az + V * s.bz) + W * s.cz) * inv;
+  u = V * inv;
+  v = W * inv;
+  return w.ok & !outside & (det != 0.0f) & !culled(det, face);
+}
+
+// per-lane form (the per-lane walk, the host service): the axes picked by selects
+RT_HD bool watertight(V3 o, const WtRay& w, V3 A, V3 B, V3 C, float face, float& t, float& u, float& v) {
+  return wt_hit(wt_shear_tri<-1>(A, B, C, o, w), w, face, t, u, v);
 }
 
 // HLSL reflect(i, n) = i - 2 * n * dot(i, n), evaluated as i - (2 n) * dot(i, n).

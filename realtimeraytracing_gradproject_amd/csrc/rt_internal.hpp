@@ -66,6 +66,10 @@ hipError_t blas_prepare(const float* d_vtx, const uint32_t* d_idx, uint32_t ntri
 // Gathers triangles into leaf order.
 hipError_t blas_reorder(const TriRec* d_in, const uint32_t* d_sorted, uint32_t n, TriRec* d_out,
                         hipStream_t stream);
+// The watertight test's vertex-form records of a built BLAS: d_out[i] = the vertices of triangle d_tris[i].prim
+// (d_tris in leaf order, as any of the build paths left it), from the BLAS's {pos, normal} vertices and indices.
+hipError_t blas_vertex_records(const TriRec* d_tris, const float* d_vtx, const uint32_t* d_idx, uint32_t n,
+                               TriVtx* d_out, hipStream_t stream);
 // Copies n nodes into the scene pool at dst, rebasing internal refs by node_base and leaf refs
 // (~slot) by tri_base (TLAS: node_base = 0, tri_base = -1 keeps ~instance refs).
 hipError_t pool_rebase(const Bvh4Node* src, uint32_t n, uint32_t node_base, int64_t tri_base, Bvh4Node* dst,

@@ -2001,6 +2001,32 @@ __global__ void k_tri_reorder(const TriRec* __restrict__ in, const uint32_t* __r
   if (i < n) out[i] = in[sorted[i]];
 }
 
+// Vertex-form records (TriVtx) of a built BLAS, for the watertight triangle test: slot i of the leaf order holds
+// triangle tris[i].prim — the sorted permutation, as whichever build path (one-launch, four-launch, multi-kernel)
+// left it in the reordered TriRec array — with its three vertex positions exactly as given. One launch per BLAS,
+// issued only when the watertight mode needs the records (the default build's launches are unchanged). The bounds
+// are those of the build: prim < the BLAS's triangle count, and its indices were range checked at upload.
+__global__ void k_tri_vertices(const TriRec* __restrict__ tris, const float* __restrict__ vtx,
+                               const uint32_t* __restrict__ idx, uint32_t n, TriVtx* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = tris[i].prim;
+  const uint32_t i0 = idx ? idx[3 * p] : 3 * p, i1 = idx ? idx[3 * p + 1] : 3 * p + 1,
+                 i2 = idx ? idx[3 * p + 2] : 3 * p + 2;
+  const float* a = vtx + (size_t)i0 * 6;
+  const float* b = vtx + (size_t)i1 * 6;
+  const float* c = vtx + (size_t)i2 * 6;
+  TriVtx t;
+  for (int k = 0; k < 3; ++k) {
+    t.v0[k] = a[k];
+    t.v1[k] = b[k];
+    t.v2[k] = c[k];
+  }
+  t.prim = p;
+  t.pad1 = t.pad2 = 0;
+  out[i] = t;
+}
+
 __global__ void k_inst_boxes(const InstanceRec* __restrict__ inst, const float* __restrict__ bb,
                              uint32_t n, float* __restrict__ box) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2268,6 +2294,13 @@ hipError_t blas_prepare(const float* d_vtx, const uint32_t* d_idx, uint32_t ntri
 hipError_t blas_reorder(const TriRec* d_in, const uint32_t* d_sorted, uint32_t n, TriRec* d_out,
                         hipStream_t s) {
   k_tri_reorder<<<grid1(n, 256), 256, 0, s>>>(d_in, d_sorted, n, d_out);
+  return hipGetLastError();
+}
+
+hipError_t blas_vertex_records(const TriRec* d_tris, const float* d_vtx, const uint32_t* d_idx, uint32_t n,
+                               TriVtx* d_out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  k_tri_vertices<<<grid1(n, 256), 256, 0, s>>>(d_tris, d_vtx, d_idx, n, d_out);
   return hipGetLastError();
 }
 

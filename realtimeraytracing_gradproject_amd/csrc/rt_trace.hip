@@ -132,7 +132,9 @@ __device__ __forceinline__ Octant octant(V3 invd) {
 // traversal order. Children are visited nearest first (sort4); the oracle mirrors the order, so
 // the box/triangle test counters match it exactly. Entering an instance pushes a sentinel and
 // moves to the BLAS root in the pool; popping the sentinel restores the world-space ray.
-template <bool ANY_HIT, bool STATS, bool CULL = false>
+// TT: the triangle test (RT_TRIANGLE_TEST_*), a compile-time choice: 0 Moller-Trumbore on pool_tris (the code as it
+// was), 1 the watertight test on pool_vtx (the same slots), with the ray's shear constants set up per instance entry.
+template <bool ANY_HIT, bool STATS, bool CULL = false, int TT = 0>
 __device__ bool trace(const SceneView& sc, V3 o, V3 d, float tmin, float tmax, HitRec& hit,
                       const LaneStack& stk, Counters& cnt) {
   const V3 winvd = v3(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
@@ -141,7 +143,8 @@ __device__ bool trace(const SceneView& sc, V3 o, V3 d, float tmin, float tmax, H
   V3 ro = o, rd = d, rinvd = winvd, rnoinv = wnoinv;
   Octant oct = woct;
   const RT_GLOBAL char* pn = (const RT_GLOBAL char*)sc.pool_nodes;
-  const RT_GLOBAL char* pt = (const RT_GLOBAL char*)sc.pool_tris;
+  const RT_GLOBAL char* pt = TT ? (const RT_GLOBAL char*)sc.pool_vtx : (const RT_GLOBAL char*)sc.pool_tris;
+  WtRay wr{};  // TT: the object ray's shear constants
   uint32_t cur = 0;
   float face = 0.0f;  // CULL: +1 / -1 (mirroring instance) for the current BLAS
   bool in_blas = false;
@@ -203,6 +206,7 @@ __device__ bool trace(const SceneView& sc, V3 o, V3 d, float tmin, float tmax, H
         rinvd = tr ? winvd : v3(safe_inv(rd.x), safe_inv(rd.y), safe_inv(rd.z));
         rnoinv = neg(mul(ro, rinvd));
         oct = octant(rinvd);
+        if (TT) wr = wt_ray(rd);
         if (CULL) face = (ir->flip ? -1.0f : 1.0f) * sc.cull_sense;
         in_blas = true;
         ref = (int)ir->pool_root;
@@ -215,8 +219,9 @@ __device__ bool trace(const SceneView& sc, V3 o, V3 d, float tmin, float tmax, H
       if (STATS) ++cnt.tri;
       if (STATS) ++cnt.tfetch;
       float t, u, v;
-      if (moller_trumbore(ro, rd, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), face, t, u, v) &&
-          t >= tmin) {
+      const bool ok = TT ? watertight(ro, wr, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), face, t, u, v)
+                         : moller_trumbore(ro, rd, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), face, t, u, v);
+      if (ok && t >= tmin) {
         const uint32_t prim = __float_as_uint(a.w);
         const bool better =
             t < hit.t || (t == hit.t && (cur < hit.inst || (cur == hit.inst && prim < hit.prim)));
@@ -440,10 +445,18 @@ __device__ __forceinline__ bool pop_cull_dead(int slot, const HitRec& h) {
 // point outside the triangle's box) — which the per-ray walk never tests. With the mask a ray's accepted set is the
 // per-ray walk's: a hit needs the triangle's own box, which implies every ancestor box (their planes enclose it and
 // the fma is monotone in the plane), so the image does not depend on the schedule. One s_and_b64 per test.
-template <bool ANY_HIT, bool STATS, int R>
+// TT 1 (watertight): tpool holds the vertex-form records (TriVtx, the same 48-B slots and prim word), wt[r] the
+// object rays' shear constants and kzu the dominant axis when every live ray of the packet shares it (else -1).
+// With a shared axis — nearly every primary-ray packet — the sheared vertices are formed straight from the SGPR
+// operands by one of three axis-specific copies of the 21-operation front end behind a uniform switch; a packet of
+// mixed axes picks each lane's components by selects (18 more VALU operations and their SGPR-to-VGPR moves). The
+// edge functions and the hit values are one common tail either way (wt_hit), so the result does not depend on the
+// path taken.
+template <bool ANY_HIT, bool STATS, int R, int TT = 0>
 __device__ __forceinline__ void packet_tri(const RT_CONST TriRec* tpool, int ref, const PacketRay<R>& ry,
                                            float tmin, uint32_t cur, float face, PacketLive<R>& pl, HitRec* hit,
-                                           const uint64_t* own, Counters& cnt) {
+                                           const uint64_t* own, Counters& cnt, const WtRay* wt = nullptr,
+                                           int kzu = -1) {
   // 32-bit byte offsets (pools are < 2 GiB): the scalar load takes them as its SGPR offset
   const RT_CONST char* tq = (const RT_CONST char*)tpool + (uint32_t)(~ref) * 48u;
   const f8v tab = *(const RT_CONST f8v*)tq;  // one s_load_dwordx8 + one x4 for the 48-B record
@@ -455,8 +468,19 @@ __device__ __forceinline__ void packet_tri(const RT_CONST TriRec* tpool, int ref
   for (int r = 0; r < R; ++r) {
     if (STATS && ray_live(hit[r])) ++cnt.tri;
     float t, u, v;
-    const bool ok = moller_trumbore_flat(ry.o[r], ry.d[r], v3(ta.x, ta.y, ta.z), v3(tb.x, tb.y, tb.z),
-                                         v3(tc.x, tc.y, tc.z), face, t, u, v);
+    bool ok;
+    if (TT) {
+      const V3 A = v3(ta.x, ta.y, ta.z), B = v3(tb.x, tb.y, tb.z), C = v3(tc.x, tc.y, tc.z);
+      WtTri s;
+      if (kzu == 0) s = wt_shear_tri<0>(A, B, C, ry.o[r], wt[r]);
+      else if (kzu == 1) s = wt_shear_tri<1>(A, B, C, ry.o[r], wt[r]);
+      else if (kzu == 2) s = wt_shear_tri<2>(A, B, C, ry.o[r], wt[r]);
+      else s = wt_shear_tri<-1>(A, B, C, ry.o[r], wt[r]);
+      ok = wt_hit(s, wt[r], face, t, u, v);
+    } else {
+      ok = moller_trumbore_flat(ry.o[r], ry.d[r], v3(ta.x, ta.y, ta.z), v3(tb.x, tb.y, tb.z), v3(tc.x, tc.y, tc.z),
+                                face, t, u, v);
+    }
     HitRec& h = hit[r];
     // bitwise & / | (no short-circuit): no exec-mask branches around the compares (-2 %)
     // a ray that is not live has t = -inf and takes nothing; a live any-hit ray still holds
@@ -727,12 +751,12 @@ __device__ __forceinline__ void lane_subtree(const RT_GLOBAL char* pn, const RT_
 // the walk (and every counter) is that of the per-child stack with a fraction of the scalar
 // bookkeeping. BLAS nodes hold their internal children in the lowest slots, so the internal child in
 // slot k is first_inner + k.
-template <bool ANY_HIT, bool STATS, int R, bool OCT>
+template <bool ANY_HIT, bool STATS, int R, bool OCT, int TT = 0>
 __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, const RT_CONST TriRec* tpool, int bref,
                                                  const PacketRay<R>& ry, float tmin, uint32_t cur, float face,
                                                  PacketLive<R>& pl, HitRec* hit, WaveStack& stk, int& sp, int cap,
                                                  const NodeOct& oc, int hybrid, int lds_root, int lds_n,
-                                                 Counters& cnt) {
+                                                 Counters& cnt, const WtRay* wt = nullptr, int kzu = -1) {
   (void)lds_root;
   (void)lds_n;
   const int base = sp;
@@ -801,7 +825,8 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
     asm volatile("" ::"s"(ch[0]), "s"(ch[1]), "s"(ch[2]), "s"(ch[3]), "s"(ch[5]), "s"(ch[6]), "s"(ch[7]));
 #if RT_HYBRID_T
     // few lanes want this node: they walk its subtree on their own (lane_subtree), then the packet pops
-    if (R == 1 && hybrid && (ent & (uint32_t)ch[6]) != 0u && (!RT_HYBRID_ROOT || sp == base)) {
+    // (the watertight walks keep the packet: lane_subtree reads Moller-Trumbore records)
+    if (TT == 0 && R == 1 && hybrid && (ent & (uint32_t)ch[6]) != 0u && (!RT_HYBRID_ROOT || sp == base)) {
       const uint64_t act = (hm[0][0] | hm[0][1]) | (hm[0][2] | hm[0][3]);
       if (__builtin_popcountll(act) <= RT_HYBRID_T) {
         const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -832,7 +857,7 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
           uint64_t own[R];
 #pragma unroll
           for (int r = 0; r < R; ++r) own[r] = hm[r][k];
-          packet_tri<ANY_HIT, STATS, R>(tpool, ch[k], ry, tmin, cur, face, pl, hit, own, cnt);
+          packet_tri<ANY_HIT, STATS, R, TT>(tpool, ch[k], ry, tmin, cur, face, pl, hit, own, cnt, wt, kzu);
         }
       if (ANY_HIT) {  // rays can only have left the packet in a triangle test
         if (!pl.update(hit)) return false;
@@ -914,11 +939,11 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
 
 // The walk of trace_packet. Rays that are not alive start with t = -inf, so every slab test
 // rejects them and the ballots need no live mask.
-template <bool ANY_HIT, bool STATS, int R, bool CULL>
+template <bool ANY_HIT, bool STATS, int R, bool CULL, int TT = 0>
 __device__ __forceinline__ void packet_walk(const SceneView& sc, const V3* o, const V3* d, float tmin, float tmax,
                                             const bool* alive, HitRec* hit, Counters& cnt) {
   const RT_CONST char* pool = (const RT_CONST char*)sc.pool_nodes;
-  const RT_CONST TriRec* tpool = (const RT_CONST TriRec*)sc.pool_tris;
+  const RT_CONST TriRec* tpool = TT ? (const RT_CONST TriRec*)sc.pool_vtx : (const RT_CONST TriRec*)sc.pool_tris;
   const RT_CONST InstanceRec* ipool = (const RT_CONST InstanceRec*)sc.inst;
   PacketLive<R> pl;
   PacketRay<R> w;
@@ -988,12 +1013,29 @@ __device__ __forceinline__ void packet_walk(const SceneView& sc, const V3* o, co
 #else
       const int lroot = 0, ln = 0;
 #endif
-      const bool more = uni ? packet_blas_walk<ANY_HIT, STATS, R, true>(pool, tpool, (int)ir.pool_root, b, tmin, cur,
-                                                                          face, pl, hit, stk, sp, cap, oc, sc.hybrid,
-                                                                          lroot, ln, cnt)
-                            : packet_blas_walk<ANY_HIT, STATS, R, false>(pool, tpool, (int)ir.pool_root, b, tmin,
-                                                                           cur, face, pl, hit, stk, sp, cap, oc, sc.hybrid,
-                                                                           lroot, ln, cnt);
+      // Watertight: each object ray's shear constants, once per instance entry, and the dominant axis when every
+      // live ray shares it (the live set only shrinks during the walk, so a shared axis stays shared)
+      WtRay wt[R];
+      int kzu = -1;
+      if (TT) {
+        int kl = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          wt[r] = wt_ray(b.d[r]);
+          kl = (r == 0 || pl.lead_r == (uint32_t)r) ? wt[r].kz : kl;
+        }
+        kzu = __builtin_amdgcn_readlane(kl, (int)pl.lead_l);  // the lead ray's axis
+        uint64_t mixed = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) mixed |= wave_ballot(wt[r].kz != kzu) & pl.mask[r];
+        kzu = mixed ? -1 : kzu;
+      }
+      const bool more = uni ? packet_blas_walk<ANY_HIT, STATS, R, true, TT>(pool, tpool, (int)ir.pool_root, b, tmin, cur,
+                                                                              face, pl, hit, stk, sp, cap, oc, sc.hybrid,
+                                                                              lroot, ln, cnt, wt, kzu)
+                            : packet_blas_walk<ANY_HIT, STATS, R, false, TT>(pool, tpool, (int)ir.pool_root, b, tmin,
+                                                                               cur, face, pl, hit, stk, sp, cap, oc,
+                                                                               sc.hybrid, lroot, ln, cnt, wt, kzu);
       if (ANY_HIT && !more) return;
     }
     if (!descend) {
@@ -1010,10 +1052,10 @@ __device__ __forceinline__ void packet_walk(const SceneView& sc, const V3* o, co
 // Traces the R rays of every lane (o, d, alive per slot) as one packet; found[r] / hit[r] per ray
 // (a ray found a hit iff one was accepted: inst is set on acceptance only). Any-hit rays report
 // acceptance only (t is -inf once accepted).
-template <bool ANY_HIT, bool STATS, int R, bool CULL = false>
+template <bool ANY_HIT, bool STATS, int R, bool CULL = false, int TT = 0>
 __device__ void trace_packet(const SceneView& sc, const V3* o, const V3* d, float tmin, float tmax,
                              const bool* alive, bool* found, HitRec* hit, Counters& cnt) {
-  packet_walk<ANY_HIT, STATS, R, CULL>(sc, o, d, tmin, tmax, alive, hit, cnt);
+  packet_walk<ANY_HIT, STATS, R, CULL, TT>(sc, o, d, tmin, tmax, alive, hit, cnt);
 #pragma unroll
   for (int r = 0; r < R; ++r) found[r] = hit[r].inst != 0xffffffffu;
 }
@@ -1159,11 +1201,11 @@ __device__ V3 surface_ref(const FrameParams& fp, V3 P, V3 n, V3 cam) {
   return add(cd, v3(det_pow(c.x, g), det_pow(c.y, g), det_pow(c.z, g)));
 }
 
-template <bool STATS>
+template <bool STATS, int TT = 0>
 __device__ bool shadow_ray(const SceneView& sc, V3 P, V3 dir, const LaneStack& stk, Counters& cnt) {
   HitRec h;
   if (STATS) ++cnt.shadow;
-  return trace<true, STATS>(sc, P, normalize(dir), 0.01f, 100000.0f, h, stk, cnt);
+  return trace<true, STATS, false, TT>(sc, P, normalize(dir), 0.01f, 100000.0f, h, stk, cnt);
 }
 
 __device__ __forceinline__ V3 miss_color(const FrameParams& fp, uint32_t py) {
@@ -1204,7 +1246,7 @@ __device__ __forceinline__ V3 unwind_chain(const V3* sk, int n, V3 c, float r) {
 // scratch, touched only by reflective hits) and the nested lerps are unwound innermost first,
 // as the recursion evaluates them (oracle/rt_oracle.c oshade_ref mirrors it). r == 0 traces no
 // reflection.
-template <bool STATS>
+template <bool STATS, int TT = 0>
 __device__ V3 shade_ref(const SceneView& sc, const FrameParams& fp, uint32_t py, V3 O, V3 D, bool f, HitRec hit,
                         const LaneStack& stk, Counters& cnt) {
   const float refl = fp.material.reflectivity;
@@ -1222,7 +1264,7 @@ __device__ V3 shade_ref(const SceneView& sc, const FrameParams& fp, uint32_t py,
         const V3 ldir = normalize(sub(v3(L0.position[0], L0.position[1], L0.position[2]), P));
         const V3 n = face_world_normal(ir, hit.prim);
         bool shadowed = dot(n, ldir) < 0.0f;
-        const bool occl = shadow_ray<STATS>(sc, P, ldir, stk, cnt);
+        const bool occl = shadow_ray<STATS, TT>(sc, P, ldir, stk, cnt);
         if (!shadowed) shadowed = occl;
         const float factor = shadowed ? 0.3f : 1.0f;
         const float li = maxf(0.0f, dot(n, ldir));
@@ -1235,7 +1277,7 @@ __device__ V3 shade_ref(const SceneView& sc, const FrameParams& fp, uint32_t py,
           sk[depth] = s;
           reflection_ray(P, n, rd, ro, rd);
           if (STATS) ++cnt.refl;
-          f = trace<false, STATS, true>(sc, ro, rd, 0.001f, 1000.0f, hit, stk, cnt);
+          f = trace<false, STATS, true, TT>(sc, ro, rd, 0.001f, 1000.0f, hit, stk, cnt);
           continue;
         }
         term = s;
@@ -1246,7 +1288,7 @@ __device__ V3 shade_ref(const SceneView& sc, const FrameParams& fp, uint32_t py,
 }
 
 // One camera sample -> color (RayGen.hlsl:28-43 and the hit/miss programs).
-template <int MODE, bool STATS>
+template <int MODE, bool STATS, int TT = 0>
 __device__ V3 shade_sample(const SceneView& sc, const FrameParams& fp, const FrameCam& cam, uint32_t px, uint32_t py,
                            float ox, float oy, const LaneStack& stk, Counters& cnt) {
   const float dx = (((float)px + ox) / fp.fwidth) * 2.0f - 1.0f;
@@ -1260,8 +1302,8 @@ __device__ V3 shade_sample(const SceneView& sc, const FrameParams& fp, const Fra
   const V3 D = normalize(v3(dw[0], dw[1], dw[2]));  // CastDefaultRay
   HitRec hit;
   if (STATS) ++cnt.primary;
-  const bool f = trace<false, STATS>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
-  if (MODE == 0 || MODE == 3) return shade_ref<STATS>(sc, fp, py, O, D, f, hit, stk, cnt);
+  const bool f = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
+  if (MODE == 0 || MODE == 3) return shade_ref<STATS, TT>(sc, fp, py, O, D, f, hit, stk, cnt);
   if (!f) return miss_color(fp, py);
   const HitInstance ir = load_hit_instance(sc, hit.inst);
   const V3 P = add(O, muls(D, hit.t));  // GetWorldHitPoint, Common.hlsl:24-27
@@ -1275,7 +1317,7 @@ __device__ V3 shade_sample(const SceneView& sc, const FrameParams& fp, const Fra
     const float nl = dot(n, L);
     if (nl > 0.0f) {
       float factor = 1.0f;
-      if (MODE == 1 && shadow_ray<STATS>(sc, P, L, stk, cnt)) factor = 0.3f;
+      if (MODE == 1 && shadow_ray<STATS, TT>(sc, P, L, stk, cnt)) factor = 0.3f;
       c = c + nl * factor;
     }
   }
@@ -1295,7 +1337,7 @@ __device__ V3 shade_sample(const SceneView& sc, const FrameParams& fp, const Fra
 // whole workgroup must call it (uniform per light: two barriers). Same results as the per-wave
 // packets (a ray's occlusion does not depend on its packet). Kept as RT_SHADOW_COMPACT: with the
 // screen-tile waves the shadow packets are already ~94-99 % full (C2-C4), so it rarely fires.
-template <bool STATS>
+template <bool STATS, int TT = 0>
 __device__ bool shadow_compact(const SceneView& sc, V3 P, V3 d, bool need, uint32_t parity, Counters& cnt) {
   __shared__ float s_ray[6][64];
   __shared__ uint32_t s_cnt[2][4];
@@ -1335,7 +1377,7 @@ __device__ bool shadow_compact(const SceneView& sc, V3 P, V3 d, bool need, uint3
   // return at once); a single inlined walk keeps the kernel's registers
   HitRec h;
   bool f;
-  trace_packet<true, STATS, 1>(sc, &q, &e, 0.01f, 100000.0f, &alive, &f, &h, cnt);
+  trace_packet<true, STATS, 1, false, TT>(sc, &q, &e, 0.01f, 100000.0f, &alive, &f, &h, cnt);
   if (!merge) return f;
   const uint64_t om = wave_ballot(f);
   if (w == 0 && lane == 0) {
@@ -1352,7 +1394,7 @@ __device__ bool shadow_compact(const SceneView& sc, V3 P, V3 d, bool need, uint3
 #ifndef RT_WAVE_TIMES
 #define RT_WAVE_TIMES 0  // 1: every wave stores its start / end clock (diagnostics; tools/wave_times.py)
 #endif
-template <int MODE, bool STATS, int R>
+template <int MODE, bool STATS, int R, int TT = 0>
 __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, const FrameCam& cam, const uint32_t* px,
                                     const uint32_t* py, float ox, float oy, const bool* inimg, V3* color,
                                     Counters& cnt) {
@@ -1372,7 +1414,7 @@ __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, 
     D[r] = normalize(v3(dw[0], dw[1], dw[2]));  // CastDefaultRay
     if (STATS && inimg[r]) ++cnt.primary;
   }
-  trace_packet<false, STATS, R>(sc, O, D, 0.0f, 100000.0f, inimg, found, hit, cnt);
+  trace_packet<false, STATS, R, false, TT>(sc, O, D, 0.0f, 100000.0f, inimg, found, hit, cnt);
 #pragma unroll
   for (int r = 0; r < R; ++r) P[r] = add(O[r], muls(D[r], hit[r].t));  // GetWorldHitPoint, Common.hlsl:24-27
   if (MODE == 0 || MODE == 3) {  // MODE 3: RT_SHADE_REF with reflectivity 0 (no reflection rays)
@@ -1427,7 +1469,7 @@ __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, 
         color[r] = unwind_chain(sk[r], depth, term, refl);
         act[r] = false;
       }
-      trace_packet<true, STATS, R>(sc, P, sd, 0.01f, 100000.0f, need, occl, sh, cnt);
+      trace_packet<true, STATS, R, false, TT>(sc, P, sd, 0.01f, 100000.0f, need, occl, sh, cnt);
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (!need[r]) continue;
@@ -1447,7 +1489,7 @@ __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, 
       if (!more) return;
 #pragma unroll
       for (int r = 0; r < R; ++r) act[r] = nxt[r];
-      trace_packet<false, STATS, R, true>(sc, ro, rd, 0.001f, 1000.0f, act, found, hit, cnt);
+      trace_packet<false, STATS, R, true, TT>(sc, ro, rd, 0.001f, 1000.0f, act, found, hit, cnt);
     }
   }
   // RT_SHADE_LAMBERT_SHADOW (MODE 1) and RT_SHADE_PRIMARY (MODE 2)
@@ -1477,9 +1519,9 @@ __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, 
     }
     if (MODE == 1) {
       if (RT_SHADOW_COMPACT && R == 1)
-        occl[0] = shadow_compact<STATS>(sc, P[0], sd[0], need[0], l & 1u, cnt);
+        occl[0] = shadow_compact<STATS, TT>(sc, P[0], sd[0], need[0], l & 1u, cnt);
       else
-        trace_packet<true, STATS, R>(sc, P, sd, 0.01f, 100000.0f, need, occl, sh, cnt);
+        trace_packet<true, STATS, R, false, TT>(sc, P, sd, 0.01f, 100000.0f, need, occl, sh, cnt);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -1535,7 +1577,7 @@ __device__ __forceinline__ void flush_stats(const Counters& c, unsigned long lon
 #define RT_TRACE_ATTR
 #endif
 
-template <int MODE, bool STATS>
+template <int MODE, bool STATS, int TT = 0>
 __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void k_trace_frame(SceneView sc, FrameParams fp,
                                                         const uint32_t* __restrict__ rows,
                                                         uint32_t* __restrict__ rgba8,
@@ -1556,7 +1598,7 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void k_trace_frame(SceneView 
       for (uint32_t sx = 0; sx < k; ++sx) {
         const float ox = ((float)sx + 0.5f) / (float)k;
         const float oy = ((float)sy + 0.5f) / (float)k;
-        acc = add(acc, shade_sample<MODE, STATS>(sc, fp, fp.cam[blockIdx.z], px, py, ox, oy, stk, cnt));
+        acc = add(acc, shade_sample<MODE, STATS, TT>(sc, fp, fp.cam[blockIdx.z], px, py, ox, oy, stk, cnt));
       }
     if (k > 1) {
       const float ns = (float)(k * k);
@@ -1678,7 +1720,7 @@ static_assert(packet_block(0) <= kPopCullThreads && packet_block(1) <= kPopCullT
 #undef RT_PK_SGPR_ATTR
 
 
-template <bool ANY_HIT, bool STATS, bool CULL>
+template <bool ANY_HIT, bool STATS, bool CULL, int TT = 0>
 __global__ __launch_bounds__(kBlock) void k_trace_rays(SceneView sc, const float4* __restrict__ rays,
                                                        uint32_t n, uint4* __restrict__ hits,
                                                        float2* __restrict__ uv,
@@ -1689,7 +1731,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays(SceneView sc, const float
   if (i < n) {
     const float4 a = rays[2 * i], b = rays[2 * i + 1];
     HitRec h;
-    const bool f = trace<ANY_HIT, STATS, CULL>(sc, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), a.w, b.w, h,
+    const bool f = trace<ANY_HIT, STATS, CULL, TT>(sc, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), a.w, b.w, h,
                                          lane_stack(sc, s_stack, i), cnt);
     if (STATS) ++cnt.primary;
     hits[i] = make_uint4(__float_as_uint(f ? h.t : b.w), f ? h.inst : 0xffffffffu,
@@ -1804,6 +1846,31 @@ hipError_t launch_mode(const SceneView& sc, const FrameParams& fp, const uint32_
                        float* rgba32f, unsigned long long* stats, int schedule, uint32_t plan_items, hipStream_t s) {
   dim3 grid((fp.width + 15) / 16, (fp.nrows + 15) / 16, fp.nframes);
   const PacketGeometry g = packet_geometry(sc, fp, schedule);
+  // Watertight mode (sc.tri_test set): the TT = 1 instantiations. The packet schedule always takes the plain grid's
+  // general kernel (no tile balance, any frame count and output format: schedule choices the image never depends
+  // on), and REF with reflectivity 0 the reflective kernel (MODE 0: the same image without MODE 3's specialisation),
+  // which keeps the code object to one packet kernel per shade mode, counter switch and sample layout.
+  if constexpr (MODE != 3) {
+    if (sc.tri_test) {
+      if (g.packet) {
+        constexpr int R = RT_PACKET_RAYS;
+        const dim3 gp(g.grid_x, g.grid_y, fp.nframes);
+#define RT_LAUNCH_WT(KS)                                                                                        \
+  hipLaunchKernelGGL((k_trace_frame_packet<MODE, STATS, R, (R == 1 ? KS : 0), false, true, 1>), gp,             \
+                     dim3(packet_block(R == 1 ? KS : 0)), 0, s, sc, fp, rows, (uint32_t*)rgba8, (float4*)rgba32f, \
+                     stats)
+        if (g.ks == 1) RT_LAUNCH_WT(1);
+        else if (g.ks == 2) RT_LAUNCH_WT(2);
+        else if (g.ks == 4) RT_LAUNCH_WT(4);
+        else RT_LAUNCH_WT(0);
+#undef RT_LAUNCH_WT
+      } else {
+        hipLaunchKernelGGL((k_trace_frame<MODE, STATS, 1>), grid, dim3(kBlock), (size_t)sc.lds_cap * kBlock * sizeof(int),
+                           s, sc, fp, rows, (uint32_t*)rgba8, (float4*)rgba32f, stats);
+      }
+      return hipGetLastError();
+    }
+  }
   if (g.packet) {
     constexpr int R = RT_PACKET_RAYS;
     const int ks = g.ks;
@@ -1884,7 +1951,7 @@ hipError_t launch_trace_frame(const SceneView& sc, const FrameParams& fp, const 
     case 0:
       // the reference scene's parity config pins reflectivity to 0: a kernel without
       // the reflection-chain state (registers, the per-lane sk[] stack) then runs at a higher occupancy
-      if (fp.material.reflectivity == 0.0f && RT_REF_NOREFL)
+      if (fp.material.reflectivity == 0.0f && RT_REF_NOREFL && !sc.tri_test)
         return stats ? launch_mode<3, true>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s)
                      : launch_mode<3, false>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s);
       return stats ? launch_mode<0, true>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s)
@@ -2302,9 +2369,16 @@ hipError_t launch_trace_rays(const SceneView& sc, const float* rays, uint32_t n,
   dim3 grid((n + kBlock - 1) / kBlock);
   size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
   const float4* r = (const float4*)rays;
-#define RT_LAUNCH_RAYS(A, C, S)                                                                          \
-  hipLaunchKernelGGL((k_trace_rays<A, S, C>), grid, dim3(kBlock), lds, s, sc, r, n, (uint4*)hits, (float2*)uv, \
-                     d_stats)
+  // watertight mode (sc.tri_test set): the TT = 1 instantiations
+#define RT_LAUNCH_RAYS(A, C, S)                                                                                   \
+  do {                                                                                                            \
+    if (sc.tri_test)                                                                                              \
+      hipLaunchKernelGGL((k_trace_rays<A, S, C, 1>), grid, dim3(kBlock), lds, s, sc, r, n, (uint4*)hits,          \
+                         (float2*)uv, d_stats);                                                                   \
+    else                                                                                                          \
+      hipLaunchKernelGGL((k_trace_rays<A, S, C>), grid, dim3(kBlock), lds, s, sc, r, n, (uint4*)hits, (float2*)uv, \
+                         d_stats);                                                                                \
+  } while (0)
   if (any_hit) {
     if (cull) { if (stats) RT_LAUNCH_RAYS(true, true, true); else RT_LAUNCH_RAYS(true, true, false); }
     else { if (stats) RT_LAUNCH_RAYS(true, false, true); else RT_LAUNCH_RAYS(true, false, false); }

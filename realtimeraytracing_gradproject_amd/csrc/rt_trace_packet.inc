@@ -1,8 +1,10 @@
 // rt_trace_packet.inc — the packet frame kernel's definition, included twice by rt_trace.hip (inside namespace
 // rt::{anonymous}) under two names and register budgets: RT_PK_NAME / RT_PK_SGPR_ATTR (see there). Not a header.
-template <int MODE, bool STATS, int R, int KS, bool BAL, bool MF>
+template <int MODE, bool STATS, int R, int KS, bool BAL, bool MF, int TT = 0>
 __global__ __launch_bounds__(packet_block(KS)) __attribute__((amdgpu_waves_per_eu(
-    (MODE == 1 && !STATS) ? (KS == 0 ? RT_SPP_WAVES : (KS == 1 ? RT_LS_WAVES : RT_KS_WAVES))
+    TT ? 1  // the watertight kernels (TT 1) keep the allocator's choice: the occupancy targets below were tuned for
+            // Moller-Trumbore's registers
+    : (MODE == 1 && !STATS) ? (KS == 0 ? RT_SPP_WAVES : (KS == 1 ? RT_LS_WAVES : RT_KS_WAVES))
     : (MODE == 3 && !STATS) ? (KS == 0 ? RT_SPP_WAVES : (KS == 1 ? RT_REF0_WAVES : RT_KS_WAVES))
                             : ((MODE == 0 && !STATS && KS == 1) ? RT_REF_WAVES : 1)))) RT_PK_SGPR_ATTR
 void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows, uint32_t* __restrict__ rgba8,
@@ -75,12 +77,12 @@ void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows,
   const uint32_t k = KS == 1 ? 1u : (KS > 1 ? (uint32_t)KS : fp.spp_side);
   const FrameCam& cam = fp.cam[MF ? bz : 0u];
   if (KS == 1) {
-    shade_sample_packet<MODE, STATS, R>(sc, fp, cam, px, py, 0.5f, 0.5f, inimg, acc, cnt);  // (0 + 0.5) / 1
+    shade_sample_packet<MODE, STATS, R, TT>(sc, fp, cam, px, py, 0.5f, 0.5f, inimg, acc, cnt);  // (0 + 0.5) / 1
   } else if (KS > 1) {
     // this lane's sample (sx, sy) of the k x k grid, the sample loop's offsets
     const float ox = ((float)(sample % KS) + 0.5f) / (float)KS;
     const float oy = ((float)(sample / KS) + 0.5f) / (float)KS;
-    shade_sample_packet<MODE, STATS, R>(sc, fp, cam, px, py, ox, oy, inimg, col, cnt);
+    shade_sample_packet<MODE, STATS, R, TT>(sc, fp, cam, px, py, ox, oy, inimg, col, cnt);
     // sum in sample order: ((0 + c0) + c1) + ... exactly as the loop adds them (0 + c0 == c0).
     // The lane id is re-read here (v_mbcnt) rather than kept live across the traces.
     uint32_t lid;
@@ -104,7 +106,7 @@ void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows,
       for (uint32_t sx = 0; sx < k; ++sx) {
         const float ox = ((float)sx + 0.5f) / (float)k;
         const float oy = ((float)sy + 0.5f) / (float)k;
-        shade_sample_packet<MODE, STATS, R>(sc, fp, cam, px, py, ox, oy, inimg, col, cnt);
+        shade_sample_packet<MODE, STATS, R, TT>(sc, fp, cam, px, py, ox, oy, inimg, col, cnt);
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = add(acc[r], col[r]);
       }
