@@ -150,6 +150,32 @@ rt_status rt_blas_build(rt_ctx_t ctx, const void* vtx, uint32_t vcount, uint32_t
  * geometry. Instances that reference it pick it up at the next rt_tlas_build. */
 rt_status rt_blas_rebuild(rt_ctx_t ctx, rt_blas_t blas, const void* vtx, uint32_t vcount,
                           uint32_t stride, const uint32_t* idx, uint32_t icount);
+/* Replaces BottomLevelASGenerator::Generate(..., updateOnly = true, previousResult) on a BLAS built with
+ * ALLOW_UPDATE (BottomLevelASGenerator.cpp:130-140, 176-230), DXR's PERFORM_UPDATE: the same topology, new vertex
+ * positions, boxes refitted in place. vtx: host array of vcount vertices, copied during the call; vcount must be
+ * the vertex count of the BLAS's last build or rebuild, whose indices stay. stride is a multiple of 4: from 24 on
+ * it carries {position, normal} as in rt_blas_build and both are replaced; from 12 to below 24 only the
+ * positions are replaced and the stored normals stay. The BVH4 nodes keep their children, their order and every
+ * allocation: the triangle records are recomputed in leaf order and every child box bottom-up, in the BLAS's own
+ * arrays and, where the BLAS has slots in the current scene pool, there too (its vertex-form records as well
+ * while they are current, whichever triangle test is selected). rt_blas_info then reports the new bounds and the
+ * device time of the refit's kernels as build_ms; node_count, depth and max_stack do not change.
+ * Synchronisation: like rt_blas_rebuild it first waits for all in-flight work (frames in flight read these
+ * arrays), then runs its kernels on the context's stream and returns once they have completed. From the second
+ * refit of a BLAS on it allocates and frees nothing.
+ * Afterwards the current TLAS still holds the BLAS's old box: launches (rt_raster_draw excepted) return
+ * RT_E_INVALID until the next rt_tlas_build, which may be update_only = 1 and then takes its usual per-frame
+ * path (no device-wide wait, no allocation, the pool layout kept).
+ * A refit keeps the tree the build chose for the old positions: large deformations degrade it (boxes overlap,
+ * frames get slower, never wrong) and rt_blas_rebuild restores it.
+ * Errors: RT_E_INVALID for an unknown BLAS, a vcount other than the build's, a bad stride or a null pointer
+ * (rt_last_error says which); the BLAS is untouched then. */
+rt_status rt_blas_refit(rt_ctx_t ctx, rt_blas_t blas, const void* vtx, uint32_t vcount, uint32_t stride);
+/* rt_blas_refit from vertices in device memory (a simulation step's output, a torch tensor): vtx_dev is read
+ * after the work already enqueued on hip_stream (NULL: the default stream) has completed — the call's device-wide
+ * wait covers it — and must stay unchanged until the call returns. Everything else as rt_blas_refit. */
+rt_status rt_blas_refit_device(rt_ctx_t ctx, rt_blas_t blas, const void* vtx_dev, uint32_t vcount,
+                               uint32_t stride, void* hip_stream);
 rt_status rt_blas_info(rt_ctx_t ctx, rt_blas_t blas, rt_bvh_info* out);
 /* Copies the BLAS to host memory for parity checks: nodes (node_count x 128 B 4-wide nodes, BFS order),
  * tris (prim_count x 48 B: v0.xyz,prim | e1.xyz,0 | e2.xyz,0 in leaf order). Either may be NULL. */

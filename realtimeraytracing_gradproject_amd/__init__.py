@@ -92,6 +92,8 @@ SIGNATURES = [
     ("rt_destroy", _I, [_P]),
     ("rt_blas_build", _I, [_P, _P, _U32, _U32, _P, _U32, _UP]),
     ("rt_blas_rebuild", _I, [_P, _U32, _P, _U32, _U32, _P, _U32]),
+    ("rt_blas_refit", _I, [_P, _U32, _P, _U32, _U32]),
+    ("rt_blas_refit_device", _I, [_P, _U32, _P, _U32, _U32, _P]),
     ("rt_blas_info", _I, [_P, _U32, ctypes.POINTER(rt_bvh_info)]),
     ("rt_blas_export", _I, [_P, _U32, _P, ctypes.c_size_t, _P, ctypes.c_size_t]),
     ("rt_tlas_build", _I, [_P, ctypes.POINTER(rt_instance), _U32, _I]),
@@ -664,6 +666,25 @@ class Context:
             st = self._lib.rt_blas_rebuild(self._h, blas, v.ctypes.data_as(_P), v.shape[0], stride,
                                      i.ctypes.data_as(_P), i.size)
         self._check(st, "rt_blas_rebuild")
+
+    def blas_refit(self, blas: int, vertices: np.ndarray):
+        """rt_blas_refit: new vertices for the BLAS's topology, boxes refitted in place. vertices: (vcount, k)
+        floats, k >= 6 replaces positions and normals, 3 <= k < 6 the positions only. tlas_build (update_only
+        allowed) must follow before the next launch."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        if v.ndim != 2:
+            v = v.reshape(-1, 6)
+        self._check(self._lib.rt_blas_refit(self._h, blas, v.ctypes.data_as(_P), v.shape[0], v.shape[1] * 4),
+                    "rt_blas_refit")
+
+    def blas_refit_device(self, blas: int, tensor, stream: Optional[int] = None):
+        """rt_blas_refit_device: as blas_refit from a contiguous float32 device tensor of shape (vcount, 3) or
+        (vcount, 6), read after the work already enqueued on `stream` (a raw hipStream_t; None: the default)."""
+        if tensor.dim() != 2 or tensor.shape[1] not in (3, 6) or not tensor.is_contiguous() \
+                or tensor.dtype != torch.float32 or not tensor.is_cuda:
+            raise ValueError("blas_refit_device: a contiguous float32 device tensor of shape (vcount, 3 | 6)")
+        self._check(self._lib.rt_blas_refit_device(self._h, blas, tensor.data_ptr(), int(tensor.shape[0]),
+                                                   int(tensor.shape[1]) * 4, stream), "rt_blas_refit_device")
 
     def blas_info(self, blas: int) -> rt_bvh_info:
         info = rt_bvh_info()

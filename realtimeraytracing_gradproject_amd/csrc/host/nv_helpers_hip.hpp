@@ -132,6 +132,15 @@ class BottomLevelASGenerator {
     return out;
   }
 
+  // DXR's PERFORM_UPDATE proper (BottomLevelASGenerator.cpp:130-140, 176-230 with ALLOW_UPDATE): refits `blas`
+  // in place with the vertices added through AddVertexBuffer — the same vertex count and indices as its build,
+  // new positions and normals. TopLevelASGenerator::Generate(ctx, /*updateOnly=*/true) must follow before the
+  // next launch. Generate(updateOnly = true) above stays the full in-place rebuild (any topology).
+  void Refit(rt_ctx_t ctx, rt_blas_t blas) {
+    if (m_vtx.empty()) throw std::logic_error("BottomLevelASGenerator: no geometry added");
+    ThrowIfFailed(rt_blas_refit(ctx, blas, m_vtx.data(), (uint32_t)(m_vtx.size() / 6), 24), ctx, "rt_blas_refit");
+  }
+
  private:
   std::vector<float> m_vtx;
   std::vector<uint32_t> m_idx;

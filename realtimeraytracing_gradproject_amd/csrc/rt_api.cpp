@@ -25,15 +25,22 @@ struct DeviceBlas {
   uint32_t ntri = 0, nnodes = 0, depth = 0, nvtx = 0, max_stack = 0;
   float bounds[6] = {0, 0, 0, 0, 0, 0};
   double build_ms = 0.0;
+  // rt_blas_refit's device scratch for this tree (parent table, arrival counters, per-node unions), allocated by
+  // the first refit and kept: a rebuild makes a new DeviceBlas, so a new tree starts without it
+  void* refit = nullptr;
+  bool refit_parents = false;  // the parent table in `refit` is written
   void release() {
     if (nodes) (void)hipFree(nodes);
     if (tris) (void)hipFree(tris);
     if (vtx) (void)hipFree(vtx);
     if (idx) (void)hipFree(idx);
+    if (refit) (void)hipFree(refit);
     nodes = nullptr;
     tris = nullptr;
     vtx = nullptr;
     idx = nullptr;
+    refit = nullptr;
+    refit_parents = false;
   }
 };
 
@@ -306,6 +313,16 @@ struct rt_ctx {
   size_t pool_vtx_cap = 0;
   uint64_t pool_vtx_gen = ~0ull;
   bool tlas_stale = false;  // a BLAS was rebuilt after the last rt_tlas_build
+  // a BLAS was refitted after the last rt_tlas_build: the current TLAS holds its old box, so launches are refused
+  // as for tlas_stale, but the pool layout stands and the next rt_tlas_build may be an update (the fast path)
+  bool tlas_refit = false;
+  // rt_blas_refit: staging of the host variant's vertices (pinned, then device; grown on demand), the pinned
+  // readback of the root box, the timing events of the refit's kernels
+  void* refit_stage_host = nullptr;
+  void* refit_stage_dev = nullptr;
+  size_t refit_stage_cap = 0;
+  float* refit_root_host = nullptr;
+  hipEvent_t refit_e0 = nullptr, refit_e1 = nullptr;
   // raster fallback scratch (grown on demand)
   rt::RasterScratch raster;
   size_t raster_tile_cap = 0, raster_prim_cap = 0, raster_bin_cap = 0;
@@ -507,6 +524,68 @@ rt_status build_vertex_pool(rt_ctx* c) {
   return RT_OK;
 }
 
+// The argument checks of rt_blas_refit / rt_blas_refit_device: nothing is touched before they pass.
+rt_status refit_check(rt_ctx* c, rt_blas_t id, const void* vtx, uint32_t vcount, uint32_t stride) {
+  if (!c) return RT_E_INVALID;
+  if (id >= c->blas.size() || !c->blas[id].nodes) return fail(c, RT_E_INVALID, "rt_blas_refit: unknown BLAS");
+  if (!vtx) return fail(c, RT_E_INVALID, "rt_blas_refit: null vertex buffer");
+  if (stride < 12 || (stride % 4)) return fail(c, RT_E_INVALID, "rt_blas_refit: stride must be a multiple of 4, at least 12");
+  if (vcount != c->blas[id].nvtx)
+    return fail(c, RT_E_INVALID, "rt_blas_refit: vertex count differs from the build's (a refit keeps the topology)");
+  return RT_OK;
+}
+
+// The refit proper, from vertices in device memory. The caller has quiesced: nothing in flight reads the BLAS's
+// arrays or the pools. Kernels on the context stream; returns once they have completed and the root box is back.
+rt_status refit_run(rt_ctx* c, rt_blas_t id, const float* d_src, uint32_t src_words, bool normals) {
+  DeviceBlas& b = c->blas[id];
+  hipStream_t s = c->stream;
+  if (!b.refit) {  // the first refit of this tree; later ones allocate nothing
+    HIPCHK(c, hipMalloc(&b.refit, rt::blas_refit_scratch_bytes(b.nnodes)), "hipMalloc(refit scratch)");
+    b.refit_parents = false;
+  }
+  if (!c->refit_root_host)
+    HIPCHK(c, hipHostMalloc((void**)&c->refit_root_host, 32, hipHostMallocDefault), "hipHostMalloc(refit readback)");
+  if (!c->refit_e0) HIPCHK(c, hipEventCreate(&c->refit_e0), "rt_blas_refit: event");
+  if (!c->refit_e1) HIPCHK(c, hipEventCreate(&c->refit_e1), "rt_blas_refit: event");
+  rt::BlasRefit r;
+  r.src = d_src;
+  r.src_words = src_words;
+  r.src_normals = normals;
+  r.vtx = b.vtx;
+  r.idx = b.idx;
+  r.nvtx = b.nvtx;
+  r.ntri = b.ntri;
+  r.nnodes = b.nnodes;
+  r.nodes = b.nodes;
+  r.tris = b.tris;
+  r.scratch = b.refit;
+  r.parents_ready = b.refit_parents;
+  // the BLAS's slots in the current pool layout (one built since the layout, or never in a TLAS, has none: the
+  // rt_tlas_build that lays it out copies the refitted arrays)
+  if (c->pool_gen == c->blas_gen && id < c->node_base.size() && id < c->tri_base.size() && c->pool_nodes &&
+      c->pool_tris) {
+    r.pool_nodes = c->pool_nodes + c->node_base[id];
+    r.pool_tris = c->pool_tris + c->tri_base[id];
+    // the vertex-form records too while they are current, whichever test is selected: a later switch to the
+    // watertight test finds them up to date
+    if (c->pool_vtx && c->pool_vtx_gen == c->pool_gen) r.pool_vtx = c->pool_vtx + c->tri_base[id];
+  }
+  r.root_host = c->refit_root_host;
+  r.e0 = c->refit_e0;
+  r.e1 = c->refit_e1;
+  hipError_t e = rt::blas_refit(r, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hip_fail(c, e, "BLAS refit");
+  b.refit_parents = true;
+  float ms = 0.0f;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->refit_e0, c->refit_e1), "rt_blas_refit: timing");
+  b.build_ms = ms;
+  for (int k = 0; k < 6; ++k) b.bounds[k] = c->refit_root_host[k];
+  c->tlas_refit = c->cur >= 0;  // the current TLAS holds the old box until rt_tlas_build (an update will do)
+  return RT_OK;
+}
+
 
 }  // namespace
 
@@ -581,6 +660,11 @@ rt_status rt_destroy(rt_ctx_t c) {
   if (c->pool_nodes) (void)hipFree(c->pool_nodes);
   if (c->pool_tris) (void)hipFree(c->pool_tris);
   if (c->pool_vtx) (void)hipFree(c->pool_vtx);
+  if (c->refit_stage_host) (void)hipHostFree(c->refit_stage_host);
+  if (c->refit_stage_dev) (void)hipFree(c->refit_stage_dev);
+  if (c->refit_root_host) (void)hipHostFree(c->refit_root_host);
+  if (c->refit_e0) (void)hipEventDestroy(c->refit_e0);
+  if (c->refit_e1) (void)hipEventDestroy(c->refit_e1);
   for (void* p : {(void*)c->raster.clip, (void*)c->raster.slots, (void*)c->raster.tiles, (void*)c->raster.tcount,
                   (void*)c->raster.toffs, (void*)c->raster.bins, (void*)c->raster.bsum, (void*)c->raster.draws})
     if (p) (void)hipFree(p);
@@ -622,6 +706,46 @@ rt_status rt_blas_rebuild(rt_ctx_t c, rt_blas_t id, const void* vtx, uint32_t vc
   ++c->blas_gen;
   c->tlas_stale = c->cur >= 0;  // the scene pool holds the old tree until rt_tlas_build
   return RT_OK;
+}
+
+rt_status rt_blas_refit(rt_ctx_t c, rt_blas_t id, const void* vtx, uint32_t vcount, uint32_t stride) {
+  rt_status st = refit_check(c, id, vtx, vcount, stride);
+  if (st != RT_OK) return st;
+  (void)hipSetDevice(c->device);
+  // frames in flight on any stream read this BLAS's arrays and its pool slots
+  HIPCHK(c, quiesce(c), "rt_blas_refit: wait for in-flight work");
+  // the vertices packed to 3 (positions) or 6 (positions, normals) floats in pinned staging, then one upload
+  const bool normals = stride >= 24;
+  const uint32_t words = normals ? 6u : 3u;
+  const size_t bytes = (size_t)vcount * words * sizeof(float);
+  const size_t want = (size_t)vcount * 6 * sizeof(float);  // room for either form: a later refit does not grow it
+  if (c->refit_stage_cap < want) {
+    if (c->refit_stage_host) (void)hipHostFree(c->refit_stage_host);
+    if (c->refit_stage_dev) (void)hipFree(c->refit_stage_dev);
+    c->refit_stage_host = c->refit_stage_dev = nullptr;
+    c->refit_stage_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->refit_stage_host, want, hipHostMallocDefault), "hipHostMalloc(refit staging)");
+    HIPCHK(c, hipMalloc(&c->refit_stage_dev, want), "hipMalloc(refit staging)");
+    c->refit_stage_cap = want;
+  }
+  float* stage = (float*)c->refit_stage_host;  // idle: the previous refit synchronised
+  const unsigned char* src = (const unsigned char*)vtx;
+  for (uint32_t i = 0; i < vcount; ++i)
+    std::memcpy(stage + (size_t)i * words, src + (size_t)i * stride, words * sizeof(float));
+  HIPCHK(c, hipMemcpyAsync(c->refit_stage_dev, stage, bytes, hipMemcpyHostToDevice, c->stream), "upload refit vertices");
+  return refit_run(c, id, (const float*)c->refit_stage_dev, words, normals);
+}
+
+rt_status rt_blas_refit_device(rt_ctx_t c, rt_blas_t id, const void* vtx_dev, uint32_t vcount, uint32_t stride,
+                               void* hip_stream) {
+  rt_status st = refit_check(c, id, vtx_dev, vcount, stride);
+  if (st != RT_OK) return st;
+  (void)hipSetDevice(c->device);
+  // The device-wide wait also completes the work already enqueued on hip_stream (the producer of vtx_dev), so
+  // the refit's kernels on the context stream read finished vertices: no further ordering is needed.
+  (void)hip_stream;
+  HIPCHK(c, quiesce(c), "rt_blas_refit_device: wait for in-flight work");
+  return refit_run(c, id, (const float*)vtx_dev, stride / 4, stride >= 24);
 }
 
 rt_status rt_blas_info(rt_ctx_t c, rt_blas_t id, rt_bvh_info* out) {
@@ -824,6 +948,7 @@ rt_status rt_tlas_build(rt_ctx_t c, const rt_instance* in, uint32_t n, int updat
   if (c->cur >= 0 && c->cur != w) HIPCHK(c, note_swap_out(c->ver[c->cur]), "rt_tlas_build: record the readers");
   c->cur = w;
   c->tlas_stale = false;
+  c->tlas_refit = false;  // the instance boxes above are those of the refitted BLASes
   c->tlas_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
   return RT_OK;
 }
@@ -1159,6 +1284,8 @@ rt_status check_dispatch(rt_ctx* c, uint32_t W, uint32_t H, const void* rgba8, b
   if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, "rt_dispatch_rays: no TLAS built");
   if (c->tlas_stale)
     return fail(c, RT_E_INVALID, "rt_dispatch_rays: scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
+  if (c->tlas_refit)
+    return fail(c, RT_E_INVALID, "rt_dispatch_rays: BLAS refitted, rt_tlas_build (an update will do) must follow");
   if (!c->have_shading) return fail(c, RT_E_INVALID, "rt_dispatch_rays: shading not set");
   if (!c->have_camera && !cameras_given) return fail(c, RT_E_INVALID, "rt_dispatch_rays: camera not set");
   if (W == 0 || H == 0 || !rgba8) return fail(c, RT_E_INVALID, "rt_dispatch_rays: bad size or output");
@@ -1694,6 +1821,8 @@ rt_status rt_trace_rays(rt_ctx_t c, const float* rays, uint32_t n, uint32_t ray_
   if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, "rt_trace_rays: no TLAS built");
   if (c->tlas_stale)
     return fail(c, RT_E_INVALID, "rt_trace_rays: scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
+  if (c->tlas_refit)
+    return fail(c, RT_E_INVALID, "rt_trace_rays: BLAS refitted, rt_tlas_build (an update will do) must follow");
   (void)hipSetDevice(c->device);
   rt::SceneView sv = scene_view(c);
   sv.cull_sense = cull_front ? -1.0f : 1.0f;

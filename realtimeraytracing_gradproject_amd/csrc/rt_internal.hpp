@@ -70,6 +70,33 @@ hipError_t blas_reorder(const TriRec* d_in, const uint32_t* d_sorted, uint32_t n
 // (d_tris in leaf order, as any of the build paths left it), from the BLAS's {pos, normal} vertices and indices.
 hipError_t blas_vertex_records(const TriRec* d_tris, const float* d_vtx, const uint32_t* d_idx, uint32_t n,
                                TriVtx* d_out, hipStream_t stream);
+// In-place refit of a built BLAS (rt_blas_refit): the vertices at src (device memory, src_words floats per
+// vertex, position first, the normal in words 3 .. 5 when src_normals) replace those of vtx; the triangle records
+// are recomputed in leaf order and the child boxes bottom-up, topology untouched. pool_nodes / pool_tris /
+// pool_vtx: the BLAS's first node / triangle in the scene pools, or null where it has no slots (or the pool is not
+// live); they receive the same boxes and records. scratch: blas_refit_scratch_bytes(nnodes) bytes of device
+// memory kept with the BLAS; parents_ready tells that an earlier refit of this tree left its parent table there.
+// Enqueues on `stream` and ends with the copy of the root box to root_host (pinned, 6 floats): the caller
+// synchronises.
+struct BlasRefit {
+  const float* src = nullptr;
+  uint32_t src_words = 0;
+  bool src_normals = false;
+  float* vtx = nullptr;
+  const uint32_t* idx = nullptr;
+  uint32_t nvtx = 0, ntri = 0, nnodes = 0;
+  Bvh4Node* nodes = nullptr;
+  TriRec* tris = nullptr;
+  void* scratch = nullptr;
+  bool parents_ready = false;
+  Bvh4Node* pool_nodes = nullptr;
+  TriRec* pool_tris = nullptr;
+  TriVtx* pool_vtx = nullptr;
+  float* root_host = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;  // recorded before / after the kernels (the refit's device time)
+};
+size_t blas_refit_scratch_bytes(uint32_t nnodes);
+hipError_t blas_refit(const BlasRefit& r, hipStream_t stream);
 // Copies n nodes into the scene pool at dst, rebasing internal refs by node_base and leaf refs
 // (~slot) by tri_base (TLAS: node_base = 0, tri_base = -1 keeps ~instance refs).
 hipError_t pool_rebase(const Bvh4Node* src, uint32_t n, uint32_t node_base, int64_t tri_base, Bvh4Node* dst,

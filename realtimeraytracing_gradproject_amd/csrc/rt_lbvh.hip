@@ -2310,4 +2310,206 @@ hipError_t tlas_prepare(const InstanceRec* d_inst, const float* d_blas_bounds, u
   return hipGetLastError();
 }
 
+// --- BLAS refit (rt_blas_refit): same BVH4 topology and leaf order, new vertices ------------------------------
+//
+// Three launches on the BLAS's own arrays (and its slots of the scene pool, written alongside): the vertices, the
+// triangle records, the child boxes bottom-up. The nodes carry no parent link, so one more launch derives a parent
+// table the first time a BLAS is refitted (k_refit_parents); it depends on the topology only and is kept.
+namespace {
+
+constexpr uint32_t kRefitRoot = 0xffffffffu;  // parent word of node 0
+constexpr uint32_t kRefitOneWg = 1024;        // nodes one workgroup climbs with its arrival counters in LDS
+
+// parent[c] = p << 5 | slot << 3 | arrivals node p waits for (its internal children, 1 .. 4), for every internal
+// child c of every node p.
+__global__ void k_refit_parents(const Bvh4Node* __restrict__ nodes, uint32_t nn, uint32_t* __restrict__ parent) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn) return;
+  if (i == 0) parent[0] = kRefitRoot;
+  const uint32_t m = nodes[i].inner_mask & 15u;
+  const uint32_t need = (uint32_t)__popc(m);
+  for (uint32_t k = 0; k < 4; ++k) {
+    const int32_t c = nodes[i].child[k];
+    if (((m >> k) & 1u) && c > 0 && (uint32_t)c < nn) parent[c] = (i << 5) | (k << 3) | need;
+  }
+}
+
+// The new vertices into the BLAS's {pos, normal} array: src holds `sw` words per vertex, the position first and,
+// with `normals`, the normal in words 3 .. 5 (without: the stored normal stays).
+__global__ void k_refit_vertices(const float* __restrict__ src, uint32_t sw, uint32_t nv, bool normals,
+                                 float* __restrict__ vtx) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nv) return;
+  const float* p = src + (size_t)i * sw;
+  float* o = vtx + (size_t)i * 6;
+  const int nw = normals ? 6 : 3;
+  for (int k = 0; k < nw; ++k) o[k] = p[k];
+}
+
+// One thread per leaf-order slot: k_tri_setup's record of triangle tris[i].prim from the new vertices (the same
+// operations, so the same bits as a fresh build's), into the BLAS's array and its slots of the pools that are live
+// (pool_tris / pool_vtx: already offset to the BLAS's first slot, or null). The first nn threads also clear the
+// climb's arrival counters.
+__global__ void k_refit_tris(const float* __restrict__ vtx, const uint32_t* __restrict__ idx, uint32_t n,
+                             TriRec* __restrict__ tris, TriRec* __restrict__ pool_tris, TriVtx* __restrict__ pool_vtx,
+                             uint32_t* __restrict__ counters, uint32_t nn) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nn) counters[i] = 0u;
+  if (i >= n) return;
+  TriRec t = tris[i];  // prim and the padding words stay
+  const uint32_t p = t.prim;
+  const uint32_t i0 = idx ? idx[3 * p] : 3 * p, i1 = idx ? idx[3 * p + 1] : 3 * p + 1,
+                 i2 = idx ? idx[3 * p + 2] : 3 * p + 2;
+  const float* a = vtx + (size_t)i0 * 6;
+  const float* b = vtx + (size_t)i1 * 6;
+  const float* c = vtx + (size_t)i2 * 6;
+  TriVtx w;
+  for (int k = 0; k < 3; ++k) {
+    t.v0[k] = a[k];
+    t.e1[k] = b[k] - a[k];
+    t.e2[k] = c[k] - a[k];
+    w.v0[k] = a[k];
+    w.v1[k] = b[k];
+    w.v2[k] = c[k];
+  }
+  tris[i] = t;
+  if (pool_tris) pool_tris[i] = t;
+  if (pool_vtx) {
+    w.prim = p;
+    w.pad1 = w.pad2 = 0;
+    pool_vtx[i] = w;
+  }
+}
+
+// float offset of box word q (lo.xyz, hi.xyz) of slot k inside a Bvh4Node (lox, hix, loy, hiy, loz, hiz: 4 each)
+__device__ __forceinline__ int slot_word(int q, int k) { return (q < 3 ? q * 8 : (q - 3) * 8 + 4) + k; }
+
+// The box pass: bottom-up over the BVH4 nodes with arrival counters, as k_refit climbs the binary tree. One thread
+// per node; a thread whose node has no internal child starts there, every other thread returns at once. The thread
+// at a node writes the node's child boxes — a leaf slot from the triangle's new vertices (k_tri_setup's canonical
+// box), an internal slot from that child's union — then hands the node's own union to the parent: the union goes to
+// ubox[node], one arrival is counted at the parent, and the thread whose arrival completes the parent (as many
+// arrivals as the parent has internal children) goes on there; every other thread returns. No thread waits for
+// another. The node's 128 bytes are written by that one thread only, with plain stores (nothing reads them before the
+// kernel ends); only the unions cross threads:
+//   kOneWg (the tree fits one workgroup): counters in LDS, workgroup-scope release / acquire around them, as the
+//     climb of k_build_small;
+//   otherwise: write-through stores of the union, vmcnt(0), an agent-scope counter, coherent loads — the hand-off
+//     of k_refit (RT_REFIT_WT), with its fence form when RT_REFIT_WT is 0.
+// `pool` (null, or the BLAS's first node in the scene pool) gets the same box words: the rebased copy differs in
+// its refs only. root_out: the root's union (the BLAS bounds).
+template <bool kOneWg>
+__global__ __launch_bounds__(kOneWg ? 1024 : 256) void k_refit_boxes(
+    Bvh4Node* __restrict__ nodes, uint32_t nn, const uint32_t* __restrict__ parent, uint32_t* counters, float* ubox,
+    const float* __restrict__ vtx, const uint32_t* __restrict__ idx, const TriRec* __restrict__ tris, uint32_t ntri,
+    Bvh4Node* __restrict__ pool, float* __restrict__ root_out) {
+  __shared__ uint32_t s_cnt[kOneWg ? kRefitOneWg : 1];
+  if (kOneWg) {
+    s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+  }
+  uint32_t node = blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= nn) return;
+  if (nodes[node].inner_mask & 15u) return;
+  for (;;) {
+    const int32_t ch[4] = {nodes[node].child[0], nodes[node].child[1], nodes[node].child[2], nodes[node].child[3]};
+    float* nb = (float*)(nodes + node);
+    float* pb = pool ? (float*)(pool + node) : nullptr;
+    float u[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int32_t c = ch[k];
+      if (c == kEmptyChild) continue;
+      if (c >= 0 ? (uint32_t)c >= nn : (uint32_t)~c >= ntri) continue;  // (a ref outside the BLAS would be a bug)
+      float bb[6];
+      if (c >= 0) {
+        const float* cu = ubox + (size_t)c * 6;
+        for (int q = 0; q < 6; ++q) bb[q] = (kOneWg || !RT_REFIT_WT) ? cu[q] : ld_wt(cu + q);
+      } else {
+        const uint32_t p = tris[~c].prim;
+        const uint32_t i0 = idx ? idx[3 * p] : 3 * p, i1 = idx ? idx[3 * p + 1] : 3 * p + 1,
+                       i2 = idx ? idx[3 * p + 2] : 3 * p + 2;
+        const float* a = vtx + (size_t)i0 * 6;
+        const float* b = vtx + (size_t)i1 * 6;
+        const float* d = vtx + (size_t)i2 * 6;
+        for (int q = 0; q < 3; ++q) {
+          bb[q] = fminf(fminf(a[q], b[q]), d[q]) + 0.0f;  // canonical +0, as k_tri_setup
+          bb[3 + q] = fmaxf(fmaxf(a[q], b[q]), d[q]) + 0.0f;
+        }
+      }
+      for (int q = 0; q < 6; ++q) {
+        nb[slot_word(q, k)] = bb[q];
+        if (pb) pb[slot_word(q, k)] = bb[q];
+      }
+      for (int q = 0; q < 3; ++q) {
+        u[q] = fminf(u[q], bb[q]);
+        u[3 + q] = fmaxf(u[3 + q], bb[3 + q]);
+      }
+    }
+    const uint32_t pr = parent[node];
+    if (pr == kRefitRoot) {
+      for (int q = 0; q < 6; ++q) root_out[q] = u[q];
+      return;
+    }
+    const uint32_t up = pr >> 5, need = pr & 7u;
+    if (up >= nn) return;  // (likewise)
+    float* o = ubox + (size_t)node * 6;
+    uint32_t old;
+    if (kOneWg) {
+      for (int q = 0; q < 6; ++q) o[q] = u[q];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      old = __hip_atomic_fetch_add(&s_cnt[up], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (old + 1u != need) return;
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    } else {
+#if RT_REFIT_WT
+      for (int q = 0; q < 6; ++q) st_wt(o + q, u[q]);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      old = __hip_atomic_fetch_add(&counters[up], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old + 1u != need) return;
+#else
+      for (int q = 0; q < 6; ++q) o[q] = u[q];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      old = __hip_atomic_fetch_add(&counters[up], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old + 1u != need) return;
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    }
+    node = up;
+  }
+}
+
+}  // namespace
+
+size_t blas_refit_scratch_bytes(uint32_t nnodes) { return (size_t)nnodes * (4 + 4 + 24) + 32; }
+
+hipError_t blas_refit(const BlasRefit& r, hipStream_t s) {
+  if (r.ntri == 0 || r.nnodes == 0 || r.nvtx == 0) return hipErrorInvalidValue;
+  // the BLAS's scratch: parent table | arrival counters | per-node unions | root box
+  uint32_t* parent = (uint32_t*)r.scratch;
+  uint32_t* counters = parent + r.nnodes;
+  float* ubox = (float*)(counters + r.nnodes);
+  float* root = ubox + (size_t)r.nnodes * 6;
+  RT_TRY(hipEventRecord(r.e0, s));
+  if (!r.parents_ready) {
+    k_refit_parents<<<grid1(r.nnodes, 256), 256, 0, s>>>(r.nodes, r.nnodes, parent);
+    RT_TRY(hipGetLastError());
+  }
+  k_refit_vertices<<<grid1(r.nvtx, 256), 256, 0, s>>>(r.src, r.src_words, r.nvtx, r.src_normals, r.vtx);
+  k_refit_tris<<<grid1(r.ntri > r.nnodes ? r.ntri : r.nnodes, 256), 256, 0, s>>>(
+      r.vtx, r.idx, r.ntri, r.tris, r.pool_tris, r.pool_vtx, counters, r.nnodes);
+  if (r.nnodes <= kRefitOneWg)
+    k_refit_boxes<true><<<1, kRefitOneWg, 0, s>>>(r.nodes, r.nnodes, parent, counters, ubox, r.vtx, r.idx, r.tris,
+                                                   r.ntri, r.pool_nodes, root);
+  else
+    k_refit_boxes<false><<<grid1(r.nnodes, 256), 256, 0, s>>>(r.nodes, r.nnodes, parent, counters, ubox, r.vtx,
+                                                               r.idx, r.tris, r.ntri, r.pool_nodes, root);
+  RT_TRY(hipGetLastError());
+  RT_TRY(hipEventRecord(r.e1, s));
+  return hipMemcpyAsync(r.root_host, root, 6 * sizeof(float), hipMemcpyDeviceToHost, s);
+}
+
 }  // namespace rt
