@@ -27,7 +27,8 @@ extern "C" {
 #endif
 
 /* Still 4: rt_set_triangle_test, rt_host_trace_triangles and the RT_TRIANGLE_TEST_* constants were added without
- * changing any existing entry point, structure or default (backward compatible additions). */
+ * changing any existing entry point, structure or default (backward compatible additions); so were rt_blas_refit /
+ * rt_blas_refit_device, and rt_dispatch_gbuffer, rt_host_shading_normals and the rt_gbuffer structure. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -301,6 +302,43 @@ rt_status rt_dispatch_rays(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t*
  * and the frames' waves share one grid (no tail between them). Same stream rules as rt_dispatch_rays. */
 rt_status rt_dispatch_frames(rt_ctx_t ctx, uint32_t W, uint32_t H, uint32_t nframes, const float* cameras,
                              void* rgba8_dev, uint64_t frame_stride, void* hip_stream);
+/* Primary-visibility outputs of one rt_dispatch_gbuffer launch; each plane is a device pointer or NULL (not written);
+ * at least one non-NULL. hits and normal are aligned to 16 bytes, uv and object to 8 (RT_E_INVALID otherwise).
+ * Pixel order is rt_dispatch_rays' compact order: entry (r * W + x) is pixel x of global row rows[r]. */
+typedef struct {
+  uint32_t* hits;    /* n x 4 words, exactly rt_trace_rays' record for the pixel's camera ray (tmin 0, tmax 1e5, no
+                        flags): (t as float, instance_id, primitive index, hit flag); a miss has flag 0 and t = tmax */
+  float*    uv;      /* n x 2: the hit's barycentrics (u, v) as rt_trace_rays writes them; a miss: 0, 0 */
+  float*    normal;  /* n x 4: xyz = the world-space normal the reference's hit program of that hit group computes —
+                        RT_HITGROUP_MODEL: CalculateInterpolatedWorldNormal (Hit.hlsl:67-81, un-negated, unit length);
+                        RT_HITGROUP_PLANE: the face normal times the instance normal matrix, NOT renormalised
+                        (Hit.hlsl:218-222) — w = 0; a miss: 0,0,0,0 */
+  uint32_t* object;  /* n x 2: (index of the instance in the rt_tlas_build list, its hit_group); a miss: ~0u, ~0u */
+} rt_gbuffer;
+
+/* The G-buffer pass: the primary-visibility data of the frame rt_dispatch_rays renders, on its pixel grid, for a
+ * denoiser, temporal reprojection, an upscaler or object picking. W, H, rows, nrows as rt_dispatch_rays (rows NULL =
+ * all H rows in order).
+ * Which ray: one camera ray per pixel through the pixel centre (offsets 0.5, 0.5), the ray rt_dispatch_rays traces at
+ * spp 1, bit for bit. rt_set_shading's spp, mode, lights and material do not affect it, and the call works on a
+ * context where rt_set_shading was never called: it needs a camera (rt_set_camera) and a current TLAS only.
+ * No shading work: no shadow rays, no reflection rays, no tile balance (the plain grid, as a watertight frame).
+ * Honours rt_set_schedule (RT_SCHED_PACKET by default, falling back to RT_SCHED_LANE when the scene's worst-case
+ * packet stack is 64 entries or more; rt_set_tile_rows does not apply: 8 x 8 tiles), rt_set_triangle_test (hit
+ * distances and barycentrics are then the watertight test's, as rt_trace_rays') and rt_set_stats:
+ * RT_STAT_PRIMARY_RAYS and RT_STAT_PIXELS grow by nrows * W, RT_STAT_DISPATCHES by 1, the traversal counters as a
+ * frame's primary rays make them grow, RT_STAT_SHADOW_RAYS and RT_STAT_REFLECTION_RAYS not at all.
+ * Stream and lifetime rules are rt_dispatch_rays': asynchronous on hip_stream (NULL = the context's stream); frames
+ * and G-buffer launches may be in flight on several streams at once, the row list's device copy and the HBM overflow
+ * stack coming from the same rings of slots; the launch is noted for the TLAS double buffer and for
+ * rt_forget_stream; between an rt_blas_refit and the next rt_tlas_build it returns RT_E_INVALID.
+ * Errors: RT_E_INVALID for a NULL `out`, all four planes NULL, a misaligned plane, W, H or nrows of 0, nrows > H, a
+ * row index >= H, no TLAS or no camera (rt_last_error says which); nothing is written then. RT_E_UNSUPPORTED for
+ * nrows * W >= 2^32 - 1 pixels or trees deeper than the traversal stack.
+ * No reference counterpart: DXR exposes RayTCurrent, InstanceID, PrimitiveIndex and the attributes inside hit
+ * programs only, and the reference writes nothing but the colour (RayGen.hlsl:42). */
+rt_status rt_dispatch_gbuffer(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                              const rt_gbuffer* out, void* hip_stream);
 /* Stream lifetime: the context notes (host-side, no event per launch) which streams launched with the current
  * TLAS version, and records one event on each of them when the next rt_tlas_build swaps that version out; the tile
  * balance likewise notes the streams that read a work list, and queries the stream of a shape's previous launch
@@ -511,6 +549,19 @@ void rt_camera_buffer(const float view[16], uint32_t W, uint32_t H, float fov_de
 rt_status rt_host_trace_triangles(const void* vtx, uint32_t vcount, uint32_t stride, const uint32_t* idx,
                                   uint32_t icount, const float* object_to_world, const float* rays, uint32_t n,
                                   uint32_t ray_flags, int triangle_test, uint32_t* hits, float* uv);
+
+/* The G-buffer's normal (rt_gbuffer.normal) for n hits on ONE mesh under ONE instance transform, on the host: the
+ * check of rt_dispatch_gbuffer's normal plane (it calls the same normal functions the kernels call) and a way to
+ * shade a picked hit without a launch. vtx / vcount / stride / idx / icount as rt_blas_build (host arrays; stride >=
+ * 24: the normals are read); object_to_world: 3x4 row-major, NULL = identity (singular: RT_E_INVALID), with the normal
+ * matrix transpose(inverse(upper3x3)) derived as rt_tlas_build derives it; hit_group: RT_HITGROUP_MODEL
+ * (CalculateInterpolatedWorldNormal, Hit.hlsl:67-81, un-negated) or RT_HITGROUP_PLANE (the face normal through the
+ * normal matrix, Hit.hlsl:218-222); prims: n primitive indices; uv: n x 2 barycentrics (read for the model group
+ * only); out: n x 4 floats (w = 0). Null or mis-sized arguments, a primitive index out of range: RT_E_INVALID. No
+ * reference counterpart on the host (the normals exist inside the hit programs only). */
+rt_status rt_host_shading_normals(const void* vtx, uint32_t vcount, uint32_t stride, const uint32_t* idx, uint32_t icount,
+                                  const float* object_to_world, uint32_t hit_group, const uint32_t* prims,
+                                  const float* uv, uint32_t n, float* out);
 
 /* ---- Camera manipulator ------------------------------------------------------------------------
  * nv_helpers_dx12::Manipulator (include/manipulator.h:33-148, src/manipulator.cpp) as plain data the

@@ -69,6 +69,12 @@ class rt_bvh_info(ctypes.Structure):
                 ("build_ms", ctypes.c_double)]
 
 
+class rt_gbuffer(ctypes.Structure):
+    """include/rt_api.h rt_gbuffer: the output planes of rt_dispatch_gbuffer (device pointers, None: not written)."""
+    _fields_ = [("hits", ctypes.c_void_p), ("uv", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("object", ctypes.c_void_p)]
+
+
 class rt_manipulator(ctypes.Structure):
     """include/rt_api.h rt_manipulator: nv_helpers_dx12::Manipulator state (manipulator.h:124-144)."""
     _fields_ = [("pos", ctypes.c_float * 3), ("interest", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
@@ -113,6 +119,7 @@ SIGNATURES = [
     ("rt_set_stats", _I, [_P, _I]),
     ("rt_dispatch_rays", _I, [_P, _U32, _U32, _P, _U32, _P, _P, _P]),
     ("rt_dispatch_frames", _I, [_P, _U32, _U32, _U32, _P, _P, ctypes.c_uint64, _P]),
+    ("rt_dispatch_gbuffer", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer), _P]),
     ("rt_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _P]),
     ("rt_raster_draw", _I, [_P, _UP, _U32, _FP, _U32, _U32, _P, _P, _P]),
     ("rt_assemble_strips", _I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P]),
@@ -153,6 +160,7 @@ SIGNATURES = [
     ("rt_camera_lookat", None, [_FP, _FP, _FP, _FP]),
     ("rt_camera_buffer", None, [_FP, _U32, _U32, ctypes.c_float, ctypes.c_float, ctypes.c_float, _FP]),
     ("rt_host_trace_triangles", _I, [_P, _U32, _U32, _P, _U32, _P, _P, _U32, _U32, _I, _P, _P]),
+    ("rt_host_shading_normals", _I, [_P, _U32, _U32, _P, _U32, _P, _U32, _P, _P, _U32, _P]),
     ("rt_manip_init", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_update", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_set_lookat", None, [ctypes.POINTER(rt_manipulator), _FP, _FP, _FP]),
@@ -311,6 +319,30 @@ def host_trace_triangles(vertices, indices, rays, triangle_test: int = RT_TRIANG
     if st != RT_OK:
         raise RtError(st, "rt_host_trace_triangles")
     return hits, uv
+
+
+def host_shading_normals(vertices, indices, prims, uv, hit_group: int = RT_HITGROUP_MODEL, object_to_world=None):
+    """rt_host_shading_normals: the G-buffer's normal plane on the host (no GPU), for hits on one mesh under one
+    instance transform. vertices: (nv, k >= 6) floats {pos, normal, ..}; indices: uint32 triangle list or None; prims:
+    n primitive indices; uv: (n, 2) barycentrics; hit_group: RT_HITGROUP_MODEL or RT_HITGROUP_PLANE; object_to_world:
+    12 floats (3x4 row-major) or None. Returns (n, 4) float32 (w = 0)."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    if v.ndim != 2:
+        v = v.reshape(-1, 6)
+    i = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+    x = None if object_to_world is None else _f32(object_to_world, 12)
+    p = np.ascontiguousarray(prims, dtype=np.uint32).ravel()
+    b = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    if b.shape[0] != p.size:
+        raise ValueError(f"expected {p.size} (u, v) pairs, got {b.shape[0]}")
+    out = np.zeros((p.size, 4), np.float32)
+    st = lib.rt_host_shading_normals(v.ctypes.data_as(_P), v.shape[0], v.shape[1] * 4,
+                                     None if i is None else i.ctypes.data_as(_P), 0 if i is None else i.size,
+                                     None if x is None else x.ctypes.data_as(_P), hit_group, p.ctypes.data_as(_P),
+                                     b.ctypes.data_as(_P), p.size, out.ctypes.data_as(_P))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_shading_normals")
+    return out
 
 
 class Manipulator:
@@ -803,6 +835,50 @@ class Context:
         self._pending = True
         self._check(self._lib.rt_dispatch_frames(self._h, width, height, n, None if cams is None else _fptr(cams),
                                                  _ptr(rgba8), frame_stride, stream), "rt_dispatch_frames")
+
+    def dispatch_gbuffer(self, width: int, height: int, hits=None, uv=None, normal=None, object=None,  # noqa: A002
+                         rows: Optional[np.ndarray] = None, stream: Optional[int] = None):
+        """rt_dispatch_gbuffer: the frame's primary-visibility planes, nrows * width entries each in the compact row
+        order of dispatch(): hits (4 x 32-bit words per pixel: t, instance id, primitive, hit flag), uv (2 floats),
+        normal (4 floats, w = 0), object (2 words: instance index, hit group). Device tensors (or raw addresses); a
+        plane left None is not written; at least one must be given."""
+        if rows is not None:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+            rp, nr = r.ctypes.data_as(_P), r.size
+        else:
+            rp, nr = None, height
+        g = rt_gbuffer()
+        for name, t, words in (("hits", hits, 4), ("uv", uv, 2), ("normal", normal, 4), ("object", object, 2)):
+            if t is not None and not isinstance(t, int):
+                if t.element_size() != 4 or t.numel() != nr * width * words or not t.is_contiguous():
+                    raise ValueError(f"dispatch_gbuffer: {name} must be a contiguous tensor of {nr * width * words} "
+                                     f"32-bit elements, got {t.numel()} of {t.element_size()} bytes")
+            setattr(g, name, _ptr(t))
+        self._check(self._lib.rt_dispatch_gbuffer(self._h, width, height, rp, nr, ctypes.byref(g), stream),
+                    "rt_dispatch_gbuffer")
+
+    def pick(self, width: int, height: int, x: int, y: int) -> Optional[dict]:
+        """What the camera ray through the centre of pixel (x, y) of a width x height frame hits: None on a miss, else
+        t, instance_id, instance (index in the tlas_build list), hit_group, primitive, uv and the world normal (see
+        rt_gbuffer). One one-row G-buffer launch on torch's current stream, synchronised."""
+        if not (0 <= x < width and 0 <= y < height):
+            raise ValueError(f"pick: pixel ({x}, {y}) outside {width} x {height}")
+        dev = f"cuda:{self.device}"
+        hits = torch.empty((width, 4), dtype=torch.int32, device=dev)
+        uv = torch.empty((width, 2), dtype=torch.float32, device=dev)
+        nrm = torch.empty((width, 4), dtype=torch.float32, device=dev)
+        obj = torch.empty((width, 2), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(self.device)
+        self.dispatch_gbuffer(width, height, hits, uv, nrm, obj, rows=np.array([y], np.uint32),
+                              stream=stream.cuda_stream)
+        stream.synchronize()
+        h = hits[x].cpu().numpy().view(np.uint32)
+        if h[3] == 0:
+            return None
+        o = obj[x].cpu().numpy().view(np.uint32)
+        return {"t": float(h[0:1].view(np.float32)[0]), "instance_id": int(h[1]), "instance": int(o[0]),
+                "hit_group": int(o[1]), "primitive": int(h[2]), "uv": tuple(float(v) for v in uv[x].cpu().numpy()),
+                "normal": tuple(float(v) for v in nrm[x, :3].cpu().numpy())}
 
     def trace_rays(self, rays, n: int, any_hit: bool, hits, uv=None, stream: Optional[int] = None,
                    cull_back: bool = False, cull_front: bool = False):

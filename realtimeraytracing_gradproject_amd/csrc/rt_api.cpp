@@ -1809,6 +1809,66 @@ rt_status rt_dispatch_frames(rt_ctx_t c, uint32_t W, uint32_t H, uint32_t nframe
   return rt::dispatch_frame(c, W, H, nullptr, H, rgba8, nullptr, s, 4, nframes, cameras, frame_stride, 0);
 }
 
+rt_status rt_dispatch_gbuffer(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                              const rt_gbuffer* out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  if (!out) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: null output structure");
+  if (!out->hits && !out->uv && !out->normal && !out->object)
+    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: every output plane is null");
+  if (((uintptr_t)out->hits | (uintptr_t)out->normal) % 16u || ((uintptr_t)out->uv | (uintptr_t)out->object) % 8u)
+    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: output plane not aligned (hits, normal: 16 bytes; uv, object: 8)");
+  if (W == 0 || H == 0) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: bad size");
+  if (!rows) nrows = H;
+  if (nrows == 0 || nrows > H) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: bad row count");
+  if (rows)
+    for (uint32_t r = 0; r < nrows; ++r)
+      if (rows[r] >= H) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: row index out of range");
+  if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: no TLAS built");
+  if (c->tlas_stale)
+    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
+  if (c->tlas_refit)
+    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: BLAS refitted, rt_tlas_build (an update will do) must follow");
+  if (!c->have_camera) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: camera not set");
+  // the kernels index a plane's entries with 32 bits, as the frame kernels index their pixels
+  if ((uint64_t)nrows * W >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, "rt_dispatch_gbuffer: more than 2^32 pixels");
+  (void)hipSetDevice(c->device);
+  hipStream_t s = pick_stream(c, stream);
+  rt::SceneView sv = scene_view(c);
+  if (sv.stack_cap > rt::kMaxTraversalStack)
+    return fail(c, RT_E_UNSUPPORTED, "rt_dispatch_gbuffer: BVH too deep for the traversal stack");
+  rt::GbufParams gb;
+  rt::frame_cam(c->cam_cb, gb.cam);
+  gb.width = W;
+  gb.nrows = nrows;
+  gb.fwidth = (float)W;  // exact: W, H < 2^24
+  gb.fheight = (float)H;
+  gb.hits = out->hits;
+  gb.uv = out->uv;
+  gb.normal = out->normal;
+  gb.object = out->object;
+  rt_status st;
+  const uint32_t* d_rows = nullptr;
+  ScratchSlot* rows_slot = nullptr;
+  uint64_t rows_gen = 0;
+  if (rows && (st = ensure_rows(c, rows, nrows, s, &rows_slot, &d_rows, &rows_gen)) != RT_OK) return st;
+  ScratchSlot* ovf_slot = nullptr;
+  if (!rt::gbuffer_packet(sv, c->schedule)) {  // the per-lane kernel's overflow stack: 16 x 16 pixel workgroups
+    const size_t lanes = (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256;
+    if ((st = ensure_overflow(c, sv, lanes, s, &ovf_slot)) != RT_OK) return st;
+  }
+  HIPCHK(c, order_after_tlas(c, s), "rt_dispatch_gbuffer: order after the TLAS build");
+  const hipError_t e = rt::launch_trace_gbuffer(sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, s);
+  if (e != hipSuccess) return hip_fail(c, e, "G-buffer launch");
+  HIPCHK(c, note_reader(c->ver[c->cur], s), "rt_dispatch_gbuffer: record use");
+  if (ovf_slot) HIPCHK(c, slot_mark_use(*ovf_slot, s), "overflow stack: record use");
+  if (rows_slot) HIPCHK(c, slot_mark_use(*rows_slot, s), "rows: record use");
+  if (c->stats_on) {
+    c->dispatches += 1;
+    c->pixels += (uint64_t)W * nrows;
+  }
+  return RT_OK;
+}
+
 rt_status rt_trace_rays(rt_ctx_t c, const float* rays, uint32_t n, uint32_t ray_flags, uint32_t* hits, float* uv,
                         void* stream) {
   if (!c || (!rays && n) || (!hits && n)) return fail(c, RT_E_INVALID, "rt_trace_rays: null argument");
@@ -1943,6 +2003,46 @@ rt_status rt_host_trace_triangles(const void* vtx, uint32_t vcount, uint32_t str
   }
   trace_range(done, n);
   for (auto& t : pool) t.join();
+  return RT_OK;
+}
+
+// Host service: the G-buffer's normal plane for hits on one mesh under one instance transform, with the hit-program
+// normal functions of rt_device.hpp the kernels call and the normal matrix fill_instance_xform derives for
+// rt_tlas_build. Here beside rt_host_trace_triangles for the same reason. No context, no GPU call.
+rt_status rt_host_shading_normals(const void* vtx, uint32_t vcount, uint32_t stride, const uint32_t* idx,
+                                  uint32_t icount, const float* object_to_world, uint32_t hit_group,
+                                  const uint32_t* prims, const float* uv, uint32_t n, float* out) {
+  if (!vtx || vcount == 0 || stride < 24 || (stride % 4) || (n && (!prims || !uv || !out))) return RT_E_INVALID;
+  if (hit_group != RT_HITGROUP_MODEL && hit_group != RT_HITGROUP_PLANE) return RT_E_INVALID;
+  uint32_t ntri;
+  if (idx) {
+    if (icount == 0 || icount % 3) return RT_E_INVALID;
+    for (uint32_t i = 0; i < icount; ++i)
+      if (idx[i] >= vcount) return RT_E_INVALID;
+    ntri = icount / 3;
+  } else {
+    if (vcount % 3) return RT_E_INVALID;
+    ntri = vcount / 3;
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (prims[i] >= ntri) return RT_E_INVALID;
+  const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  rt::InstanceRec ir;
+  std::memset(&ir, 0, sizeof(ir));
+  if (!fill_instance_xform(object_to_world ? object_to_world : I, ir)) return RT_E_INVALID;
+  const float* v = (const float*)vtx;
+  const uint32_t vstride = stride / 4;
+  for (uint32_t i = 0; i < n; ++i) {
+    const rt::V3 nr = hit_group == RT_HITGROUP_PLANE
+                          ? rt::face_world_normal<false>(v, vstride, idx, ir.nrm, prims[i])
+                          : rt::interpolated_world_normal<false>(v, vstride, idx, ir.nrm, prims[i], uv[2 * (size_t)i],
+                                                                 uv[2 * (size_t)i + 1]);
+    float* o = out + 4 * (size_t)i;
+    o[0] = nr.x;
+    o[1] = nr.y;
+    o[2] = nr.z;
+    o[3] = 0.0f;
+  }
   return RT_OK;
 }
 

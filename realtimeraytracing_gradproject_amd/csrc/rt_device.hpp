@@ -227,6 +227,19 @@ struct FrameParams {
   uint32_t waves_per_frame;  // waves of the plain grid per frame (wave slot = frame * waves_per_frame + ...)
 };
 
+// What a G-buffer launch (rt_dispatch_gbuffer) needs besides the scene: RayGen's camera, the frame's size and the
+// output planes (device pointers, each may be null: not written; entry orow * width + x of a plane is pixel x of
+// the row list's entry orow). No lights, no material: the pass traces the camera rays and shades nothing.
+struct GbufParams {
+  FrameCam cam;
+  uint32_t width, nrows;
+  float fwidth, fheight;  // the frame's width and height as floats (height: the full frame's, not the row count)
+  uint32_t* hits;         // 4 words per pixel: rt_trace_rays' record
+  float* uv;              // 2 floats
+  float* normal;          // 4 floats
+  uint32_t* object;       // 2 words: instance index, hit group
+};
+
 // Tile-balance split codes (FrameParams::plan): parts per tile. The costliest quadrant of the costliest C4 tiles
 // takes 0.55 of the whole packet's fetches, the costliest 2 x 2 cell 0.35 (tools/split_study.py): the kernel's
 // estimate of a whole tile from one part's time, and the plan's estimate of a part from the whole.
@@ -660,6 +673,68 @@ RT_HD bool watertight(V3 o, const WtRay& w, V3 A, V3 B, V3 C, float face, float&
 RT_HD V3 reflect_dir(V3 i, V3 n) {
   const float t = dot(i, n);
   return v3(i.x - (2.0f * n.x) * t, i.y - (2.0f * n.y) * t, i.z - (2.0f * n.z) * t);
+}
+
+// ------------------------------------------------------------------------------------------
+// Hit-program normals (Hit.hlsl:67-81, :218-222), over plain data: the mesh's {pos, normal} vertex array
+// (vstride floats per vertex), its triangle list (or null: non-indexed) and the instance's 9-float normal matrix.
+// The kernels call them on the scene's device arrays (rt_trace.hip passes address-space-1 pointers: FP / IP are
+// template parameters so the loads stay global loads), rt_host_shading_normals on the caller's host arrays: the
+// same operations in the same order, so the same bits.
+// ------------------------------------------------------------------------------------------
+template <typename IP>
+RT_HD void tri_vertex_ids(IP idx, uint32_t prim, uint32_t& i0, uint32_t& i1, uint32_t& i2) {
+  if (idx) {
+    i0 = idx[3 * prim];
+    i1 = idx[3 * prim + 1];
+    i2 = idx[3 * prim + 2];
+  } else {
+    i0 = 3 * prim;
+    i1 = 3 * prim + 1;
+    i2 = 3 * prim + 2;
+  }
+}
+
+template <typename FP>
+RT_HD V3 ldv3(FP p) {
+  return v3(p[0], p[1], p[2]);
+}
+
+// normalize with its 1 / sqrt by rcp_exact when EX (the IEEE 1.0f / x, bit for bit: the same vector). Used on the REF
+// shading's paths only: in the Lambert kernels the extra uniform branch of rcp_exact's slow path costs more than the
+// division it replaces (RT_RCP_EXACT), in the REF kernels it pays.
+template <bool EX>
+RT_HD V3 normalize_x(V3 a) {
+  if (EX) return muls(a, rcp_exact(sqrtf(dot(a, a))));
+  return normalize(a);
+}
+
+// CalculateInterpolatedWorldNormal (Hit.hlsl:67-81): vertex order 1,2,0 against (u, v, 1-u-v).
+template <bool EX, typename FP, typename IP>
+RT_HD V3 interpolated_world_normal(FP vtx, uint32_t vstride, IP idx, const float* nrm, uint32_t prim, float u,
+                                   float v) {
+  uint32_t i0, i1, i2;
+  tri_vertex_ids(idx, prim, i0, i1, i2);
+  const V3 n0 = ldv3(vtx + (size_t)i1 * vstride + 3);
+  const V3 n1 = ldv3(vtx + (size_t)i2 * vstride + 3);
+  const V3 n2 = ldv3(vtx + (size_t)i0 * vstride + 3);
+  const float bz = (1.0f - u) - v;
+  V3 n = normalize_x<EX>(add(add(muls(n0, u), muls(n1, v)), muls(n2, bz)));
+  n = mat3_mul(nrm, n);
+  return normalize_x<EX>(n);
+}
+
+// PlaneClosestHit face normal (Hit.hlsl:218-222): normalize(cross(e1, e2)), then the instance
+// normal matrix without renormalisation.
+template <bool EX, typename FP, typename IP>
+RT_HD V3 face_world_normal(FP vtx, uint32_t vstride, IP idx, const float* nrm, uint32_t prim) {
+  uint32_t i0, i1, i2;
+  tri_vertex_ids(idx, prim, i0, i1, i2);
+  const V3 p0 = ldv3(vtx + (size_t)i0 * vstride);
+  const V3 p1 = ldv3(vtx + (size_t)i1 * vstride);
+  const V3 p2 = ldv3(vtx + (size_t)i2 * vstride);
+  V3 n = normalize_x<EX>(cross(sub(p1, p0), sub(p2, p0)));
+  return mat3_mul(nrm, n);
 }
 
 }  // namespace rt

@@ -171,6 +171,13 @@ hipError_t launch_trace_rays(const SceneView& scene, const float* rays, uint32_t
                              uint32_t* hits, float* uv, unsigned long long* d_stats, bool stats,
                              hipStream_t stream);
 
+// The G-buffer pass (rt_dispatch_gbuffer): the plain grid of the packet kernel, or (gbuffer_packet false: the
+// per-lane schedule, or trees too deep for the packet stack) the per-lane kernel over 16 x 16 pixel workgroups, whose
+// scene view carries the launch's overflow stack. Counters when `stats`; the triangle test is sc.tri_test.
+bool gbuffer_packet(const SceneView& scene, int schedule);
+hipError_t launch_trace_gbuffer(const SceneView& scene, const GbufParams& gb, const uint32_t* d_rows,
+                                unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
+
 // rank_stride_rows: rows from one rank's block of `gathered` to the next (0: rows_per_rank, one frame per block;
 // a batched gather holds several frames per rank block and passes their total)
 // in_bpp: bytes per pixel of the gathered strips (4 RGBA8, 3 RGB8: the alpha byte restored as 255); out is RGBA8

@@ -1080,55 +1080,16 @@ __device__ __forceinline__ HitInstance load_hit_instance(const SceneView& sc, ui
   return h;
 }
 
-__device__ __forceinline__ V3 ldg3(const RT_GLOBAL float* p) { return v3(p[0], p[1], p[2]); }
-
-__device__ __forceinline__ void tri_vertex_ids(const HitInstance& hi, uint32_t prim, uint32_t& i0, uint32_t& i1,
-                                               uint32_t& i2) {
-  if (hi.idx) {
-    i0 = hi.idx[3 * prim];
-    i1 = hi.idx[3 * prim + 1];
-    i2 = hi.idx[3 * prim + 2];
-  } else {
-    i0 = 3 * prim;
-    i1 = 3 * prim + 1;
-    i2 = 3 * prim + 2;
-  }
-}
-
-// normalize with its 1 / sqrt by rcp_exact when EX (the IEEE 1.0f / x, bit for bit: the same vector). Used on the REF
-// shading's paths only: in the Lambert kernels the extra uniform branch of rcp_exact's slow path costs more than the
-// division it replaces (RT_RCP_EXACT), in the REF kernels it pays.
-template <bool EX>
-__device__ __forceinline__ V3 normalize_x(V3 a) {
-  if (EX) return muls(a, rcp_exact(sqrtf(dot(a, a))));
-  return normalize(a);
-}
-
-// CalculateInterpolatedWorldNormal (Hit.hlsl:67-81): vertex order 1,2,0 against (u, v, 1-u-v).
+// The hit programs' normals (rt_device.hpp: interpolated_world_normal, face_world_normal — shared with the host
+// service rt_host_shading_normals) on a hit instance's device arrays: 6 floats per vertex, global loads.
 template <bool EX = false>
 __device__ V3 interpolated_world_normal(const HitInstance& hi, uint32_t prim, float u, float v) {
-  uint32_t i0, i1, i2;
-  tri_vertex_ids(hi, prim, i0, i1, i2);
-  const V3 n0 = ldg3(hi.vtx + (size_t)i1 * 6 + 3);
-  const V3 n1 = ldg3(hi.vtx + (size_t)i2 * 6 + 3);
-  const V3 n2 = ldg3(hi.vtx + (size_t)i0 * 6 + 3);
-  const float bz = (1.0f - u) - v;
-  V3 n = normalize_x<EX>(add(add(muls(n0, u), muls(n1, v)), muls(n2, bz)));
-  n = mat3_mul(hi.nrm, n);
-  return normalize_x<EX>(n);
+  return rt::interpolated_world_normal<EX>(hi.vtx, 6u, hi.idx, hi.nrm, prim, u, v);
 }
 
-// PlaneClosestHit face normal (Hit.hlsl:218-222): normalize(cross(e1, e2)), then the instance
-// normal matrix without renormalisation.
 template <bool EX = false>
 __device__ V3 face_world_normal(const HitInstance& hi, uint32_t prim) {
-  uint32_t i0, i1, i2;
-  tri_vertex_ids(hi, prim, i0, i1, i2);
-  const V3 p0 = ldg3(hi.vtx + (size_t)i0 * 6);
-  const V3 p1 = ldg3(hi.vtx + (size_t)i1 * 6);
-  const V3 p2 = ldg3(hi.vtx + (size_t)i2 * 6);
-  V3 n = normalize_x<EX>(cross(sub(p1, p0), sub(p2, p0)));
-  return mat3_mul(hi.nrm, n);
+  return rt::face_world_normal<EX>(hi.vtx, 6u, hi.idx, hi.nrm, prim);
 }
 
 
@@ -1737,6 +1698,108 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays(SceneView sc, const float
     hits[i] = make_uint4(__float_as_uint(f ? h.t : b.w), f ? h.inst : 0xffffffffu,
                          f ? h.prim : 0xffffffffu, f ? 1u : 0u);
     if (uv) uv[i] = make_float2(f ? h.u : 0.0f, f ? h.v : 0.0f);
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
+// ------------------------------------------------------------------------------------------
+// G-buffer pass (rt_dispatch_gbuffer): the primary-visibility data of a frame — the camera ray's hit record,
+// barycentrics, the hit program's world normal, instance and hit group — with no shading work. No reference
+// counterpart: DXR shows RayTCurrent / InstanceID / PrimitiveIndex / the attributes to hit programs only.
+// ------------------------------------------------------------------------------------------
+
+// RayGen's camera ray of pixel (px, py) through its centre: shade_sample_packet's expressions, in its order.
+__device__ __forceinline__ void gbuffer_ray(const GbufParams& gb, uint32_t px, uint32_t py, V3& O, V3& D) {
+  const float dx = (((float)px + 0.5f) / gb.fwidth) * 2.0f - 1.0f;
+  const float dy = (((float)py + 0.5f) / gb.fheight) * 2.0f - 1.0f;
+  float dc[4], dw[4];
+  const float ndc[4] = {dx, -dy, 1.0f, 1.0f};
+  hlsl_mul4(gb.cam.proj_inv, ndc, dc);
+  const float dcam[4] = {dc[0], dc[1], dc[2], 0.0f};
+  hlsl_mul4(gb.cam.view_inv, dcam, dw);
+  O = v3(gb.cam.origin[0], gb.cam.origin[1], gb.cam.origin[2]);  // mul(viewInverse, (0,0,0,1))
+  D = normalize(v3(dw[0], dw[1], dw[2]));  // CastDefaultRay
+}
+
+// One pixel's planes: entry o of each plane the launch asked for (the pointers are kernel arguments: one uniform
+// branch per plane). hits / normal are one 16-B store per lane (an 8-pixel tile row is a full 128-B line), uv /
+// object one 8-B store. A miss: t = tmax, flag 0, ids ~0, zeros elsewhere, by the same stores. The model group's
+// normal is CalculateInterpolatedWorldNormal un-negated (EX false: its negation is what the Lambert kernels shade
+// with, bit for bit), the plane group's the face normal through the normal matrix (not renormalised).
+__device__ __forceinline__ void gbuffer_store(const SceneView& sc, const GbufParams& gb, uint32_t o, bool f,
+                                              const HitRec& hit) {
+  if (gb.hits)
+    reinterpret_cast<uint4*>(gb.hits)[o] = make_uint4(__float_as_uint(f ? hit.t : 100000.0f), f ? hit.inst : 0xffffffffu,
+                                                      f ? hit.prim : 0xffffffffu, f ? 1u : 0u);
+  if (gb.uv) reinterpret_cast<float2*>(gb.uv)[o] = make_float2(f ? hit.u : 0.0f, f ? hit.v : 0.0f);
+  if (gb.normal) {
+    V3 n = v3(0.0f, 0.0f, 0.0f);
+    if (f) {
+      const HitInstance ir = load_hit_instance(sc, hit.inst);
+      n = ir.hit_group == 2u ? face_world_normal(ir, hit.prim) : interpolated_world_normal(ir, hit.prim, hit.u, hit.v);
+    }
+    reinterpret_cast<float4*>(gb.normal)[o] = make_float4(n.x, n.y, n.z, 0.0f);
+  }
+  if (gb.object) {
+    uint32_t group = 0xffffffffu;
+    if (f) group = gp(sc.inst)[hit.inst].hit_group;
+    reinterpret_cast<uint2*>(gb.object)[o] = make_uint2(f ? hit.inst : 0xffffffffu, group);
+  }
+}
+
+// Packet schedule: the frame kernel's one-sample layout (a wave = an 8 x 8 pixel tile, a workgroup RT_PACKET_WX x
+// RT_PACKET_WY waves, the plain grid), one closest-hit packet walk per wave. Rays outside the image or the row list
+// join the packet dead; only in-image pixels are stored. Held to the plain kernels' SGPR budget (8 waves per SIMD).
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_PLAIN_SGPR_ATTR
+void k_trace_gbuffer_packet(SceneView sc, GbufParams gb, const uint32_t* __restrict__ rows,
+                            unsigned long long* __restrict__ stats) {
+#if RT_LDS_TOP
+  {
+    const RT_GLOBAL f4v* src = (const RT_GLOBAL f4v*)((const RT_GLOBAL char*)sc.pool_nodes + ((uint32_t)sc.lds_root << 7));
+    const uint32_t nrow = (uint32_t)sc.lds_n * 8u;
+    for (uint32_t i = threadIdx.x; i < nrow; i += packet_block(1)) g_top[i] = src[i];
+    __syncthreads();
+  }
+#endif
+  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
+  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
+  const bool inimg = x < gb.width && orow < gb.nrows;
+  uint32_t py = 0;
+  if (inimg) py = rows ? rows[orow] : orow;
+  V3 O, D;
+  gbuffer_ray(gb, x, py, O, D);
+  Counters cnt;
+  if (STATS && inimg) ++cnt.primary;
+  HitRec hit;
+  bool found;
+  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  if (inimg) gbuffer_store(sc, gb, orow * gb.width + x, found, hit);  // < 2^32 pixels (rt_api.cpp)
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_frame's indexing, LDS stack
+// and per-launch HBM overflow.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_gbuffer(SceneView sc, GbufParams gb, const uint32_t* __restrict__ rows,
+                                                          unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  Counters cnt;
+  if (px < gb.width && orow < gb.nrows) {
+    const uint32_t py = rows ? rows[orow] : orow;
+    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+    V3 O, D;
+    gbuffer_ray(gb, px, py, O, D);
+    HitRec hit;
+    if (STATS) ++cnt.primary;
+    const bool f = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
+    gbuffer_store(sc, gb, orow * gb.width + px, f, hit);
   }
   if (STATS) flush_stats<false>(cnt, stats);
 }
@@ -2387,6 +2450,37 @@ hipError_t launch_trace_rays(const SceneView& sc, const float* rays, uint32_t n,
     else { if (stats) RT_LAUNCH_RAYS(false, false, true); else RT_LAUNCH_RAYS(false, false, false); }
   }
 #undef RT_LAUNCH_RAYS
+  return hipGetLastError();
+}
+
+bool gbuffer_packet(const SceneView& sc, int schedule) {
+  return schedule == RT_SCHED_PACKET && sc.packet_cap < kPacketStack;  // packet_geometry's rule
+}
+
+hipError_t launch_trace_gbuffer(const SceneView& sc, const GbufParams& gb, const uint32_t* d_rows,
+                                unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
+  // counters and the triangle test (sc.tri_test: the watertight instantiations on the vertex-form pool) are
+  // compile-time choices, as for the frame kernels
+#define RT_LAUNCH_GBUF(K, GRID, BLOCK, LDS)                                                                  \
+  do {                                                                                                       \
+    if (sc.tri_test) {                                                                                       \
+      if (stats) hipLaunchKernelGGL((K<true, 1>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);              \
+      else hipLaunchKernelGGL((K<false, 1>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);                   \
+    } else {                                                                                                 \
+      if (stats) hipLaunchKernelGGL((K<true, 0>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);              \
+      else hipLaunchKernelGGL((K<false, 0>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);                   \
+    }                                                                                                        \
+  } while (0)
+  if (gbuffer_packet(sc, schedule)) {
+    const uint32_t tw = 8u * (uint32_t)packet_wx(1), th = 8u * (uint32_t)packet_wy(1);
+    const dim3 grid((gb.width + tw - 1) / tw, (gb.nrows + th - 1) / th);
+    RT_LAUNCH_GBUF(k_trace_gbuffer_packet, grid, dim3(packet_block(1)), 0);
+  } else {
+    const dim3 grid((gb.width + 15) / 16, (gb.nrows + 15) / 16);
+    const size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
+    RT_LAUNCH_GBUF(k_trace_gbuffer, grid, dim3(kBlock), lds);
+  }
+#undef RT_LAUNCH_GBUF
   return hipGetLastError();
 }
 
