@@ -28,7 +28,8 @@ extern "C" {
 
 /* Still 4: rt_set_triangle_test, rt_host_trace_triangles and the RT_TRIANGLE_TEST_* constants were added without
  * changing any existing entry point, structure or default (backward compatible additions); so were rt_blas_refit /
- * rt_blas_refit_device, and rt_dispatch_gbuffer, rt_host_shading_normals and the rt_gbuffer structure. */
+ * rt_blas_refit_device, rt_dispatch_gbuffer, rt_host_shading_normals and the rt_gbuffer structure, and
+ * rt_set_motion_history, rt_dispatch_gbuffer_motion, rt_host_motion_project / _vectors and rt_gbuffer_motion. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -339,6 +340,56 @@ typedef struct {
  * programs only, and the reference writes nothing but the colour (RayGen.hlsl:42). */
 rt_status rt_dispatch_gbuffer(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
                               const rt_gbuffer* out, void* hip_stream);
+
+/* Motion history, for rt_dispatch_gbuffer_motion. 0 (default): nothing is kept; rt_blas_refit and rt_tlas_build do
+ * exactly what they do without it (no allocation, no copy, no extra upload). 1: from the next rt_tlas_build on, each
+ * TLAS version also holds, per instance, that instance's PREVIOUS object-to-world matrix and a pointer to its BLAS's
+ * PREVIOUS vertex positions; that next build counts as a changed layout (it waits for all in-flight work once), later
+ * per-frame updates are again the fast path. What "previous" means:
+ *  - the previous state is the scene as of the rt_tlas_build before the one that made the current TLAS;
+ *  - instance i's previous transform is instance i's transform in that earlier list, provided the list had an
+ *    instance i with the same BLAS id and that BLAS was not rebuilt in between; otherwise it is the current transform
+ *    (a new or re-meshed object has no motion);
+ *  - a BLAS's previous positions are its positions before the FIRST rt_blas_refit[_device] issued between the two
+ *    builds (one device-to-device copy, taken by that refit; later refits in the interval do not snapshot again);
+ *    with no refit in between they are the current positions (the record points at the live array, no copy);
+ *    rt_blas_rebuild resets the BLAS to no motion;
+ *  - the first rt_tlas_build after history is switched on has no predecessor: everything is static;
+ *  - the previous camera is the caller's (prev_cb below): the caller owns frame pacing.
+ * RT_E_INVALID for a NULL context. */
+rt_status rt_set_motion_history(rt_ctx_t ctx, int enable);
+
+/* rt_gbuffer's four planes, exactly, and a fifth. At least one of the five non-NULL. */
+typedef struct {
+  uint32_t* hits;
+  float*    uv;
+  float*    normal;
+  uint32_t* object;
+  float*    motion;  /* n x 4 floats, 16-byte aligned: (mx, my, w_prev, w_cur), see rt_dispatch_gbuffer_motion */
+} rt_gbuffer_motion;
+
+/* rt_dispatch_gbuffer with a motion plane, for temporal reprojection and upscalers. Everything rt_dispatch_gbuffer
+ * documents holds: the camera ray, the schedule rule and its per-lane fall-back, the triangle test, the counters (the
+ * motion plane adds nothing to them), the slot rings, streams and lifetimes, its errors; hits, uv, normal and object
+ * come out bit-identical to rt_dispatch_gbuffer's for the same launch.
+ * motion, per pixel: (mx, my, w_prev, w_cur). The hit's object point P = (p1 u + p2 v) + p0 ((1 - u) - v) (the
+ * vertex order and weights of the interpolated normal) is evaluated on the BLAS's current and on its previous
+ * positions; each goes through its own object-to-world 3x4 (the instance's current / previous transform) and is
+ * projected with its own camera buffer (the context's / prev_cb, rt_set_camera's layout; prev_cb NULL = the
+ * context's camera): clip = mul(projection, mul(view, (P, 1))), x = (clip.x / clip.w + 1) * 0.5 * W,
+ * y = (1 - clip.y / clip.w) * 0.5 * H (H the full frame's height, not nrows). mx = x_prev - x_cur and
+ * my = y_prev - y_cur in pixels (+x right, +y down): pixel (px, py)'s surface point was at (px + 0.5 + mx,
+ * py + 0.5 + my) in the previous frame. w_prev, w_cur: the two clip.w, the view depth (for the reference's
+ * XMMatrixPerspectiveFovRH the distance along the view axis). The current position is projected too, never assumed,
+ * so a point whose inputs did not change gets exactly mx = my = 0 and w_prev == w_cur, bit for bit. A miss is the
+ * static world point O + D * 1e5 through the same projection (the sky moves under camera rotation). w_prev <= 0 (the
+ * point was behind the previous camera): mx = my = +INFINITY, w_prev still written. float32, no contraction, IEEE
+ * quotients.
+ * Errors beyond rt_dispatch_gbuffer's, RT_E_INVALID with nothing written (rt_last_error says which): a motion plane
+ * while history is off, or while the current TLAS was built before history was switched on; motion not 16-byte
+ * aligned. Without a motion plane the call needs no history. */
+rt_status rt_dispatch_gbuffer_motion(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                     const rt_gbuffer_motion* out, const float prev_cb[64], void* hip_stream);
 /* Stream lifetime: the context notes (host-side, no event per launch) which streams launched with the current
  * TLAS version, and records one event on each of them when the next rt_tlas_build swaps that version out; the tile
  * balance likewise notes the streams that read a work list, and queries the stream of a shape's previous launch
@@ -562,6 +613,26 @@ rt_status rt_host_trace_triangles(const void* vtx, uint32_t vcount, uint32_t str
 rt_status rt_host_shading_normals(const void* vtx, uint32_t vcount, uint32_t stride, const uint32_t* idx, uint32_t icount,
                                   const float* object_to_world, uint32_t hit_group, const uint32_t* prims,
                                   const float* uv, uint32_t n, float* out);
+
+/* The projection stage of rt_gbuffer_motion.motion on the host, for n pairs of world points: pts_cur / pts_prev
+ * n x 3 floats (the point now and in the previous frame), cb / prev_cb the two camera buffers (rt_set_camera's
+ * layout; prev_cb NULL = cb), W x H the full frame; out: n x 4 floats (mx, my, w_prev, w_cur) as
+ * rt_dispatch_gbuffer_motion defines them. It calls the function the motion kernels call. Null arguments, W or H of
+ * 0: RT_E_INVALID (n = 0 with null arrays is RT_OK). */
+rt_status rt_host_motion_project(const float* pts_cur, const float* pts_prev, uint32_t n, const float cb[64],
+                                 const float prev_cb[64], uint32_t W, uint32_t H, float* out);
+
+/* rt_gbuffer_motion.motion for n hits on ONE mesh under ONE instance, on the host: the object-point stage and the
+ * projection stage the motion kernels run, so the check of rt_dispatch_gbuffer_motion's plane. vtx / vcount / stride /
+ * idx / icount as rt_blas_build (host arrays, stride >= 12); prev_vtx: the previous vertices in the same layout, NULL
+ * = vtx; object_to_world / prev_object_to_world: 3x4 row-major, NULL = identity / = object_to_world, used as given
+ * (no inverse is taken: a singular matrix is not an error here); cb, prev_cb, W, H as rt_host_motion_project; prims:
+ * n primitive indices; uv: n x 2 barycentrics; out: n x 4 floats. Null or mis-sized arguments, a primitive index out
+ * of range: RT_E_INVALID. */
+rt_status rt_host_motion_vectors(const void* vtx, const void* prev_vtx, uint32_t vcount, uint32_t stride,
+                                 const uint32_t* idx, uint32_t icount, const float* object_to_world,
+                                 const float* prev_object_to_world, const float cb[64], const float prev_cb[64],
+                                 uint32_t W, uint32_t H, const uint32_t* prims, const float* uv, uint32_t n, float* out);
 
 /* ---- Camera manipulator ------------------------------------------------------------------------
  * nv_helpers_dx12::Manipulator (include/manipulator.h:33-148, src/manipulator.cpp) as plain data the

@@ -75,6 +75,12 @@ class rt_gbuffer(ctypes.Structure):
                 ("object", ctypes.c_void_p)]
 
 
+class rt_gbuffer_motion(ctypes.Structure):
+    """include/rt_api.h rt_gbuffer_motion: rt_gbuffer's planes and the motion plane of rt_dispatch_gbuffer_motion."""
+    _fields_ = [("hits", ctypes.c_void_p), ("uv", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("object", ctypes.c_void_p), ("motion", ctypes.c_void_p)]
+
+
 class rt_manipulator(ctypes.Structure):
     """include/rt_api.h rt_manipulator: nv_helpers_dx12::Manipulator state (manipulator.h:124-144)."""
     _fields_ = [("pos", ctypes.c_float * 3), ("interest", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
@@ -120,6 +126,8 @@ SIGNATURES = [
     ("rt_dispatch_rays", _I, [_P, _U32, _U32, _P, _U32, _P, _P, _P]),
     ("rt_dispatch_frames", _I, [_P, _U32, _U32, _U32, _P, _P, ctypes.c_uint64, _P]),
     ("rt_dispatch_gbuffer", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer), _P]),
+    ("rt_set_motion_history", _I, [_P, _I]),
+    ("rt_dispatch_gbuffer_motion", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer_motion), _FP, _P]),
     ("rt_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _P]),
     ("rt_raster_draw", _I, [_P, _UP, _U32, _FP, _U32, _U32, _P, _P, _P]),
     ("rt_assemble_strips", _I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P]),
@@ -161,6 +169,8 @@ SIGNATURES = [
     ("rt_camera_buffer", None, [_FP, _U32, _U32, ctypes.c_float, ctypes.c_float, ctypes.c_float, _FP]),
     ("rt_host_trace_triangles", _I, [_P, _U32, _U32, _P, _U32, _P, _P, _U32, _U32, _I, _P, _P]),
     ("rt_host_shading_normals", _I, [_P, _U32, _U32, _P, _U32, _P, _U32, _P, _P, _U32, _P]),
+    ("rt_host_motion_project", _I, [_P, _P, _U32, _P, _P, _U32, _U32, _P]),
+    ("rt_host_motion_vectors", _I, [_P, _P, _U32, _U32, _P, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
     ("rt_manip_init", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_update", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_set_lookat", None, [ctypes.POINTER(rt_manipulator), _FP, _FP, _FP]),
@@ -342,6 +352,59 @@ def host_shading_normals(vertices, indices, prims, uv, hit_group: int = RT_HITGR
                                      b.ctypes.data_as(_P), p.size, out.ctypes.data_as(_P))
     if st != RT_OK:
         raise RtError(st, "rt_host_shading_normals")
+    return out
+
+
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(_P)
+
+
+def host_motion_project(points, prev_points, camera, prev_camera, width: int, height: int):
+    """rt_host_motion_project: the motion plane's projection stage on the host (no GPU). points / prev_points: (n, 3)
+    world points now and in the previous frame; camera / prev_camera: 64-float camera buffers (prev_camera None: the
+    same camera). Returns (n, 4) float32: mx, my, w_prev, w_cur (rt_dispatch_gbuffer_motion)."""
+    a = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(prev_points, dtype=np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError(f"expected {a.shape[0]} previous points, got {b.shape[0]}")
+    cb = _f32(camera, 64)
+    pcb = None if prev_camera is None else _f32(prev_camera, 64)
+    out = np.zeros((a.shape[0], 4), np.float32)
+    st = lib.rt_host_motion_project(_vp(a), _vp(b), a.shape[0], _vp(cb), _vp(pcb), width, height, _vp(out))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_motion_project")
+    return out
+
+
+def host_motion_vectors(vertices, indices, prims, uv, camera, width: int, height: int, prev_vertices=None,
+                        object_to_world=None, prev_object_to_world=None, prev_camera=None):
+    """rt_host_motion_vectors: the motion plane on the host (no GPU) for hits on one mesh under one instance.
+    vertices: (nv, k >= 3) floats; prev_vertices: the same layout or None (= vertices); indices: uint32 triangle list
+    or None; prims: n primitive indices; uv: (n, 2) barycentrics; object_to_world / prev_object_to_world: 12 floats
+    or None (identity / the current one); camera / prev_camera: 64-float camera buffers (prev_camera None: the same).
+    Returns (n, 4) float32: mx, my, w_prev, w_cur."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    if v.ndim != 2:
+        v = v.reshape(-1, 6)
+    pv = None
+    if prev_vertices is not None:
+        pv = np.ascontiguousarray(prev_vertices, dtype=np.float32).reshape(-1, v.shape[1])
+        if pv.shape != v.shape:
+            raise ValueError(f"previous vertices: expected shape {v.shape}, got {pv.shape}")
+    i = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+    x = None if object_to_world is None else _f32(object_to_world, 12)
+    px = None if prev_object_to_world is None else _f32(prev_object_to_world, 12)
+    cb = _f32(camera, 64)
+    pcb = None if prev_camera is None else _f32(prev_camera, 64)
+    p = np.ascontiguousarray(prims, dtype=np.uint32).ravel()
+    b = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    if b.shape[0] != p.size:
+        raise ValueError(f"expected {p.size} (u, v) pairs, got {b.shape[0]}")
+    out = np.zeros((p.size, 4), np.float32)
+    st = lib.rt_host_motion_vectors(_vp(v), _vp(pv), v.shape[0], v.shape[1] * 4, _vp(i), 0 if i is None else i.size,
+                                    _vp(x), _vp(px), _vp(cb), _vp(pcb), width, height, _vp(p), _vp(b), p.size, _vp(out))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_motion_vectors")
     return out
 
 
@@ -856,6 +919,36 @@ class Context:
             setattr(g, name, _ptr(t))
         self._check(self._lib.rt_dispatch_gbuffer(self._h, width, height, rp, nr, ctypes.byref(g), stream),
                     "rt_dispatch_gbuffer")
+
+    def set_motion_history(self, on: bool):
+        """rt_set_motion_history: from the next tlas_build on, each TLAS version keeps every instance's previous
+        transform and its BLAS's positions before the interval's first refit (dispatch_gbuffer_motion's inputs)."""
+        self._check(self._lib.rt_set_motion_history(self._h, 1 if on else 0), "rt_set_motion_history")
+
+    def dispatch_gbuffer_motion(self, width: int, height: int, hits=None, uv=None, normal=None, object=None,  # noqa: A002
+                                motion=None, prev_camera=None, rows: Optional[np.ndarray] = None,
+                                stream: Optional[int] = None):
+        """rt_dispatch_gbuffer_motion: dispatch_gbuffer's planes and motion (4 floats per pixel: mx, my, w_prev,
+        w_cur — the pixel's surface point was at (x + 0.5 + mx, y + 0.5 + my) in the previous frame, +inf when it was
+        behind the previous camera; the two view depths). prev_camera: the previous frame's 64-float camera buffer
+        (None: the current camera). motion needs set_motion_history(True) before the TLAS was built."""
+        if rows is not None:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+            rp, nr = r.ctypes.data_as(_P), r.size
+        else:
+            rp, nr = None, height
+        g = rt_gbuffer_motion()
+        for name, t, words in (("hits", hits, 4), ("uv", uv, 2), ("normal", normal, 4), ("object", object, 2),
+                               ("motion", motion, 4)):
+            if t is not None and not isinstance(t, int):
+                if t.element_size() != 4 or t.numel() != nr * width * words or not t.is_contiguous():
+                    raise ValueError(f"dispatch_gbuffer_motion: {name} must be a contiguous tensor of "
+                                     f"{nr * width * words} 32-bit elements, got {t.numel()} of {t.element_size()} bytes")
+            setattr(g, name, _ptr(t))
+        pcb = None if prev_camera is None else _f32(prev_camera, 64)
+        self._check(self._lib.rt_dispatch_gbuffer_motion(self._h, width, height, rp, nr, ctypes.byref(g),
+                                                         None if pcb is None else _fptr(pcb), stream),
+                    "rt_dispatch_gbuffer_motion")
 
     def pick(self, width: int, height: int, x: int, y: int) -> Optional[dict]:
         """What the camera ray through the centre of pixel (x, y) of a width x height frame hits: None on a miss, else

@@ -29,18 +29,28 @@ struct DeviceBlas {
   // the first refit and kept: a rebuild makes a new DeviceBlas, so a new tree starts without it
   void* refit = nullptr;
   bool refit_parents = false;  // the parent table in `refit` is written
+  // motion history (rt_set_motion_history): the vertex array as it was before the first refit since the last
+  // rt_tlas_build (vtx's layout; allocated by the first refit made with history on and kept), whether that snapshot
+  // was taken since the last rt_tlas_build, and the tree's serial number (a rebuild makes a new DeviceBlas with a
+  // new one, and without a snapshot: a re-meshed object has no motion)
+  float* prev_vtx = nullptr;
+  bool prev_taken = false;
+  uint64_t serial = 0;
   void release() {
     if (nodes) (void)hipFree(nodes);
     if (tris) (void)hipFree(tris);
     if (vtx) (void)hipFree(vtx);
     if (idx) (void)hipFree(idx);
     if (refit) (void)hipFree(refit);
+    if (prev_vtx) (void)hipFree(prev_vtx);
     nodes = nullptr;
     tris = nullptr;
     vtx = nullptr;
     idx = nullptr;
     refit = nullptr;
     refit_parents = false;
+    prev_vtx = nullptr;
+    prev_taken = false;
   }
 };
 
@@ -154,8 +164,14 @@ struct TlasVersion {
   uint32_t pool_base = 0;         // this version's TLAS root in the scene pool
   bool valid = false;             // built against the current pool layout
   std::vector<rt_instance> host;  // the instances as given
-  rt::InstanceRec* staging = nullptr;  // pinned upload staging (records, then BLAS boxes)
+  rt::InstanceRec* staging = nullptr;  // pinned upload staging (records, then BLAS boxes, then motion records)
   size_t staging_bytes = 0;
+  // motion history: room for `motion_cap` MotionRecs after the boxes in `inst` and in the staging (0 while history
+  // is off: nothing is allocated for them), the records of this build (inside `inst`; null when built without
+  // history), and the serial numbers of the instances' BLASes at this build
+  uint32_t motion_cap = 0;
+  const rt::MotionRec* motion = nullptr;
+  std::vector<uint64_t> blas_serial;
   ScratchSlot use;                // launches that read this version: per-stream events, recorded when it stops being current
   std::vector<hipStream_t> readers;  // streams that launched with it since it became current (no event per launch)
   hipEvent_t ready = nullptr;     // recorded on the context stream when the version's pool slot is written
@@ -316,6 +332,8 @@ struct rt_ctx {
   // a BLAS was refitted after the last rt_tlas_build: the current TLAS holds its old box, so launches are refused
   // as for tlas_stale, but the pool layout stands and the next rt_tlas_build may be an update (the fast path)
   bool tlas_refit = false;
+  // rt_set_motion_history: TLAS versions carry MotionRecs and refits snapshot the vertices they overwrite
+  bool motion_on = false;
   // rt_blas_refit: staging of the host variant's vertices (pinned, then device; grown on demand), the pinned
   // readback of the root box, the timing events of the refit's kernels
   void* refit_stage_host = nullptr;
@@ -497,6 +515,10 @@ rt_status upload_blas(rt_ctx* c, DeviceBlas& b, const void* vtx, uint32_t vcount
 
 hipStream_t pick_stream(rt_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
 
+// Byte offset of the MotionRecs in a TLAS version's instance buffer (and its staging) for a build of n instances:
+// after the n records and the n BLAS boxes, at the records' 16-byte alignment.
+size_t motion_offset(uint32_t n) { return ((size_t)n * (sizeof(rt::InstanceRec) + 24) + 15) & ~(size_t)15; }
+
 // The watertight mode's vertex-form pool for the current pool layout (node_base / tri_base of pool_gen): one
 // k_tri_vertices launch per BLAS on the context stream, into [BLAS 0 | BLAS 1 ..] like pool_tris. The caller has
 // made sure nothing in flight reads the pool (rt_tlas_build's layout change has quiesced; rt_set_triangle_test
@@ -548,6 +570,14 @@ rt_status refit_run(rt_ctx* c, rt_blas_t id, const float* d_src, uint32_t src_wo
     HIPCHK(c, hipHostMalloc((void**)&c->refit_root_host, 32, hipHostMallocDefault), "hipHostMalloc(refit readback)");
   if (!c->refit_e0) HIPCHK(c, hipEventCreate(&c->refit_e0), "rt_blas_refit: event");
   if (!c->refit_e1) HIPCHK(c, hipEventCreate(&c->refit_e1), "rt_blas_refit: event");
+  // motion history: the positions this interval's first refit is about to overwrite, one device-to-device copy
+  // ahead of the refit's kernels on the same stream (nothing in flight reads prev_vtx: the caller has quiesced)
+  if (c->motion_on && !b.prev_taken) {
+    const size_t bytes = (size_t)b.nvtx * 6 * sizeof(float);
+    if (!b.prev_vtx) HIPCHK(c, hipMalloc(&b.prev_vtx, bytes), "hipMalloc(previous vertices)");
+    HIPCHK(c, hipMemcpyAsync(b.prev_vtx, b.vtx, bytes, hipMemcpyDeviceToDevice, s), "snapshot the previous vertices");
+    b.prev_taken = true;
+  }
   rt::BlasRefit r;
   r.src = d_src;
   r.src_words = src_words;
@@ -684,8 +714,8 @@ rt_status rt_blas_build(rt_ctx_t c, const void* vtx, uint32_t vcount, uint32_t s
     b.release();
     return st;
   }
+  b.serial = ++c->blas_gen;
   c->blas.push_back(b);
-  ++c->blas_gen;
   *out = (rt_blas_t)(c->blas.size() - 1);
   return RT_OK;
 }
@@ -702,8 +732,8 @@ rt_status rt_blas_rebuild(rt_ctx_t c, rt_blas_t id, const void* vtx, uint32_t vc
     return st;
   }
   c->blas[id].release();
+  b.serial = ++c->blas_gen;
   c->blas[id] = b;
-  ++c->blas_gen;
   c->tlas_stale = c->cur >= 0;  // the scene pool holds the old tree until rt_tlas_build
   return RT_OK;
 }
@@ -810,14 +840,36 @@ rt_status rt_tlas_build(rt_ctx_t c, const rt_instance* in, uint32_t n, int updat
     r.idx = b.idx;
     for (int k = 0; k < 6; ++k) bb[i * 6 + k] = b.bounds[k];
   }
+  // Motion history: each instance's record from the list this build replaces (the current version's, read here,
+  // before a layout change below clears `cur`), when that list was itself built with history on. Instance i keeps
+  // its earlier transform if the list had an instance i of the same, un-rebuilt BLAS; the previous positions are
+  // the refit's snapshot where one was taken since that build, else the live array (no copy).
+  std::vector<rt::MotionRec> mrecs;
+  std::vector<uint64_t> serials(n);
+  for (uint32_t i = 0; i < n; ++i) serials[i] = c->blas[in[i].blas].serial;
+  if (c->motion_on) {
+    const TlasVersion* pv = c->cur >= 0 && c->ver[c->cur].motion ? &c->ver[c->cur] : nullptr;
+    mrecs.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      const DeviceBlas& b = c->blas[in[i].blas];
+      const bool same = pv && i < pv->ninst && pv->host[i].blas == in[i].blas && pv->blas_serial[i] == b.serial;
+      rt::MotionRec& m = mrecs[i];
+      std::memcpy(m.prev_o2w, same ? pv->host[i].xform3x4_rowmajor : in[i].xform3x4_rowmajor, sizeof(m.prev_o2w));
+      m.prev_vtx = pv && b.prev_taken ? b.prev_vtx : b.vtx;
+      m.pad_ = 0;
+    }
+  }
   const uint32_t tlas_cap = n > 1 ? n - 1 : 1;
   hipStream_t s = c->stream;
   // Fast path (a per-frame update): the pool's BLAS part is current and each version's arrays and pool slot
   // hold n instances. The version launches do not read is written after ITS last launches (device-side waits),
   // with scratch kept from earlier builds: no device-wide synchronisation, no allocation. The host waits for
   // this build alone (the tree's node count and stack bound come back to size the next launches).
+  // (with motion history on, also room for n MotionRecs: the first build after the switch is a layout change)
+  const uint32_t motion_n = c->motion_on ? n : 0u;
   const bool fast = c->pool_gen == c->blas_gen && c->pool_tlas_cap >= tlas_cap && c->ver[0].cap >= n &&
-                    c->ver[1].cap >= n && c->tlas_scratch_cap >= n;
+                    c->ver[1].cap >= n && c->tlas_scratch_cap >= n && c->ver[0].motion_cap >= motion_n &&
+                    c->ver[1].motion_cap >= motion_n;
   if (!fast) {
     // layout change (BLAS built or rebuilt, more instances): every launch that may read the pools or the
     // instance records finishes first, as the reference waits on its fence before rebuilding (:1482-1568)
@@ -867,7 +919,8 @@ rt_status rt_tlas_build(rt_ctx_t c, const rt_instance* in, uint32_t n, int updat
       TlasVersion& tv = c->ver[v];
       tv.valid = false;
       tv.pool_base = (uint32_t)(tlas0 + (size_t)v * slot_cap);
-      if (tv.cap < n) {
+      tv.motion = nullptr;
+      if (tv.cap < n || tv.motion_cap < motion_n) {
         if (tv.nodes) (void)hipFree(tv.nodes);
         if (tv.inst) (void)hipFree(tv.inst);
         if (tv.sorted) (void)hipFree(tv.sorted);
@@ -877,13 +930,17 @@ rt_status rt_tlas_build(rt_ctx_t c, const rt_instance* in, uint32_t n, int updat
         tv.sorted = nullptr;
         tv.staging = nullptr;
         tv.cap = 0;
+        tv.motion_cap = 0;
         HIPCHK(c, hipMalloc(&tv.nodes, (size_t)tlas_cap * sizeof(rt::Bvh4Node)), "hipMalloc(tlas)");
-        // the instance records, then the BLAS boxes of the build (one upload from the staging, same layout)
-        HIPCHK(c, hipMalloc(&tv.inst, (size_t)n * (sizeof(rt::InstanceRec) + 24)), "hipMalloc(instances)");
+        // the instance records, then the BLAS boxes of the build, then (motion history on) the motion records: one
+        // upload from the staging, same layout
+        tv.staging_bytes = motion_n ? motion_offset(n) + (size_t)n * sizeof(rt::MotionRec)
+                                    : (size_t)n * sizeof(rt::InstanceRec) + (size_t)n * 24;
+        HIPCHK(c, hipMalloc(&tv.inst, tv.staging_bytes), "hipMalloc(instances)");
         HIPCHK(c, hipMalloc(&tv.sorted, (size_t)n * 4), "hipMalloc(tlas order)");
-        tv.staging_bytes = (size_t)n * sizeof(rt::InstanceRec) + (size_t)n * 24;
         HIPCHK(c, hipHostMalloc((void**)&tv.staging, tv.staging_bytes, hipHostMallocDefault), "hipHostMalloc(tlas staging)");
         tv.cap = n;
+        tv.motion_cap = motion_n;
       }
       if (!tv.ready && !(tv.ready = new_sync_event())) return fail(c, RT_E_HIP, "rt_tlas_build: event");
     }
@@ -916,10 +973,17 @@ rt_status rt_tlas_build(rt_ctx_t c, const rt_instance* in, uint32_t n, int updat
   std::memcpy(tv.staging, recs.data(), recs.size() * sizeof(rt::InstanceRec));  // staging idle: its last build synced
   float* bb_stage = (float*)((char*)tv.staging + (size_t)n * sizeof(rt::InstanceRec));
   std::memcpy(bb_stage, bb.data(), bb.size() * 4);
-  // records and boxes in one copy: the version's buffer holds the n records, then the n BLAS boxes
+  // records and boxes in one copy: the version's buffer holds the n records, then the n BLAS boxes (and, with
+  // motion history on, the n motion records behind them, in the same copy)
   const float* d_bb = (const float*)((const char*)tv.inst + (size_t)n * sizeof(rt::InstanceRec));
-  hipError_t e = hipMemcpyAsync(tv.inst, tv.staging, (size_t)n * sizeof(rt::InstanceRec) + bb.size() * 4,
-                                hipMemcpyHostToDevice, s);
+  size_t upload = (size_t)n * sizeof(rt::InstanceRec) + bb.size() * 4;
+  if (motion_n) {
+    char* m_stage = (char*)tv.staging + motion_offset(n);
+    std::memset((char*)tv.staging + upload, 0, motion_offset(n) - upload);
+    std::memcpy(m_stage, mrecs.data(), (size_t)n * sizeof(rt::MotionRec));
+    upload = motion_offset(n) + (size_t)n * sizeof(rt::MotionRec);
+  }
+  hipError_t e = hipMemcpyAsync(tv.inst, tv.staging, upload, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = rt::tlas_prepare(tv.inst, d_bb, n, c->d_tlas_box, s);
   float ms = 0.0f;
   uint32_t nn = 0, depth = 0, mstack = 0;
@@ -943,6 +1007,10 @@ rt_status rt_tlas_build(rt_ctx_t c, const rt_instance* in, uint32_t n, int updat
   std::memcpy(tv.bounds, bounds, sizeof(bounds));
   tv.ms = ms;
   tv.host.assign(in, in + n);
+  tv.blas_serial.swap(serials);
+  tv.motion = motion_n ? (const rt::MotionRec*)((const char*)tv.inst + motion_offset(n)) : nullptr;
+  if (motion_n)  // the next interval's first refit of each BLAS snapshots again
+    for (DeviceBlas& b : c->blas) b.prev_taken = false;
   tv.valid = true;
   // the version launches read until now: its readers' events, recorded now, cover every launch that read it
   if (c->cur >= 0 && c->cur != w) HIPCHK(c, note_swap_out(c->ver[c->cur]), "rt_tlas_build: record the readers");
@@ -1809,43 +1877,63 @@ rt_status rt_dispatch_frames(rt_ctx_t c, uint32_t W, uint32_t H, uint32_t nframe
   return rt::dispatch_frame(c, W, H, nullptr, H, rgba8, nullptr, s, 4, nframes, cameras, frame_stride, 0);
 }
 
-rt_status rt_dispatch_gbuffer(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
-                              const rt_gbuffer* out, void* stream) {
-  if (!c) return RT_E_INVALID;
-  if (!out) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: null output structure");
-  if (!out->hits && !out->uv && !out->normal && !out->object)
-    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: every output plane is null");
-  if (((uintptr_t)out->hits | (uintptr_t)out->normal) % 16u || ((uintptr_t)out->uv | (uintptr_t)out->object) % 8u)
-    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: output plane not aligned (hits, normal: 16 bytes; uv, object: 8)");
-  if (W == 0 || H == 0) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: bad size");
+// The forward chain of two camera buffers (rt_set_camera's layout: view cb[0..15], projection cb[16..31]; prev_cb
+// null: the same camera twice), as a motion launch and the host services pass it to rt_device.hpp's motion_entry.
+static void motion_cams(const float* cb, const float* prev_cb, rt::MotionCams& m) {
+  const float* pcb = prev_cb ? prev_cb : cb;
+  std::memcpy(m.view, cb, sizeof(m.view));
+  std::memcpy(m.proj, cb + 16, sizeof(m.proj));
+  std::memcpy(m.prev_view, pcb, sizeof(m.prev_view));
+  std::memcpy(m.prev_proj, pcb + 16, sizeof(m.prev_proj));
+}
+
+// rt_dispatch_gbuffer (fn names it in the messages; out.motion null, the four-plane kernels) and
+// rt_dispatch_gbuffer_motion (the motion kernels: the same four planes and out.motion, which may be null too).
+static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion_kernels, uint32_t W, uint32_t H,
+                                  const uint32_t* rows, uint32_t nrows, const rt_gbuffer_motion& out,
+                                  const float* prev_cb, void* stream) {
+  if (!out.hits && !out.uv && !out.normal && !out.object && !out.motion)
+    return fail(c, RT_E_INVALID, fn + ": every output plane is null");
+  if (((uintptr_t)out.hits | (uintptr_t)out.normal) % 16u || ((uintptr_t)out.uv | (uintptr_t)out.object) % 8u)
+    return fail(c, RT_E_INVALID, fn + ": output plane not aligned (hits, normal: 16 bytes; uv, object: 8)");
+  if ((uintptr_t)out.motion % 16u) return fail(c, RT_E_INVALID, fn + ": motion plane not aligned to 16 bytes");
+  if (W == 0 || H == 0) return fail(c, RT_E_INVALID, fn + ": bad size");
   if (!rows) nrows = H;
-  if (nrows == 0 || nrows > H) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: bad row count");
+  if (nrows == 0 || nrows > H) return fail(c, RT_E_INVALID, fn + ": bad row count");
   if (rows)
     for (uint32_t r = 0; r < nrows; ++r)
-      if (rows[r] >= H) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: row index out of range");
-  if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: no TLAS built");
+      if (rows[r] >= H) return fail(c, RT_E_INVALID, fn + ": row index out of range");
+  if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, fn + ": no TLAS built");
   if (c->tlas_stale)
-    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
+    return fail(c, RT_E_INVALID, fn + ": scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
   if (c->tlas_refit)
-    return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: BLAS refitted, rt_tlas_build (an update will do) must follow");
-  if (!c->have_camera) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: camera not set");
+    return fail(c, RT_E_INVALID, fn + ": BLAS refitted, rt_tlas_build (an update will do) must follow");
+  if (!c->have_camera) return fail(c, RT_E_INVALID, fn + ": camera not set");
+  if (out.motion && !c->motion_on)
+    return fail(c, RT_E_INVALID, fn + ": motion plane asked for, but motion history is off (rt_set_motion_history)");
+  if (out.motion && !c->ver[c->cur].motion)
+    return fail(c, RT_E_INVALID, fn + ": the current TLAS was built before motion history was switched on");
   // the kernels index a plane's entries with 32 bits, as the frame kernels index their pixels
-  if ((uint64_t)nrows * W >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, "rt_dispatch_gbuffer: more than 2^32 pixels");
+  if ((uint64_t)nrows * W >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, fn + ": more than 2^32 pixels");
   (void)hipSetDevice(c->device);
   hipStream_t s = pick_stream(c, stream);
   rt::SceneView sv = scene_view(c);
   if (sv.stack_cap > rt::kMaxTraversalStack)
-    return fail(c, RT_E_UNSUPPORTED, "rt_dispatch_gbuffer: BVH too deep for the traversal stack");
-  rt::GbufParams gb;
+    return fail(c, RT_E_UNSUPPORTED, fn + ": BVH too deep for the traversal stack");
+  rt::GbufMotionParams mp;
+  rt::GbufParams& gb = mp.gb;
   rt::frame_cam(c->cam_cb, gb.cam);
   gb.width = W;
   gb.nrows = nrows;
   gb.fwidth = (float)W;  // exact: W, H < 2^24
   gb.fheight = (float)H;
-  gb.hits = out->hits;
-  gb.uv = out->uv;
-  gb.normal = out->normal;
-  gb.object = out->object;
+  gb.hits = out.hits;
+  gb.uv = out.uv;
+  gb.normal = out.normal;
+  gb.object = out.object;
+  motion_cams(c->cam_cb, prev_cb, mp.cams);
+  mp.motion = out.motion;
+  mp.recs = c->ver[c->cur].motion;
   rt_status st;
   const uint32_t* d_rows = nullptr;
   ScratchSlot* rows_slot = nullptr;
@@ -1856,16 +1944,49 @@ rt_status rt_dispatch_gbuffer(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t
     const size_t lanes = (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256;
     if ((st = ensure_overflow(c, sv, lanes, s, &ovf_slot)) != RT_OK) return st;
   }
-  HIPCHK(c, order_after_tlas(c, s), "rt_dispatch_gbuffer: order after the TLAS build");
-  const hipError_t e = rt::launch_trace_gbuffer(sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, s);
+  HIPCHK(c, order_after_tlas(c, s), (fn + ": order after the TLAS build").c_str());
+  const hipError_t e = motion_kernels
+                           ? rt::launch_trace_gbuffer_motion(sv, mp, d_rows, c->d_stats, c->stats_on, c->schedule, s)
+                           : rt::launch_trace_gbuffer(sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, s);
   if (e != hipSuccess) return hip_fail(c, e, "G-buffer launch");
-  HIPCHK(c, note_reader(c->ver[c->cur], s), "rt_dispatch_gbuffer: record use");
+  HIPCHK(c, note_reader(c->ver[c->cur], s), (fn + ": record use").c_str());
   if (ovf_slot) HIPCHK(c, slot_mark_use(*ovf_slot, s), "overflow stack: record use");
   if (rows_slot) HIPCHK(c, slot_mark_use(*rows_slot, s), "rows: record use");
   if (c->stats_on) {
     c->dispatches += 1;
     c->pixels += (uint64_t)W * nrows;
   }
+  return RT_OK;
+}
+
+rt_status rt_dispatch_gbuffer(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                              const rt_gbuffer* out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  if (!out) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer: null output structure");
+  const rt_gbuffer_motion planes = {out->hits, out->uv, out->normal, out->object, nullptr};
+  return gbuffer_dispatch(c, "rt_dispatch_gbuffer", false, W, H, rows, nrows, planes, nullptr, stream);
+}
+
+rt_status rt_dispatch_gbuffer_motion(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                     const rt_gbuffer_motion* out, const float prev_cb[64], void* stream) {
+  if (!c) return RT_E_INVALID;
+  if (!out) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer_motion: null output structure");
+  return gbuffer_dispatch(c, "rt_dispatch_gbuffer_motion", true, W, H, rows, nrows, *out, prev_cb, stream);
+}
+
+rt_status rt_set_motion_history(rt_ctx_t c, int enable) {
+  if (!c) return RT_E_INVALID;
+  const bool on = enable != 0;
+  if (on == c->motion_on) return RT_OK;
+  c->motion_on = on;
+  // Either way the versions built so far stop serving motion launches and stop being predecessors (a version's
+  // records describe an unbroken history only), the next build with history on lays the versions out anew, and
+  // snapshots taken under the old setting are forgotten. Launches in flight keep their arguments: nothing is freed.
+  for (TlasVersion& v : c->ver) {
+    v.motion = nullptr;
+    v.motion_cap = 0;
+  }
+  for (DeviceBlas& b : c->blas) b.prev_taken = false;
   return RT_OK;
 }
 
@@ -2042,6 +2163,56 @@ rt_status rt_host_shading_normals(const void* vtx, uint32_t vcount, uint32_t str
     o[1] = nr.y;
     o[2] = nr.z;
     o[3] = 0.0f;
+  }
+  return RT_OK;
+}
+
+// Host services: the motion plane's two stages (rt_device.hpp: motion_object_points, motion_entry — the functions the
+// motion kernels call) on host arrays. Here for rt_host_shading_normals' reason. No context, no GPU call.
+rt_status rt_host_motion_project(const float* pts_cur, const float* pts_prev, uint32_t n, const float cb[64],
+                                 const float prev_cb[64], uint32_t W, uint32_t H, float* out) {
+  if (!cb || W == 0 || H == 0 || (n && (!pts_cur || !pts_prev || !out))) return RT_E_INVALID;
+  rt::MotionCams cams;
+  motion_cams(cb, prev_cb, cams);
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* a = pts_cur + 3 * (size_t)i;
+    const float* b = pts_prev + 3 * (size_t)i;
+    rt::motion_entry(cams, rt::v3(a[0], a[1], a[2]), rt::v3(b[0], b[1], b[2]), (float)W, (float)H, out + 4 * (size_t)i);
+  }
+  return RT_OK;
+}
+
+rt_status rt_host_motion_vectors(const void* vtx, const void* prev_vtx, uint32_t vcount, uint32_t stride,
+                                 const uint32_t* idx, uint32_t icount, const float* object_to_world,
+                                 const float* prev_object_to_world, const float cb[64], const float prev_cb[64],
+                                 uint32_t W, uint32_t H, const uint32_t* prims, const float* uv, uint32_t n,
+                                 float* out) {
+  if (!vtx || vcount == 0 || stride < 12 || (stride % 4) || !cb || W == 0 || H == 0 || (n && (!prims || !uv || !out)))
+    return RT_E_INVALID;
+  uint32_t ntri;
+  if (idx) {
+    if (icount == 0 || icount % 3) return RT_E_INVALID;
+    for (uint32_t i = 0; i < icount; ++i)
+      if (idx[i] >= vcount) return RT_E_INVALID;
+    ntri = icount / 3;
+  } else {
+    if (vcount % 3) return RT_E_INVALID;
+    ntri = vcount / 3;
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (prims[i] >= ntri) return RT_E_INVALID;
+  const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  const float* m = object_to_world ? object_to_world : I;
+  const float* pm = prev_object_to_world ? prev_object_to_world : m;
+  rt::MotionCams cams;
+  motion_cams(cb, prev_cb, cams);
+  const float* v = (const float*)vtx;
+  const float* pv = prev_vtx ? (const float*)prev_vtx : v;
+  const uint32_t vstride = stride / 4;
+  for (uint32_t i = 0; i < n; ++i) {
+    rt::V3 oc, op;
+    rt::motion_object_points(v, pv, vstride, idx, prims[i], uv[2 * (size_t)i], uv[2 * (size_t)i + 1], oc, op);
+    rt::motion_entry(cams, rt::xform_point(m, oc), rt::xform_point(pm, op), (float)W, (float)H, out + 4 * (size_t)i);
   }
   return RT_OK;
 }

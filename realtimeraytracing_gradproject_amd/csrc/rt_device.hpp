@@ -240,6 +240,33 @@ struct GbufParams {
   uint32_t* object;       // 2 words: instance index, hit group
 };
 
+// Motion history (rt_set_motion_history) of one instance of a TLAS version, parallel to its InstanceRec: the
+// instance's object-to-world transform in the list the version replaced and its BLAS's vertex positions before
+// the first refit since (both the current ones where there is no predecessor: no motion). prev_vtx has the
+// BLAS's vertex layout, so it is indexed exactly like InstanceRec::vtx. 64 B: four 16-B loads per hit.
+struct alignas(16) MotionRec {
+  float prev_o2w[12];
+  const float* prev_vtx;
+  uint64_t pad_;
+};
+static_assert(sizeof(MotionRec) == 64, "MotionRec must be 64 B");
+
+// The forward camera chain of a motion launch: view and projection (XMMATRIX memory order, cb[0..15] and
+// cb[16..31] of rt_set_camera's layout) of the current and of the previous camera buffer.
+struct MotionCams {
+  float view[16], proj[16];
+  float prev_view[16], prev_proj[16];
+};
+
+// rt_dispatch_gbuffer_motion: the G-buffer launch's parameters unchanged, the two cameras' forward matrices, the
+// fifth plane (4 floats per pixel: mx, my, w_prev, w_cur; null: not written) and the TLAS version's MotionRec array.
+struct GbufMotionParams {
+  GbufParams gb;
+  MotionCams cams;
+  float* motion;
+  const MotionRec* recs;
+};
+
 // Tile-balance split codes (FrameParams::plan): parts per tile. The costliest quadrant of the costliest C4 tiles
 // takes 0.55 of the whole packet's fetches, the costliest 2 x 2 cell 0.35 (tools/split_study.py): the kernel's
 // estimate of a whole tile from one part's time, and the plan's estimate of a part from the whole.
@@ -735,6 +762,54 @@ RT_HD V3 face_world_normal(FP vtx, uint32_t vstride, IP idx, const float* nrm, u
   const V3 p2 = ldv3(vtx + (size_t)i2 * vstride);
   V3 n = normalize_x<EX>(cross(sub(p1, p0), sub(p2, p0)));
   return mat3_mul(nrm, n);
+}
+
+// ------------------------------------------------------------------------------------------
+// Motion vectors (rt_dispatch_gbuffer_motion), in two stages over plain data, called by the motion
+// kernels on the scene's device arrays and by rt_host_motion_vectors / rt_host_motion_project on host arrays.
+// ------------------------------------------------------------------------------------------
+
+// Stage 1, the object point of a hit: P = (p1 u + p2 v) + p0 ((1 - u) - v), the vertex order and weights of
+// interpolated_world_normal, on the current and on the previous positions (two arrays of one layout, one index list;
+// the same array twice gives the same point twice, bit for bit).
+template <typename FP, typename IP>
+RT_HD void motion_object_points(FP vtx, FP prev_vtx, uint32_t vstride, IP idx, uint32_t prim, float u, float v,
+                                V3& cur, V3& prev) {
+  uint32_t i0, i1, i2;
+  tri_vertex_ids(idx, prim, i0, i1, i2);
+  const float bz = (1.0f - u) - v;
+  cur = add(add(muls(ldv3(vtx + (size_t)i1 * vstride), u), muls(ldv3(vtx + (size_t)i2 * vstride), v)),
+            muls(ldv3(vtx + (size_t)i0 * vstride), bz));
+  prev = add(add(muls(ldv3(prev_vtx + (size_t)i1 * vstride), u), muls(ldv3(prev_vtx + (size_t)i2 * vstride), v)),
+             muls(ldv3(prev_vtx + (size_t)i0 * vstride), bz));
+}
+
+// Stage 2a, a world point on the screen: clip = mul(projection, mul(view, (P, 1))), the forward chain of RayGen's
+// inverse one; x = (clip.x / clip.w + 1) 0.5 W, y = (1 - clip.y / clip.w) 0.5 H in pixels (+x right, +y down, pixel
+// centres at .5); w = clip.w, the view depth. IEEE quotients (the compiler's correctly rounded division).
+RT_HD void motion_screen(const float* view, const float* proj, V3 P, float fwidth, float fheight, float& x, float& y,
+                         float& w) {
+  const float p4[4] = {P.x, P.y, P.z, 1.0f};
+  float pv[4], clip[4];
+  hlsl_mul4(view, p4, pv);
+  hlsl_mul4(proj, pv, clip);
+  w = clip[3];
+  x = ((clip[0] / w + 1.0f) * 0.5f) * fwidth;
+  y = ((1.0f - clip[1] / w) * 0.5f) * fheight;
+}
+
+// Stage 2b, one pixel's motion entry (mx, my, w_prev, w_cur) from the world point now and then. Both points go
+// through motion_screen, so unchanged inputs give exactly 0, 0 and w_prev == w_cur. A point behind the previous
+// camera (w_prev <= 0) has no previous pixel: mx = my = +inf.
+RT_HD void motion_entry(const MotionCams& cams, V3 cur, V3 prev, float fwidth, float fheight, float out[4]) {
+  float xc, yc, wc, xp, yp, wp;
+  motion_screen(cams.view, cams.proj, cur, fwidth, fheight, xc, yc, wc);
+  motion_screen(cams.prev_view, cams.prev_proj, prev, fwidth, fheight, xp, yp, wp);
+  const bool behind = wp <= 0.0f;
+  out[0] = behind ? __builtin_inff() : xp - xc;
+  out[1] = behind ? __builtin_inff() : yp - yc;
+  out[2] = wp;
+  out[3] = wc;
 }
 
 }  // namespace rt

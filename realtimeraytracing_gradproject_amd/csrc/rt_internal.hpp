@@ -177,6 +177,9 @@ hipError_t launch_trace_rays(const SceneView& scene, const float* rays, uint32_t
 bool gbuffer_packet(const SceneView& scene, int schedule);
 hipError_t launch_trace_gbuffer(const SceneView& scene, const GbufParams& gb, const uint32_t* d_rows,
                                 unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
+// The same pass with the motion plane (rt_dispatch_gbuffer_motion): the motion kernels on the same grids.
+hipError_t launch_trace_gbuffer_motion(const SceneView& scene, const GbufMotionParams& mp, const uint32_t* d_rows,
+                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
 
 // rank_stride_rows: rows from one rank's block of `gathered` to the next (0: rows_per_rank, one frame per block;
 // a batched gather holds several frames per rank block and passes their total)

@@ -1804,6 +1804,112 @@ __global__ __launch_bounds__(kBlock) void k_trace_gbuffer(SceneView sc, GbufPara
   if (STATS) flush_stats<false>(cnt, stats);
 }
 
+// ------------------------------------------------------------------------------------------
+// G-buffer pass with motion vectors (rt_dispatch_gbuffer_motion): the G-buffer kernels' launch shapes,
+// ray and four planes (gbuffer_ray, gbuffer_store: the same calls, so the same bits) and a fifth plane, `motion`.
+// ------------------------------------------------------------------------------------------
+
+// One pixel's motion entry (mx, my, w_prev, w_cur), entry o of the plane when the launch asked for it (one uniform
+// branch on the kernel's pointer argument, one 16-B store per lane: an 8-pixel tile row is a full 128-B line). A hit:
+// the object point of (prim, u, v) on the instance's current and previous positions (per-lane gathers: 3 indices,
+// 3 + 3 positions), each through its own object-to-world transform (the InstanceRec's, the MotionRec's: 16-B
+// loads). A miss: the static world point O + D tmax. Then rt_device.hpp's projection stage, shared with the host.
+__device__ __forceinline__ void gbuffer_motion_store(const SceneView& sc, const GbufMotionParams& mp, uint32_t o, bool f,
+                                                     const HitRec& hit, V3 O, V3 D) {
+  if (!mp.motion) return;
+  V3 cur, prev;
+  if (f) {
+    const RT_GLOBAL InstanceRec* ir = gp(sc.inst) + hit.inst;
+    const RT_GLOBAL MotionRec* mr = gp(mp.recs) + hit.inst;
+    float m[12], pm[12];
+    for (int k = 0; k < 12; ++k) m[k] = ir->o2w[k];
+    for (int k = 0; k < 12; ++k) pm[k] = mr->prev_o2w[k];
+    V3 oc, op;
+    motion_object_points(gp(ir->vtx), gp(mr->prev_vtx), 6u, gp(ir->idx), hit.prim, hit.u, hit.v, oc, op);
+    cur = xform_point(m, oc);
+    prev = xform_point(pm, op);
+  } else {
+    cur = prev = add(O, muls(D, 100000.0f));
+  }
+  float e[4];
+  motion_entry(mp.cams, cur, prev, mp.gb.fwidth, mp.gb.fheight, e);
+  reinterpret_cast<float4*>(mp.motion)[o] = make_float4(e[0], e[1], e[2], e[3]);
+}
+
+// The packet kernel's SGPR budget: the compiler's own (86 SGPRs, no spills: 7 waves per SIMD), or with
+// RT_MOTION_PLAIN_SGPRS=1 the plain kernels' cap (8 waves per SIMD). Under the cap the 128 camera floats crowd the
+// walk: 8 SGPR spills in <false, 0>, and <false, 1> / <true, 0> spill to scratch, which this path does not allow, so
+// the cap is off; DESIGN §3.8 has the A/B of the two builds.
+#ifndef RT_MOTION_PLAIN_SGPRS
+#define RT_MOTION_PLAIN_SGPRS 0
+#endif
+#if RT_MOTION_PLAIN_SGPRS
+#define RT_MOTION_SGPR_ATTR RT_PLAIN_SGPR_ATTR
+#else
+#define RT_MOTION_SGPR_ATTR
+#endif
+
+// k_trace_gbuffer_packet with the fifth plane: the same tile layout, ray and walk.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_MOTION_SGPR_ATTR
+void k_trace_gbuffer_motion_packet(SceneView sc, GbufMotionParams mp, const uint32_t* __restrict__ rows,
+                                   unsigned long long* __restrict__ stats) {
+#if RT_LDS_TOP
+  {
+    const RT_GLOBAL f4v* src = (const RT_GLOBAL f4v*)((const RT_GLOBAL char*)sc.pool_nodes + ((uint32_t)sc.lds_root << 7));
+    const uint32_t nrow = (uint32_t)sc.lds_n * 8u;
+    for (uint32_t i = threadIdx.x; i < nrow; i += packet_block(1)) g_top[i] = src[i];
+    __syncthreads();
+  }
+#endif
+  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
+  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
+  const bool inimg = x < mp.gb.width && orow < mp.gb.nrows;
+  uint32_t py = 0;
+  if (inimg) py = rows ? rows[orow] : orow;
+  V3 O, D;
+  gbuffer_ray(mp.gb, x, py, O, D);
+  Counters cnt;
+  if (STATS && inimg) ++cnt.primary;
+  HitRec hit;
+  bool found;
+  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  if (inimg) {
+    const uint32_t o = orow * mp.gb.width + x;  // < 2^32 pixels (rt_api.cpp)
+    gbuffer_store(sc, mp.gb, o, found, hit);
+    gbuffer_motion_store(sc, mp, o, found, hit, O, D);
+  }
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// k_trace_gbuffer with the fifth plane: the per-lane twin.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_gbuffer_motion(SceneView sc, GbufMotionParams mp,
+                                                                 const uint32_t* __restrict__ rows,
+                                                                 unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  Counters cnt;
+  if (px < mp.gb.width && orow < mp.gb.nrows) {
+    const uint32_t py = rows ? rows[orow] : orow;
+    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+    V3 O, D;
+    gbuffer_ray(mp.gb, px, py, O, D);
+    HitRec hit;
+    if (STATS) ++cnt.primary;
+    const bool f = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
+    const uint32_t o = orow * mp.gb.width + px;
+    gbuffer_store(sc, mp.gb, o, f, hit);
+    gbuffer_motion_store(sc, mp, o, f, hit, O, D);
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
 // Un-interleaves the gathered strips (rank-major blocks; rank k holds strips s % nranks == k) into the RGBA8 frame.
 // in_bpp 3: the strips are RGB8 and the constant alpha 255 is restored here (RayGen.hlsl:42 writes float4(c, 1)).
 __global__ void k_assemble(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
@@ -2457,32 +2563,48 @@ bool gbuffer_packet(const SceneView& sc, int schedule) {
   return schedule == RT_SCHED_PACKET && sc.packet_cap < kPacketStack;  // packet_geometry's rule
 }
 
-hipError_t launch_trace_gbuffer(const SceneView& sc, const GbufParams& gb, const uint32_t* d_rows,
-                                unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
-  // counters and the triangle test (sc.tri_test: the watertight instantiations on the vertex-form pool) are
-  // compile-time choices, as for the frame kernels
-#define RT_LAUNCH_GBUF(K, GRID, BLOCK, LDS)                                                                  \
+// counters and the triangle test (sc.tri_test: the watertight instantiations on the vertex-form pool) are
+// compile-time choices, as for the frame kernels; P: the launch's parameter structure
+#define RT_LAUNCH_GBUF(K, GRID, BLOCK, LDS, P)                                                               \
   do {                                                                                                       \
     if (sc.tri_test) {                                                                                       \
-      if (stats) hipLaunchKernelGGL((K<true, 1>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);              \
-      else hipLaunchKernelGGL((K<false, 1>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);                   \
+      if (stats) hipLaunchKernelGGL((K<true, 1>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);               \
+      else hipLaunchKernelGGL((K<false, 1>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);                    \
     } else {                                                                                                 \
-      if (stats) hipLaunchKernelGGL((K<true, 0>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);              \
-      else hipLaunchKernelGGL((K<false, 0>), GRID, BLOCK, LDS, s, sc, gb, d_rows, d_stats);                   \
+      if (stats) hipLaunchKernelGGL((K<true, 0>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);               \
+      else hipLaunchKernelGGL((K<false, 0>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);                    \
     }                                                                                                        \
   } while (0)
+
+hipError_t launch_trace_gbuffer(const SceneView& sc, const GbufParams& gb, const uint32_t* d_rows,
+                                unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
   if (gbuffer_packet(sc, schedule)) {
     const uint32_t tw = 8u * (uint32_t)packet_wx(1), th = 8u * (uint32_t)packet_wy(1);
     const dim3 grid((gb.width + tw - 1) / tw, (gb.nrows + th - 1) / th);
-    RT_LAUNCH_GBUF(k_trace_gbuffer_packet, grid, dim3(packet_block(1)), 0);
+    RT_LAUNCH_GBUF(k_trace_gbuffer_packet, grid, dim3(packet_block(1)), 0, gb);
   } else {
     const dim3 grid((gb.width + 15) / 16, (gb.nrows + 15) / 16);
     const size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
-    RT_LAUNCH_GBUF(k_trace_gbuffer, grid, dim3(kBlock), lds);
+    RT_LAUNCH_GBUF(k_trace_gbuffer, grid, dim3(kBlock), lds, gb);
   }
-#undef RT_LAUNCH_GBUF
   return hipGetLastError();
 }
+
+hipError_t launch_trace_gbuffer_motion(const SceneView& sc, const GbufMotionParams& mp, const uint32_t* d_rows,
+                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
+  const GbufParams& gb = mp.gb;  // the G-buffer launch's grids
+  if (gbuffer_packet(sc, schedule)) {
+    const uint32_t tw = 8u * (uint32_t)packet_wx(1), th = 8u * (uint32_t)packet_wy(1);
+    const dim3 grid((gb.width + tw - 1) / tw, (gb.nrows + th - 1) / th);
+    RT_LAUNCH_GBUF(k_trace_gbuffer_motion_packet, grid, dim3(packet_block(1)), 0, mp);
+  } else {
+    const dim3 grid((gb.width + 15) / 16, (gb.nrows + 15) / 16);
+    const size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
+    RT_LAUNCH_GBUF(k_trace_gbuffer_motion, grid, dim3(kBlock), lds, mp);
+  }
+  return hipGetLastError();
+}
+#undef RT_LAUNCH_GBUF
 
 hipError_t launch_assemble_strips(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
                                   const void* gathered, void* out, hipStream_t s, uint32_t rank_stride_rows,
