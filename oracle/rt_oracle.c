@@ -1723,7 +1723,7 @@ int oracle_render_split(const oracle_scene* s, const float cb[64], const oracle_
     jobs[t].rgba8 = rgba8; jobs[t].rgba32f = rgba32f;
   }
   /* the device runs wave packets unless asked for per-lane rays or the trees are too deep for
-   * its one-VGPR stack (rt_trace.hip launch_mode) */
+   * its one-VGPR stack (rt_trace.hip packet_geometry) */
   uint32_t maxd = 0;
   for (int q = 0; q < s->nblas; ++q) if (s->blas[q].depth > maxd) maxd = s->blas[q].depth;
   const int packet = !brute && schedule == 0 && (s->tlas_max_stack + maxd) < OPK;

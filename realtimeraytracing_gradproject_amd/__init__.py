@@ -878,13 +878,29 @@ class Context:
         self._check(self._lib.rt_stats_reset(self._h), "rt_stats_reset")
 
     # launches ---------------------------------------------------------------------------------
+    @staticmethod
+    def _rows_arg(rows, height: int):
+        """A launch's rows argument as (pointer, count, the array that owns the pointer: kept until the call returns);
+        None: every row of the frame."""
+        if rows is None:
+            return None, height, None
+        r = np.ascontiguousarray(rows, dtype=np.uint32)
+        return r.ctypes.data_as(_P), r.size, r
+
+    @staticmethod
+    def _set_planes(g, method: str, entries: int, planes):
+        """Fills the output structure g from planes, (name, tensor or address or None, 32-bit words per entry) each: a
+        tensor must hold exactly `entries` entries."""
+        for name, t, words in planes:
+            if t is not None and not isinstance(t, int):
+                if t.element_size() != 4 or t.numel() != entries * words or not t.is_contiguous():
+                    raise ValueError(f"{method}: {name} must be a contiguous tensor of {entries * words} "
+                                     f"32-bit elements, got {t.numel()} of {t.element_size()} bytes")
+            setattr(g, name, _ptr(t))
+
     def dispatch(self, width: int, height: int, rgba8, rgba32f=None, rows: Optional[np.ndarray] = None,
                  stream: Optional[int] = None):
-        if rows is not None:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-            rp, nr = r.ctypes.data_as(_P), r.size
-        else:
-            rp, nr = None, height
+        rp, nr, _keep = self._rows_arg(rows, height)
         self._check(self._lib.rt_dispatch_rays(self._h, width, height, rp, nr, _ptr(rgba8), _ptr(rgba32f), stream),
                     "rt_dispatch_rays")
 
@@ -905,18 +921,10 @@ class Context:
         order of dispatch(): hits (4 x 32-bit words per pixel: t, instance id, primitive, hit flag), uv (2 floats),
         normal (4 floats, w = 0), object (2 words: instance index, hit group). Device tensors (or raw addresses); a
         plane left None is not written; at least one must be given."""
-        if rows is not None:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-            rp, nr = r.ctypes.data_as(_P), r.size
-        else:
-            rp, nr = None, height
+        rp, nr, _keep = self._rows_arg(rows, height)
         g = rt_gbuffer()
-        for name, t, words in (("hits", hits, 4), ("uv", uv, 2), ("normal", normal, 4), ("object", object, 2)):
-            if t is not None and not isinstance(t, int):
-                if t.element_size() != 4 or t.numel() != nr * width * words or not t.is_contiguous():
-                    raise ValueError(f"dispatch_gbuffer: {name} must be a contiguous tensor of {nr * width * words} "
-                                     f"32-bit elements, got {t.numel()} of {t.element_size()} bytes")
-            setattr(g, name, _ptr(t))
+        self._set_planes(g, "dispatch_gbuffer", nr * width,
+                         (("hits", hits, 4), ("uv", uv, 2), ("normal", normal, 4), ("object", object, 2)))
         self._check(self._lib.rt_dispatch_gbuffer(self._h, width, height, rp, nr, ctypes.byref(g), stream),
                     "rt_dispatch_gbuffer")
 
@@ -932,19 +940,11 @@ class Context:
         w_cur — the pixel's surface point was at (x + 0.5 + mx, y + 0.5 + my) in the previous frame, +inf when it was
         behind the previous camera; the two view depths). prev_camera: the previous frame's 64-float camera buffer
         (None: the current camera). motion needs set_motion_history(True) before the TLAS was built."""
-        if rows is not None:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-            rp, nr = r.ctypes.data_as(_P), r.size
-        else:
-            rp, nr = None, height
+        rp, nr, _keep = self._rows_arg(rows, height)
         g = rt_gbuffer_motion()
-        for name, t, words in (("hits", hits, 4), ("uv", uv, 2), ("normal", normal, 4), ("object", object, 2),
-                               ("motion", motion, 4)):
-            if t is not None and not isinstance(t, int):
-                if t.element_size() != 4 or t.numel() != nr * width * words or not t.is_contiguous():
-                    raise ValueError(f"dispatch_gbuffer_motion: {name} must be a contiguous tensor of "
-                                     f"{nr * width * words} 32-bit elements, got {t.numel()} of {t.element_size()} bytes")
-            setattr(g, name, _ptr(t))
+        self._set_planes(g, "dispatch_gbuffer_motion", nr * width,
+                         (("hits", hits, 4), ("uv", uv, 2), ("normal", normal, 4), ("object", object, 2),
+                          ("motion", motion, 4)))
         pcb = None if prev_camera is None else _f32(prev_camera, 64)
         self._check(self._lib.rt_dispatch_gbuffer_motion(self._h, width, height, rp, nr, ctypes.byref(g),
                                                          None if pcb is None else _fptr(pcb), stream),

@@ -1310,6 +1310,63 @@ static rt_status ensure_rows(rt_ctx* c, const uint32_t* rows, uint32_t nrows, hi
   return RT_OK;
 }
 
+// Whether the scene can be traced: a TLAS, built after the last BLAS rebuild / refit. fn: the entry point's name in
+// the message.
+static rt_status check_scene_ready(rt_ctx* c, const char* fn) {
+  const char* why = (c->cur < 0 && !c->tlas_stale) ? ": no TLAS built"
+                    : c->tlas_stale ? ": scene stale (BLAS rebuilt, or the last rt_tlas_build failed)"
+                    : c->tlas_refit ? ": BLAS refitted, rt_tlas_build (an update will do) must follow"
+                                    : nullptr;
+  return why ? fail(c, RT_E_INVALID, std::string(fn) + why) : RT_OK;
+}
+
+// A dispatch's row list: rows null means every row of the frame (*nrows becomes H).
+static rt_status check_rows(rt_ctx* c, const char* fn, uint32_t H, const uint32_t* rows, uint32_t* nrows) {
+  if (!rows) *nrows = H;
+  if (*nrows == 0 || *nrows > H) return fail(c, RT_E_INVALID, std::string(fn) + ": bad row count");
+  if (rows)
+    for (uint32_t r = 0; r < *nrows; ++r)
+      if (rows[r] >= H) return fail(c, RT_E_INVALID, std::string(fn) + ": row index out of range");
+  return RT_OK;
+}
+
+// One trace launch on stream s, from the scene view to the record of what it read. The take_* calls collect the
+// scratch slots the kernel reads; finish(), given the launcher's result, notes s as a reader of the current TLAS
+// version and marks every slot taken, so a launch that went through finish() cannot have a buffer recycled under it.
+// fn: the entry point's name in the messages.
+struct TraceLaunch {
+  rt_ctx* c;
+  const char* fn;
+  hipStream_t s;
+  rt::SceneView sv = {};
+  ScratchSlot *rows = nullptr, *ovf = nullptr, *plan = nullptr;
+
+  rt_status open() {
+    sv = scene_view(c);
+    if (sv.stack_cap > rt::kMaxTraversalStack)
+      return fail(c, RT_E_UNSUPPORTED, std::string(fn) + ": BVH too deep for the traversal stack");
+    return RT_OK;
+  }
+  rt_status take_rows(const uint32_t* host_rows, uint32_t nrows, const uint32_t** d_rows, uint64_t* gen) {
+    return host_rows ? ensure_rows(c, host_rows, nrows, s, &rows, d_rows, gen) : RT_OK;
+  }
+  // the per-lane kernels' HBM overflow stack; then the launch waits for the TLAS build (the last step before it)
+  rt_status take_overflow_and_order(size_t lanes) {
+    const rt_status st = lanes ? ensure_overflow(c, sv, lanes, s, &ovf) : RT_OK;
+    if (st != RT_OK) return st;
+    HIPCHK(c, order_after_tlas(c, s), (std::string(fn) + ": order after the TLAS build").c_str());
+    return RT_OK;
+  }
+  rt_status finish(hipError_t launched, const char* what) {
+    if (launched != hipSuccess) return hip_fail(c, launched, what);
+    HIPCHK(c, note_reader(c->ver[c->cur], s), (std::string(fn) + ": record use").c_str());
+    if (ovf) HIPCHK(c, slot_mark_use(*ovf, s), "overflow stack: record use");
+    if (plan) HIPCHK(c, slot_mark_use(*plan, s), "tile plan: record use");
+    if (rows) HIPCHK(c, slot_mark_use(*rows, s), "rows: record use");
+    return RT_OK;
+  }
+};
+
 }  // extern "C"
 
 namespace rt {
@@ -1349,11 +1406,8 @@ hipError_t ctx_forget_stream(rt_ctx* c, hipStream_t s) {
 void* ctx_stream(rt_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 rt_status check_dispatch(rt_ctx* c, uint32_t W, uint32_t H, const void* rgba8, bool cameras_given) {
-  if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, "rt_dispatch_rays: no TLAS built");
-  if (c->tlas_stale)
-    return fail(c, RT_E_INVALID, "rt_dispatch_rays: scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
-  if (c->tlas_refit)
-    return fail(c, RT_E_INVALID, "rt_dispatch_rays: BLAS refitted, rt_tlas_build (an update will do) must follow");
+  const rt_status st = check_scene_ready(c, "rt_dispatch_rays");
+  if (st != RT_OK) return st;
   if (!c->have_shading) return fail(c, RT_E_INVALID, "rt_dispatch_rays: shading not set");
   if (!c->have_camera && !cameras_given) return fail(c, RT_E_INVALID, "rt_dispatch_rays: camera not set");
   if (W == 0 || H == 0 || !rgba8) return fail(c, RT_E_INVALID, "rt_dispatch_rays: bad size or output");
@@ -1541,53 +1595,21 @@ void frame_cam(const float cb[64], FrameCam& cam) {
   rt::hlsl_mul4(cb + 32, zero_one, cam.origin);
 }
 
-// The frame launch behind rt_dispatch_rays and rt_render_strips (d_rows: a device row list or null; the
-// caller validated the arguments with check_dispatch and keeps d_rows alive until the launch completed).
-// nframes frames in one launch (the grid's z): frame z with camera buffer cams[64 z ..] (null: the context's
-// camera for every frame) into out + z * frame_stride bytes (0: nrows * W * out_bpp, compact); out_bpp 4 = RGBA8,
-// 3 = RGB8 (strips).
-rt_status dispatch_frame(rt_ctx* c, uint32_t W, uint32_t H, const uint32_t* d_rows, uint32_t nrows, void* rgba8,
-                         float* rgba32f, hipStream_t s, uint32_t out_bpp, uint32_t nframes, const float* cams,
-                         uint64_t frame_stride, uint64_t rows_gen) {
-  if (nframes < 1 || nframes > (uint32_t)rt::kMaxLaunchFrames || (out_bpp != 3 && out_bpp != 4) ||
-      (nframes > 1 && rgba32f))
-    return fail(c, RT_E_INVALID, "dispatch: 1..4 frames per launch, RGBA8 or RGB8, float output for one frame only");
-  const uint64_t frame_bytes = frame_stride ? frame_stride : (uint64_t)nrows * W * out_bpp;
-  if (frame_bytes * nframes >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, "dispatch: frame exceeds 4 GB");
-  c->fp.width = W;
-  c->fp.height = H;
-  c->fp.fwidth = (float)W;  // exact: W, H < 2^24
-  c->fp.fheight = (float)H;
-  c->fp.nrows = nrows;
-  c->fp.tile_rows = c->tile_rows;
-  c->fp.out_bpp = out_bpp;
-  c->fp.nframes = nframes;
-  c->fp.frame_bytes = (uint32_t)frame_bytes;
-  for (uint32_t z = 0; z < nframes; ++z) frame_cam(cams ? cams + 64 * z : c->cam_cb, c->fp.cam[z]);
-  rt::SceneView sv = scene_view(c);
-  if (sv.stack_cap > rt::kMaxTraversalStack)
-    return fail(c, RT_E_UNSUPPORTED, "rt_dispatch_rays: BVH too deep for the traversal stack");
-  ScratchSlot* ovf_slot = nullptr;
-  {
-    const size_t lanes = (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256 * nframes;
-    rt_status st = ensure_overflow(c, sv, lanes, s, &ovf_slot);
-    if (st != RT_OK) return st;
-  }
-  HIPCHK(c, order_after_tlas(c, s), "rt_dispatch_rays: order after the TLAS build");
-  // tile balance (packet schedule): the per-tile wave times of this shape, and a work list when it pays
-  const rt::PacketGeometry g = rt::packet_geometry(sv, c->fp, c->schedule);
+// The tile balance of a frame launch (packet schedule): the per-tile wave times of this shape, and a work list when
+// it pays. Sets fp.plan / fp.cost for the launch (both null: the plain grid, nothing recorded), *plan_items to the
+// list's budget of waves, and *plan_slot_out to the ring slot of a forced layout's list (the launch reads it).
+static rt_status balance_frame(rt_ctx* c, const rt::SceneView& sv, const rt::PacketGeometry& g, uint32_t W,
+                               uint32_t nrows, const uint32_t* d_rows, uint32_t nframes, hipStream_t s,
+                               uint64_t rows_gen, uint32_t* plan_items, ScratchSlot** plan_slot_out) {
   c->fp.plan = nullptr;
   c->fp.cost = nullptr;
-  c->fp.grid_x = g.grid_x;
-  c->fp.waves_per_frame = g.waves_per_frame;
-  uint32_t plan_items = 0;
-  ScratchSlot* plan_slot = nullptr;
+  *plan_items = 0;
   const bool forced = c->balance >= 2;
   if (forced && (uint64_t)g.waves_per_frame * nframes > rt::kPlanMaxTiles)
     return fail(c, RT_E_UNSUPPORTED, "tile balance: forced layouts take at most 32768 waves per launch");
   // launches of more waves than the plan kernel holds run the plain grid (they are many rounds of the GPU's wave
   // slots deep: the slowest tile is a small part of them, C5's 518,400 waves)
-  // (a watertight launch always takes the plain grid: launch_trace_frame)
+  // (a watertight launch always takes the plain grid: select_frame_kernel, rt_trace.hip)
   if (c->balance && g.packet && g.plannable && (forced || !c->stats_on) && !sv.tri_test &&
       (uint64_t)g.waves_per_frame * nframes <= rt::kPlanMaxTiles) {
     const uint32_t ntiles = g.waves_per_frame * nframes;
@@ -1654,11 +1676,11 @@ rt_status dispatch_frame(rt_ctx* c, uint32_t W, uint32_t H, const uint32_t* d_ro
       a.extra_cap = c->bal_forced_cap ? c->bal_forced_cap : (most - 1u) * ntiles;
         a.stats = m->stats_dev;
         a.slots = plan_slots(c, sv);
-        plan_items = ntiles + a.extra_cap;
+        *plan_items = ntiles + a.extra_cap;
         bool hit;
-        plan_slot = ring_acquire(c->plans, s, nullptr, &hit, &be);
+        ScratchSlot* plan_slot = *plan_slot_out = ring_acquire(c->plans, s, nullptr, &hit, &be);
         if (be != hipSuccess) return hip_fail(c, be, "tile balance: order after in-flight launches");
-        HIPCHK(c, slot_reserve(*plan_slot, ((size_t)rt::plan_xwords(plan_items, a.wl) + 3u * ntiles + 1) * 4),
+        HIPCHK(c, slot_reserve(*plan_slot, ((size_t)rt::plan_xwords(*plan_items, a.wl) + 3u * ntiles + 1) * 4),
                "hipMalloc(tile plan)");
         a.plan = (uint32_t*)plan_slot->buf;
         HIPCHK(c, rt::launch_tile_plan(a, s), "tile plan launch");
@@ -1693,7 +1715,7 @@ rt_status dispatch_frame(rt_ctx* c, uint32_t W, uint32_t H, const uint32_t* d_ro
         if (use && m->cur >= 0) {
           if (std::find(m->readers.begin(), m->readers.end(), s) == m->readers.end()) m->readers.push_back(s);
           c->fp.plan = (const uint32_t*)m->list[m->cur].buf;
-          plan_items = m->cur_items;
+          *plan_items = m->cur_items;
         }
       }
       if (active) m->launches += 1;
@@ -1702,17 +1724,58 @@ rt_status dispatch_frame(rt_ctx* c, uint32_t W, uint32_t H, const uint32_t* d_ro
         m->streams.push_back(s);
     }
   }
-  hipError_t e = rt::launch_trace_frame(sv, c->fp, d_rows, rgba8, rgba32f, c->d_stats, c->stats_on,
-                                        c->schedule, plan_items, s);
-  if (e != hipSuccess) return hip_fail(c, e, "trace launch");
-  HIPCHK(c, note_reader(c->ver[c->cur], s), "rt_dispatch_rays: record use");
-  if (ovf_slot) HIPCHK(c, slot_mark_use(*ovf_slot, s), "overflow stack: record use");
-  if (plan_slot) HIPCHK(c, slot_mark_use(*plan_slot, s), "tile plan: record use");
+  return RT_OK;
+}
+
+// The frame launch behind rt_dispatch_rays, rt_dispatch_frames and rt_render_strips (d_rows: a device row list or
+// null; the caller validated the arguments with check_dispatch and keeps d_rows alive until the launch completed).
+// nframes frames in one launch (the grid's z): frame z with camera buffer cams[64 z ..] (null: the context's
+// camera for every frame) into out + z * frame_stride bytes (0: nrows * W * out_bpp, compact); out_bpp 4 = RGBA8,
+// 3 = RGB8 (strips). Prologue, balance, launch, epilogue.
+static rt_status launch_frame(TraceLaunch& L, uint32_t W, uint32_t H, const uint32_t* d_rows, uint32_t nrows,
+                              void* rgba8, float* rgba32f, uint32_t out_bpp, uint32_t nframes, const float* cams,
+                              uint64_t frame_stride, uint64_t rows_gen) {
+  rt_ctx* c = L.c;
+  if (nframes < 1 || nframes > (uint32_t)rt::kMaxLaunchFrames || (out_bpp != 3 && out_bpp != 4) ||
+      (nframes > 1 && rgba32f))
+    return fail(c, RT_E_INVALID, "dispatch: 1..4 frames per launch, RGBA8 or RGB8, float output for one frame only");
+  const uint64_t frame_bytes = frame_stride ? frame_stride : (uint64_t)nrows * W * out_bpp;
+  if (frame_bytes * nframes >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, "dispatch: frame exceeds 4 GB");
+  c->fp.width = W;
+  c->fp.height = H;
+  c->fp.fwidth = (float)W;  // exact: W, H < 2^24
+  c->fp.fheight = (float)H;
+  c->fp.nrows = nrows;
+  c->fp.tile_rows = c->tile_rows;
+  c->fp.out_bpp = out_bpp;
+  c->fp.nframes = nframes;
+  c->fp.frame_bytes = (uint32_t)frame_bytes;
+  for (uint32_t z = 0; z < nframes; ++z) frame_cam(cams ? cams + 64 * z : c->cam_cb, c->fp.cam[z]);
+  rt_status st = L.open();
+  if (st != RT_OK) return st;
+  if ((st = L.take_overflow_and_order((size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256 * nframes)) != RT_OK) return st;
+  const rt::PacketGeometry g = rt::packet_geometry(L.sv, c->fp, c->schedule);
+  c->fp.grid_x = g.grid_x;
+  c->fp.waves_per_frame = g.waves_per_frame;
+  uint32_t plan_items = 0;
+  if ((st = balance_frame(c, L.sv, g, W, nrows, d_rows, nframes, L.s, rows_gen, &plan_items, &L.plan)) != RT_OK)
+    return st;
+  st = L.finish(rt::launch_trace_frame(L.sv, c->fp, d_rows, rgba8, rgba32f, c->d_stats, c->stats_on, c->schedule,
+                                       plan_items, L.s),
+                "trace launch");
+  if (st != RT_OK) return st;
   if (c->stats_on) {
     c->dispatches += nframes;
     c->pixels += (uint64_t)W * nrows * nframes;
   }
   return RT_OK;
+}
+
+rt_status dispatch_frame(rt_ctx* c, uint32_t W, uint32_t H, const uint32_t* d_rows, uint32_t nrows, void* rgba8,
+                         float* rgba32f, hipStream_t s, uint32_t out_bpp, uint32_t nframes, const float* cams,
+                         uint64_t frame_stride, uint64_t rows_gen) {
+  TraceLaunch L{c, "rt_dispatch_rays", s};
+  return launch_frame(L, W, H, d_rows, nrows, rgba8, rgba32f, out_bpp, nframes, cams, frame_stride, rows_gen);
 }
 
 }  // namespace rt
@@ -1842,23 +1905,15 @@ rt_status rt_raster_draw(rt_ctx_t c, const rt_blas_t* draws, uint32_t ndraws, co
 rt_status rt_dispatch_rays(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
                            void* rgba8, float* rgba32f, void* stream) {
   if (!c) return RT_E_INVALID;
-  if (!rows) nrows = H;
-  if (nrows == 0 || nrows > H) return fail(c, RT_E_INVALID, "rt_dispatch_rays: bad row count");
-  if (rows)
-    for (uint32_t r = 0; r < nrows; ++r)
-      if (rows[r] >= H) return fail(c, RT_E_INVALID, "rt_dispatch_rays: row index out of range");
-  (void)hipSetDevice(c->device);
-  hipStream_t s = pick_stream(c, stream);
-  rt_status st = rt::check_dispatch(c, W, H, rgba8);
+  rt_status st = check_rows(c, "rt_dispatch_rays", H, rows, &nrows);
   if (st != RT_OK) return st;
+  (void)hipSetDevice(c->device);
+  TraceLaunch L{c, "rt_dispatch_rays", pick_stream(c, stream)};
+  if ((st = rt::check_dispatch(c, W, H, rgba8)) != RT_OK) return st;
   const uint32_t* d_rows = nullptr;
-  ScratchSlot* rows_slot = nullptr;
   uint64_t rows_gen = 0;
-  if (rows && (st = ensure_rows(c, rows, nrows, s, &rows_slot, &d_rows, &rows_gen)) != RT_OK) return st;
-  if ((st = rt::dispatch_frame(c, W, H, d_rows, nrows, rgba8, rgba32f, s, 4, 1, nullptr, 0, rows_gen)) != RT_OK)
-    return st;
-  if (rows_slot) HIPCHK(c, slot_mark_use(*rows_slot, s), "rows: record use");
-  return RT_OK;
+  if ((st = L.take_rows(rows, nrows, &d_rows, &rows_gen)) != RT_OK) return st;
+  return rt::launch_frame(L, W, H, d_rows, nrows, rgba8, rgba32f, 4, 1, nullptr, 0, rows_gen);
 }
 
 rt_status rt_dispatch_frames(rt_ctx_t c, uint32_t W, uint32_t H, uint32_t nframes, const float* cameras,
@@ -1898,16 +1953,8 @@ static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion
     return fail(c, RT_E_INVALID, fn + ": output plane not aligned (hits, normal: 16 bytes; uv, object: 8)");
   if ((uintptr_t)out.motion % 16u) return fail(c, RT_E_INVALID, fn + ": motion plane not aligned to 16 bytes");
   if (W == 0 || H == 0) return fail(c, RT_E_INVALID, fn + ": bad size");
-  if (!rows) nrows = H;
-  if (nrows == 0 || nrows > H) return fail(c, RT_E_INVALID, fn + ": bad row count");
-  if (rows)
-    for (uint32_t r = 0; r < nrows; ++r)
-      if (rows[r] >= H) return fail(c, RT_E_INVALID, fn + ": row index out of range");
-  if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, fn + ": no TLAS built");
-  if (c->tlas_stale)
-    return fail(c, RT_E_INVALID, fn + ": scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
-  if (c->tlas_refit)
-    return fail(c, RT_E_INVALID, fn + ": BLAS refitted, rt_tlas_build (an update will do) must follow");
+  rt_status st = check_rows(c, fn.c_str(), H, rows, &nrows);
+  if (st != RT_OK || (st = check_scene_ready(c, fn.c_str())) != RT_OK) return st;
   if (!c->have_camera) return fail(c, RT_E_INVALID, fn + ": camera not set");
   if (out.motion && !c->motion_on)
     return fail(c, RT_E_INVALID, fn + ": motion plane asked for, but motion history is off (rt_set_motion_history)");
@@ -1916,10 +1963,8 @@ static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion
   // the kernels index a plane's entries with 32 bits, as the frame kernels index their pixels
   if ((uint64_t)nrows * W >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, fn + ": more than 2^32 pixels");
   (void)hipSetDevice(c->device);
-  hipStream_t s = pick_stream(c, stream);
-  rt::SceneView sv = scene_view(c);
-  if (sv.stack_cap > rt::kMaxTraversalStack)
-    return fail(c, RT_E_UNSUPPORTED, fn + ": BVH too deep for the traversal stack");
+  TraceLaunch L{c, fn.c_str(), pick_stream(c, stream)};
+  if ((st = L.open()) != RT_OK) return st;
   rt::GbufMotionParams mp;
   rt::GbufParams& gb = mp.gb;
   rt::frame_cam(c->cam_cb, gb.cam);
@@ -1934,24 +1979,17 @@ static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion
   motion_cams(c->cam_cb, prev_cb, mp.cams);
   mp.motion = out.motion;
   mp.recs = c->ver[c->cur].motion;
-  rt_status st;
   const uint32_t* d_rows = nullptr;
-  ScratchSlot* rows_slot = nullptr;
   uint64_t rows_gen = 0;
-  if (rows && (st = ensure_rows(c, rows, nrows, s, &rows_slot, &d_rows, &rows_gen)) != RT_OK) return st;
-  ScratchSlot* ovf_slot = nullptr;
-  if (!rt::gbuffer_packet(sv, c->schedule)) {  // the per-lane kernel's overflow stack: 16 x 16 pixel workgroups
-    const size_t lanes = (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256;
-    if ((st = ensure_overflow(c, sv, lanes, s, &ovf_slot)) != RT_OK) return st;
-  }
-  HIPCHK(c, order_after_tlas(c, s), (fn + ": order after the TLAS build").c_str());
-  const hipError_t e = motion_kernels
-                           ? rt::launch_trace_gbuffer_motion(sv, mp, d_rows, c->d_stats, c->stats_on, c->schedule, s)
-                           : rt::launch_trace_gbuffer(sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, s);
-  if (e != hipSuccess) return hip_fail(c, e, "G-buffer launch");
-  HIPCHK(c, note_reader(c->ver[c->cur], s), (fn + ": record use").c_str());
-  if (ovf_slot) HIPCHK(c, slot_mark_use(*ovf_slot, s), "overflow stack: record use");
-  if (rows_slot) HIPCHK(c, slot_mark_use(*rows_slot, s), "rows: record use");
+  if ((st = L.take_rows(rows, nrows, &d_rows, &rows_gen)) != RT_OK) return st;
+  // the per-lane kernel's overflow stack: 16 x 16 pixel workgroups
+  const size_t lanes = rt::gbuffer_packet(L.sv, c->schedule) ? 0 : (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256;
+  if ((st = L.take_overflow_and_order(lanes)) != RT_OK) return st;
+  st = L.finish(motion_kernels
+                    ? rt::launch_trace_gbuffer(L.sv, mp, d_rows, c->d_stats, c->stats_on, c->schedule, L.s)
+                    : rt::launch_trace_gbuffer(L.sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, L.s),
+                "G-buffer launch");
+  if (st != RT_OK) return st;
   if (c->stats_on) {
     c->dispatches += 1;
     c->pixels += (uint64_t)W * nrows;
@@ -1999,30 +2037,17 @@ rt_status rt_trace_rays(rt_ctx_t c, const float* rays, uint32_t n, uint32_t ray_
   const bool cull_back = (ray_flags & RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES) != 0;
   const bool cull_front = (ray_flags & RT_RAY_FLAG_CULL_FRONT_FACING_TRIANGLES) != 0;
   if (cull_back && cull_front) return fail(c, RT_E_INVALID, "rt_trace_rays: both cull flags set");
-  if (c->cur < 0 && !c->tlas_stale) return fail(c, RT_E_INVALID, "rt_trace_rays: no TLAS built");
-  if (c->tlas_stale)
-    return fail(c, RT_E_INVALID, "rt_trace_rays: scene stale (BLAS rebuilt, or the last rt_tlas_build failed)");
-  if (c->tlas_refit)
-    return fail(c, RT_E_INVALID, "rt_trace_rays: BLAS refitted, rt_tlas_build (an update will do) must follow");
+  rt_status st = check_scene_ready(c, "rt_trace_rays");
+  if (st != RT_OK) return st;
   (void)hipSetDevice(c->device);
-  rt::SceneView sv = scene_view(c);
-  sv.cull_sense = cull_front ? -1.0f : 1.0f;
-  if (sv.stack_cap > rt::kMaxTraversalStack)
-    return fail(c, RT_E_UNSUPPORTED, "rt_trace_rays: BVH too deep for the traversal stack");
+  TraceLaunch L{c, "rt_trace_rays", pick_stream(c, stream)};
+  if ((st = L.open()) != RT_OK) return st;
+  L.sv.cull_sense = cull_front ? -1.0f : 1.0f;
   if (n == 0) return RT_OK;
-  hipStream_t s = pick_stream(c, stream);
-  ScratchSlot* ovf_slot = nullptr;
-  {
-    rt_status st = ensure_overflow(c, sv, (size_t)((n + 255) / 256) * 256, s, &ovf_slot);
-    if (st != RT_OK) return st;
-  }
-  HIPCHK(c, order_after_tlas(c, s), "rt_trace_rays: order after the TLAS build");
-  hipError_t e = rt::launch_trace_rays(sv, rays, n, (ray_flags & RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH) != 0,
-                                       cull_back || cull_front, hits, uv, c->d_stats, c->stats_on, s);
-  if (e != hipSuccess) return hip_fail(c, e, "trace_rays launch");
-  HIPCHK(c, note_reader(c->ver[c->cur], s), "rt_trace_rays: record use");
-  if (ovf_slot) HIPCHK(c, slot_mark_use(*ovf_slot, s), "overflow stack: record use");
-  return RT_OK;
+  if ((st = L.take_overflow_and_order((size_t)((n + 255) / 256) * 256)) != RT_OK) return st;
+  return L.finish(rt::launch_trace_rays(L.sv, rays, n, (ray_flags & RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH) != 0,
+                                        cull_back || cull_front, hits, uv, c->d_stats, c->stats_on, L.s),
+                  "trace_rays launch");
 }
 
 // Host service: rt_trace_rays by brute force over one mesh under one instance transform, with the intersection

@@ -123,9 +123,23 @@ struct PacketGeometry {
   bool plannable = false;              // a work list may drive the launch
 };
 PacketGeometry packet_geometry(const SceneView& sc, const FrameParams& fp, int schedule);
-// The GPU's wave slots for the packet kernel a tile-balance launch of this shape runs (the recording / list
-// instantiation): hipOccupancyMaxActiveBlocksPerMultiprocessor of that kernel x waves per workgroup x the device's
-// CUs, cached per (kernel, device); 0 if the runtime cannot tell.
+// A frame launch's compile-time choices: which instantiation of the frame kernels it runs. select_frame_kernel is
+// the one place that derives them (rt_trace.hip: canonical() holds every rule); `balance`: the launch runs a work
+// list or records wave times (FrameParams::plan / cost).
+struct FrameKernel {
+  bool packet = false;  // the packet kernel (PacketGeometry::packet), else the per-lane one
+  int mode = 0;         // shade mode 0 .. 2; 3: REF with reflectivity 0, without the reflection chain
+  bool stats = false;   // device counters
+  int ks = 0;           // PacketGeometry::ks
+  bool bal = false;     // the tile balance's kernel (work list, wave times); never under the watertight test
+  bool mf = true;       // the general kernel: several frames per launch or RGB8 strips; false: one RGBA8 frame
+  int tt = 0;           // triangle test (1: watertight)
+};
+FrameKernel select_frame_kernel(const SceneView& sc, const FrameParams& fp, const PacketGeometry& g, bool stats,
+                                bool balance);
+// The GPU's wave slots for the packet kernel a tile-balance launch of this shape runs (select_frame_kernel with the
+// balance on and the counters off: what launch_trace_frame launches): hipOccupancyMaxActiveBlocksPerMultiprocessor of
+// that kernel x waves per workgroup x the device's CUs, cached per (kernel, device); 0 if the runtime cannot tell.
 uint32_t trace_wave_slots(const SceneView& sc, const FrameParams& fp, int schedule, int device);
 
 // Tile balance (k_tile_plan): the summary the plan kernel leaves in host-mapped memory for the next dispatches.
@@ -175,11 +189,11 @@ hipError_t launch_trace_rays(const SceneView& scene, const float* rays, uint32_t
 // per-lane schedule, or trees too deep for the packet stack) the per-lane kernel over 16 x 16 pixel workgroups, whose
 // scene view carries the launch's overflow stack. Counters when `stats`; the triangle test is sc.tri_test.
 bool gbuffer_packet(const SceneView& scene, int schedule);
-hipError_t launch_trace_gbuffer(const SceneView& scene, const GbufParams& gb, const uint32_t* d_rows,
+// P: GbufParams (rt_dispatch_gbuffer, the four-plane kernels) or GbufMotionParams (rt_dispatch_gbuffer_motion: the
+// same pass with the motion plane, the motion kernels on the same grids); both instantiated in rt_trace.hip
+template <typename P>
+hipError_t launch_trace_gbuffer(const SceneView& scene, const P& params, const uint32_t* d_rows,
                                 unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
-// The same pass with the motion plane (rt_dispatch_gbuffer_motion): the motion kernels on the same grids.
-hipError_t launch_trace_gbuffer_motion(const SceneView& scene, const GbufMotionParams& mp, const uint32_t* d_rows,
-                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
 
 // rank_stride_rows: rows from one rank's block of `gathered` to the next (0: rows_per_rank, one frame per block;
 // a batched gather holds several frames per rank block and passes their total)

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -638,6 +639,18 @@ __shared__ int g_hyb[kMaxPacketWaves][kHybridStack * kHybridLanes];
 // of the scene's largest BLAS, copied in by every packet workgroup at its start; the BLAS walk reads those nodes'
 // planes from here (ds_read_b128, a broadcast of one address) instead of the scalar cache
 __shared__ f4v g_top[RT_LDS_TOP * 8];
+// A packet kernel's first statement (BLOCK: its workgroup's threads). Every thread takes part, before any wave may
+// leave (the work list's end): the barrier needs the whole workgroup.
+template <int BLOCK>
+__device__ __forceinline__ void stage_top_nodes(const SceneView& sc) {
+  const RT_GLOBAL f4v* src = (const RT_GLOBAL f4v*)((const RT_GLOBAL char*)sc.pool_nodes + ((uint32_t)sc.lds_root << 7));
+  const uint32_t nrow = (uint32_t)sc.lds_n * 8u;
+  for (uint32_t i = threadIdx.x; i < nrow; i += BLOCK) g_top[i] = src[i];
+  __syncthreads();
+}
+#else
+template <int BLOCK>
+__device__ __forceinline__ void stage_top_nodes(const SceneView&) {}
 #endif
 
 // Per-lane subtree walk inside the packet schedule (north star: wavefront ballot / prefix-sum ray
@@ -1747,63 +1760,6 @@ __device__ __forceinline__ void gbuffer_store(const SceneView& sc, const GbufPar
   }
 }
 
-// Packet schedule: the frame kernel's one-sample layout (a wave = an 8 x 8 pixel tile, a workgroup RT_PACKET_WX x
-// RT_PACKET_WY waves, the plain grid), one closest-hit packet walk per wave. Rays outside the image or the row list
-// join the packet dead; only in-image pixels are stored. Held to the plain kernels' SGPR budget (8 waves per SIMD).
-template <bool STATS, int TT>
-__global__ __launch_bounds__(packet_block(1)) RT_PLAIN_SGPR_ATTR
-void k_trace_gbuffer_packet(SceneView sc, GbufParams gb, const uint32_t* __restrict__ rows,
-                            unsigned long long* __restrict__ stats) {
-#if RT_LDS_TOP
-  {
-    const RT_GLOBAL f4v* src = (const RT_GLOBAL f4v*)((const RT_GLOBAL char*)sc.pool_nodes + ((uint32_t)sc.lds_root << 7));
-    const uint32_t nrow = (uint32_t)sc.lds_n * 8u;
-    for (uint32_t i = threadIdx.x; i < nrow; i += packet_block(1)) g_top[i] = src[i];
-    __syncthreads();
-  }
-#endif
-  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
-  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
-  const bool inimg = x < gb.width && orow < gb.nrows;
-  uint32_t py = 0;
-  if (inimg) py = rows ? rows[orow] : orow;
-  V3 O, D;
-  gbuffer_ray(gb, x, py, O, D);
-  Counters cnt;
-  if (STATS && inimg) ++cnt.primary;
-  HitRec hit;
-  bool found;
-  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
-  if (inimg) gbuffer_store(sc, gb, orow * gb.width + x, found, hit);  // < 2^32 pixels (rt_api.cpp)
-  if (STATS) flush_stats<true>(cnt, stats);
-}
-
-// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_frame's indexing, LDS stack
-// and per-launch HBM overflow.
-template <bool STATS, int TT>
-__global__ __launch_bounds__(kBlock) void k_trace_gbuffer(SceneView sc, GbufParams gb, const uint32_t* __restrict__ rows,
-                                                          unsigned long long* __restrict__ stats) {
-  extern __shared__ int s_stack[];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
-  Counters cnt;
-  if (px < gb.width && orow < gb.nrows) {
-    const uint32_t py = rows ? rows[orow] : orow;
-    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
-    V3 O, D;
-    gbuffer_ray(gb, px, py, O, D);
-    HitRec hit;
-    if (STATS) ++cnt.primary;
-    const bool f = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
-    gbuffer_store(sc, gb, orow * gb.width + px, f, hit);
-  }
-  if (STATS) flush_stats<false>(cnt, stats);
-}
-
 // ------------------------------------------------------------------------------------------
 // G-buffer pass with motion vectors (rt_dispatch_gbuffer_motion): the G-buffer kernels' launch shapes,
 // ray and four planes (gbuffer_ray, gbuffer_store: the same calls, so the same bits) and a fifth plane, `motion`.
@@ -1849,63 +1805,83 @@ __device__ __forceinline__ void gbuffer_motion_store(const SceneView& sc, const 
 #define RT_MOTION_SGPR_ATTR
 #endif
 
-// k_trace_gbuffer_packet with the fifth plane: the same tile layout, ray and walk.
-template <bool STATS, int TT>
-__global__ __launch_bounds__(packet_block(1)) RT_MOTION_SGPR_ATTR
-void k_trace_gbuffer_motion_packet(SceneView sc, GbufMotionParams mp, const uint32_t* __restrict__ rows,
-                                   unsigned long long* __restrict__ stats) {
-#if RT_LDS_TOP
-  {
-    const RT_GLOBAL f4v* src = (const RT_GLOBAL f4v*)((const RT_GLOBAL char*)sc.pool_nodes + ((uint32_t)sc.lds_root << 7));
-    const uint32_t nrow = (uint32_t)sc.lds_n * 8u;
-    for (uint32_t i = threadIdx.x; i < nrow; i += packet_block(1)) g_top[i] = src[i];
-    __syncthreads();
-  }
-#endif
+// The kernels below are written once for both launches. P is the launch's parameter structure, and with it the
+// kernel's argument block: GbufParams (the four planes) or GbufMotionParams (the four planes and motion). A
+// four-plane launch compiles the motion store out.
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const GbufParams& p) { return p; }
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const GbufMotionParams& p) { return p.gb; }
+__device__ __forceinline__ void gbuffer_motion_store(const SceneView&, const GbufParams&, uint32_t, bool, const HitRec&,
+                                                     V3, V3) {}
+
+// Packet schedule: the frame kernel's one-sample layout (a wave = an 8 x 8 pixel tile, a workgroup RT_PACKET_WX x
+// RT_PACKET_WY waves, the plain grid), one closest-hit packet walk per wave. Rays outside the image or the row list
+// join the packet dead; only in-image pixels are stored.
+template <bool STATS, int TT, typename P>
+__device__ __forceinline__ void gbuffer_packet_body(const SceneView& sc, const P& p,
+                                                    const uint32_t* __restrict__ rows,
+                                                    unsigned long long* __restrict__ stats) {
+  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
+  const GbufParams& gb = gbuf(p);
   constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
   const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
   const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
-  const bool inimg = x < mp.gb.width && orow < mp.gb.nrows;
+  const bool inimg = x < gb.width && orow < gb.nrows;
   uint32_t py = 0;
   if (inimg) py = rows ? rows[orow] : orow;
   V3 O, D;
-  gbuffer_ray(mp.gb, x, py, O, D);
+  gbuffer_ray(gb, x, py, O, D);
   Counters cnt;
   if (STATS && inimg) ++cnt.primary;
   HitRec hit;
   bool found;
   trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
   if (inimg) {
-    const uint32_t o = orow * mp.gb.width + x;  // < 2^32 pixels (rt_api.cpp)
-    gbuffer_store(sc, mp.gb, o, found, hit);
-    gbuffer_motion_store(sc, mp, o, found, hit, O, D);
+    const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
+    gbuffer_store(sc, gb, o, found, hit);
+    gbuffer_motion_store(sc, p, o, found, hit, O, D);
   }
   if (STATS) flush_stats<true>(cnt, stats);
 }
 
-// k_trace_gbuffer with the fifth plane: the per-lane twin.
+// The packet kernel under its two register budgets (amdgpu_num_sgpr takes no template-dependent value): the
+// four-plane one held to the plain kernels' SGPR budget (8 waves per SIMD), the motion one to RT_MOTION_SGPR_ATTR.
 template <bool STATS, int TT>
-__global__ __launch_bounds__(kBlock) void k_trace_gbuffer_motion(SceneView sc, GbufMotionParams mp,
-                                                                 const uint32_t* __restrict__ rows,
-                                                                 unsigned long long* __restrict__ stats) {
+__global__ __launch_bounds__(packet_block(1)) RT_PLAIN_SGPR_ATTR
+void k_trace_gbuffer_packet(SceneView sc, GbufParams gb, const uint32_t* __restrict__ rows,
+                            unsigned long long* __restrict__ stats) {
+  gbuffer_packet_body<STATS, TT>(sc, gb, rows, stats);
+}
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_MOTION_SGPR_ATTR
+void k_trace_gbuffer_motion_packet(SceneView sc, GbufMotionParams mp, const uint32_t* __restrict__ rows,
+                                   unsigned long long* __restrict__ stats) {
+  gbuffer_packet_body<STATS, TT>(sc, mp, rows, stats);
+}
+
+// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_frame's indexing, LDS stack
+// and per-launch HBM overflow.
+template <bool STATS, int TT, typename P>
+__global__ __launch_bounds__(kBlock) void k_trace_gbuffer(SceneView sc, P p, const uint32_t* __restrict__ rows,
+                                                          unsigned long long* __restrict__ stats) {
   extern __shared__ int s_stack[];
+  const GbufParams& gb = gbuf(p);
   const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
   const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
   const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
   Counters cnt;
-  if (px < mp.gb.width && orow < mp.gb.nrows) {
+  if (px < gb.width && orow < gb.nrows) {
     const uint32_t py = rows ? rows[orow] : orow;
     const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
     V3 O, D;
-    gbuffer_ray(mp.gb, px, py, O, D);
+    gbuffer_ray(gb, px, py, O, D);
     HitRec hit;
     if (STATS) ++cnt.primary;
     const bool f = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
-    const uint32_t o = orow * mp.gb.width + px;
-    gbuffer_store(sc, mp.gb, o, f, hit);
-    gbuffer_motion_store(sc, mp, o, f, hit, O, D);
+    const uint32_t o = orow * gb.width + px;
+    gbuffer_store(sc, gb, o, f, hit);
+    gbuffer_motion_store(sc, p, o, f, hit, O, D);
   }
   if (STATS) flush_stats<false>(cnt, stats);
 }
@@ -2007,82 +1983,77 @@ __global__ __launch_bounds__(256) void k_assemble16_rgb(uint32_t W4, uint32_t H,
   }
 }
 
-// whether a launch needs the general frame kernel (MF): several frames, or RGB8 strips
-__host__ inline bool launch_multi_frame(const FrameParams& fp) { return fp.nframes > 1u || fp.out_bpp != 4u; }
+// Runtime choices lifted to template arguments. OneOf<Vs...>{v} is a value that must equal one of Vs; lift(f, a, b,
+// ...) calls f(std::integral_constant<..., V>{}...) with each choice's matching constant and returns true, or calls
+// nothing and returns false when a value is outside its list. f is instantiated for every combination of the lists:
+// it names a kernel only under `if constexpr` where not every combination exists.
+template <auto... Vs>
+struct OneOf {
+  std::common_type_t<decltype(Vs)...> v;
+};
+using Flag = OneOf<false, true>;
+template <typename F>
+bool lift(F&& f) {
+  f();
+  return true;
+}
+template <typename F, auto... Vs, typename... Rest>
+bool lift(F&& f, OneOf<Vs...> c, Rest... rest) {
+  return ((c.v == Vs && lift([&](auto... cs) { f(std::integral_constant<decltype(Vs), Vs>{}, cs...); }, rest...)) || ...);
+}
 
-template <int MODE, bool STATS>
-hipError_t launch_mode(const SceneView& sc, const FrameParams& fp, const uint32_t* rows, void* rgba8,
-                       float* rgba32f, unsigned long long* stats, int schedule, uint32_t plan_items, hipStream_t s) {
-  dim3 grid((fp.width + 15) / 16, (fp.nrows + 15) / 16, fp.nframes);
-  const PacketGeometry g = packet_geometry(sc, fp, schedule);
+// Every rule of the frame kernels' selection: the instantiations that exist are the values this maps to themselves.
+constexpr FrameKernel canonical(FrameKernel k) {
   // Watertight mode (sc.tri_test set): the TT = 1 instantiations. The packet schedule always takes the plain grid's
   // general kernel (no tile balance, any frame count and output format: schedule choices the image never depends
   // on), and REF with reflectivity 0 the reflective kernel (MODE 0: the same image without MODE 3's specialisation),
   // which keeps the code object to one packet kernel per shade mode, counter switch and sample layout.
-  if constexpr (MODE != 3) {
-    if (sc.tri_test) {
-      if (g.packet) {
+  if (k.tt) {
+    if (k.mode == 3) k.mode = 0;
+    k.bal = false;
+    k.mf = true;
+  }
+  if (k.stats) k.mf = true;            // counter passes always take the general (MF) kernel: fewer instantiations
+  if (RT_PACKET_RAYS != 1) k.ks = 0;   // sample lanes need one ray per lane
+  if (!k.packet) {                     // the per-lane kernel has none of the three
+    k.ks = 0;
+    k.bal = false;
+    k.mf = true;
+  }
+  return k;
+}
+constexpr bool same(const FrameKernel& a, const FrameKernel& b) {
+  return a.packet == b.packet && a.mode == b.mode && a.stats == b.stats && a.ks == b.ks && a.bal == b.bal &&
+         a.mf == b.mf && a.tt == b.tt;
+}
+
+// A selection's kernel: what to launch, and what to ask the runtime about (trace_wave_slots). fn null: no such kernel
+// (a shade mode out of range).
+using FrameKernelFn = void (*)(SceneView, FrameParams, const uint32_t*, uint32_t*, float4*, unsigned long long*);
+struct FrameLaunch {
+  FrameKernelFn fn = nullptr;
+  int block = 0;
+  size_t lds = 0;  // dynamic LDS: the per-lane kernel's stacks
+};
+FrameLaunch frame_launch(const FrameKernel& sel, const SceneView& sc) {
+  FrameLaunch l;
+  l.block = sel.packet ? packet_block(sel.ks) : kBlock;
+  l.lds = sel.packet ? 0 : (size_t)sc.lds_cap * kBlock * sizeof(int);
+  lift(
+      [&](auto P, auto M, auto S, auto KS, auto B, auto MF, auto T) {
+        constexpr FrameKernel k{P.value, M.value, S.value, KS.value, B.value, MF.value, T.value};
         constexpr int R = RT_PACKET_RAYS;
-        const dim3 gp(g.grid_x, g.grid_y, fp.nframes);
-#define RT_LAUNCH_WT(KS)                                                                                        \
-  hipLaunchKernelGGL((k_trace_frame_packet<MODE, STATS, R, (R == 1 ? KS : 0), false, true, 1>), gp,             \
-                     dim3(packet_block(R == 1 ? KS : 0)), 0, s, sc, fp, rows, (uint32_t*)rgba8, (float4*)rgba32f, \
-                     stats)
-        if (g.ks == 1) RT_LAUNCH_WT(1);
-        else if (g.ks == 2) RT_LAUNCH_WT(2);
-        else if (g.ks == 4) RT_LAUNCH_WT(4);
-        else RT_LAUNCH_WT(0);
-#undef RT_LAUNCH_WT
-      } else {
-        hipLaunchKernelGGL((k_trace_frame<MODE, STATS, 1>), grid, dim3(kBlock), (size_t)sc.lds_cap * kBlock * sizeof(int),
-                           s, sc, fp, rows, (uint32_t*)rgba8, (float4*)rgba32f, stats);
-      }
-      return hipGetLastError();
-    }
-  }
-  if (g.packet) {
-    constexpr int R = RT_PACKET_RAYS;
-    const int ks = g.ks;
-    // the plain grid, or (tile balance) one wave per work-list item, as many as the list's budget
-    dim3 gp = fp.plan ? dim3((plan_items + g.wl - 1) / g.wl) : dim3(g.grid_x, g.grid_y, fp.nframes);
-    // counter passes always take the general (MF) kernel: fewer instantiations
-    const bool mf = STATS || launch_multi_frame(fp);
-#define RT_LAUNCH_PACKET_K(KS, BALV, MFV)                                                                      \
-  do {                                                                                                         \
-    if constexpr (!BALV && !STATS && MODE != 0 && (R == 1 ? KS : 0) >= 1)                                        \
-      hipLaunchKernelGGL((k_trace_frame_packet8<MODE, STATS, R, (R == 1 ? KS : 0), BALV, MFV>), gp,           \
-                         dim3(packet_block(R == 1 ? KS : 0)), 0, s, sc, fp, rows, (uint32_t*)rgba8,             \
-                         (float4*)rgba32f, stats);                                                             \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_trace_frame_packet<MODE, STATS, R, (R == 1 ? KS : 0), BALV, MFV>), gp,            \
-                         dim3(packet_block(R == 1 ? KS : 0)), 0, s, sc, fp, rows, (uint32_t*)rgba8,             \
-                         (float4*)rgba32f, stats);                                                             \
-  } while (0)
-#define RT_LAUNCH_PACKET(KS)                                                                                   \
-  do {                                                                                                         \
-    if constexpr (STATS) {                                                                                     \
-      if (fp.plan || fp.cost) RT_LAUNCH_PACKET_K(KS, true, true);                                              \
-      else RT_LAUNCH_PACKET_K(KS, false, true);                                                                \
-    } else if (fp.plan || fp.cost) {                                                                           \
-      if (mf) RT_LAUNCH_PACKET_K(KS, true, true);                                                              \
-      else RT_LAUNCH_PACKET_K(KS, true, false);                                                                \
-    } else {                                                                                                   \
-      if (mf) RT_LAUNCH_PACKET_K(KS, false, true);                                                             \
-      else RT_LAUNCH_PACKET_K(KS, false, false);                                                               \
-    }                                                                                                          \
-  } while (0)
-    if (ks == 1) RT_LAUNCH_PACKET(1);
-    else if (ks == 2) RT_LAUNCH_PACKET(2);
-    else if (ks == 4) RT_LAUNCH_PACKET(4);
-    else RT_LAUNCH_PACKET(0);
-#undef RT_LAUNCH_PACKET
-#undef RT_LAUNCH_PACKET_K
-  } else {
-    size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
-    hipLaunchKernelGGL((k_trace_frame<MODE, STATS>), grid, dim3(kBlock), lds, s, sc, fp, rows,
-                       (uint32_t*)rgba8, (float4*)rgba32f, stats);
-  }
-  return hipGetLastError();
+        if constexpr (same(canonical(k), k)) {
+          if constexpr (!k.packet) l.fn = &k_trace_frame<k.mode, k.stats, k.tt>;
+          // k_trace_frame_packet8: see its definition (the launches that can use the eighth wave)
+          else if constexpr (!k.bal && !k.stats && k.mode != 0 && k.ks >= 1 && !k.tt)
+            l.fn = &k_trace_frame_packet8<k.mode, k.stats, R, k.ks, k.bal, k.mf>;
+          else l.fn = &k_trace_frame_packet<k.mode, k.stats, R, k.ks, k.bal, k.mf, k.tt>;
+        }
+      },
+      Flag{sel.packet}, OneOf<0, 1, 2, 3>{sel.mode}, Flag{sel.stats}, OneOf<0, 1, 2, 4>{sel.ks}, Flag{sel.bal},
+      Flag{sel.mf}, OneOf<0, 1>{sel.tt});
+  return l;
 }
 
 }  // namespace
@@ -2113,27 +2084,35 @@ PacketGeometry packet_geometry(const SceneView& sc, const FrameParams& fp, int s
   return g;
 }
 
+FrameKernel select_frame_kernel(const SceneView& sc, const FrameParams& fp, const PacketGeometry& g, bool stats,
+                                bool balance) {
+  FrameKernel k;
+  k.packet = g.packet;
+  // the reference scene's parity config pins reflectivity to 0: a kernel without
+  // the reflection-chain state (registers, the per-lane sk[] stack) then runs at a higher occupancy
+  k.mode = (fp.shade_mode == 0 && fp.material.reflectivity == 0.0f && RT_REF_NOREFL) ? 3 : (int)fp.shade_mode;
+  k.stats = stats;
+  k.ks = g.ks;
+  k.bal = balance;
+  k.mf = fp.nframes > 1u || fp.out_bpp != 4u;  // several frames, or RGB8 strips
+  k.tt = sc.tri_test ? 1 : 0;
+  return canonical(k);
+}
+
 hipError_t launch_trace_frame(const SceneView& sc, const FrameParams& fp, const uint32_t* d_rows,
                               void* rgba8, float* rgba32f, unsigned long long* d_stats, bool stats,
                               int schedule, uint32_t plan_items, hipStream_t s) {
-  switch (fp.shade_mode) {
-    case 0:
-      // the reference scene's parity config pins reflectivity to 0: a kernel without
-      // the reflection-chain state (registers, the per-lane sk[] stack) then runs at a higher occupancy
-      if (fp.material.reflectivity == 0.0f && RT_REF_NOREFL && !sc.tri_test)
-        return stats ? launch_mode<3, true>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s)
-                     : launch_mode<3, false>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s);
-      return stats ? launch_mode<0, true>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s)
-                   : launch_mode<0, false>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s);
-    case 1:
-      return stats ? launch_mode<1, true>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s)
-                   : launch_mode<1, false>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s);
-    case 2:
-      return stats ? launch_mode<2, true>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s)
-                   : launch_mode<2, false>(sc, fp, d_rows, rgba8, rgba32f, d_stats, schedule, plan_items, s);
-    default:
-      return hipErrorInvalidValue;
-  }
+  const PacketGeometry g = packet_geometry(sc, fp, schedule);
+  const FrameKernel k = select_frame_kernel(sc, fp, g, stats, fp.plan || fp.cost);
+  const FrameLaunch l = frame_launch(k, sc);
+  if (!l.fn) return hipErrorInvalidValue;
+  // per lane 16 x 16 pixel workgroups; the packet kernel's plain grid, or (tile balance) one wave per work-list
+  // item, as many as the list's budget
+  const dim3 grid = !k.packet             ? dim3((fp.width + 15) / 16, (fp.nrows + 15) / 16, fp.nframes)
+                    : (k.bal && fp.plan) ? dim3((plan_items + g.wl - 1) / g.wl)
+                                         : dim3(g.grid_x, g.grid_y, fp.nframes);
+  hipLaunchKernelGGL(l.fn, grid, dim3(l.block), l.lds, s, sc, fp, d_rows, (uint32_t*)rgba8, (float4*)rgba32f, d_stats);
+  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2476,39 +2455,19 @@ __global__ __launch_bounds__(kPlanThreads) void k_tile_plan(PlanArgs a) {
   }
 }
 
-namespace {
-template <int MODE, int KS>
-const void* bal_kernel(bool mf) {
-  constexpr int R = RT_PACKET_RAYS;
-  return mf ? reinterpret_cast<const void*>(&k_trace_frame_packet<MODE, false, R, (R == 1 ? KS : 0), true, true>)
-            : reinterpret_cast<const void*>(&k_trace_frame_packet<MODE, false, R, (R == 1 ? KS : 0), true, false>);
-}
-template <int MODE>
-const void* bal_kernel_ks(int ks, bool mf) {
-  return ks == 1 ? bal_kernel<MODE, 1>(mf) : ks == 2 ? bal_kernel<MODE, 2>(mf) : ks == 4 ? bal_kernel<MODE, 4>(mf)
-                                                                                       : bal_kernel<MODE, 0>(mf);
-}
-}  // namespace
-
 uint32_t trace_wave_slots(const SceneView& sc, const FrameParams& fp, int schedule, int device) {
   const PacketGeometry g = packet_geometry(sc, fp, schedule);
   if (!g.packet) return 0;
-  const bool mf = launch_multi_frame(fp);
-  const void* k = nullptr;
-  switch (fp.shade_mode) {  // the instantiation launch_trace_frame picks (non-STATS, BAL)
-    case 0: k = (fp.material.reflectivity == 0.0f && RT_REF_NOREFL) ? bal_kernel_ks<3>(g.ks, mf)
-                                                                    : bal_kernel_ks<0>(g.ks, mf);
-            break;
-    case 1: k = bal_kernel_ks<1>(g.ks, mf); break;
-    case 2: k = bal_kernel_ks<2>(g.ks, mf); break;
-    default: return 0;
-  }
+  // what launch_trace_frame launches for this shape with the balance on and the counters off
+  const FrameLaunch l = frame_launch(select_frame_kernel(sc, fp, g, false, true), sc);
+  if (!l.fn) return 0;
+  const void* k = reinterpret_cast<const void*>(l.fn);
+  const int block = l.block;
   static std::mutex mu;
   static std::vector<std::pair<std::pair<const void*, int>, uint32_t>> cache;
   std::lock_guard<std::mutex> lk(mu);
   for (const auto& e : cache)
     if (e.first.first == k && e.first.second == device) return e.second;
-  const int block = packet_block(RT_PACKET_RAYS == 1 ? g.ks : 0);
   int nb = 0, cus = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, block, 0) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || nb <= 0 || cus <= 0)
@@ -2538,24 +2497,14 @@ hipError_t launch_trace_rays(const SceneView& sc, const float* rays, uint32_t n,
   dim3 grid((n + kBlock - 1) / kBlock);
   size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
   const float4* r = (const float4*)rays;
-  // watertight mode (sc.tri_test set): the TT = 1 instantiations
-#define RT_LAUNCH_RAYS(A, C, S)                                                                                   \
-  do {                                                                                                            \
-    if (sc.tri_test)                                                                                              \
-      hipLaunchKernelGGL((k_trace_rays<A, S, C, 1>), grid, dim3(kBlock), lds, s, sc, r, n, (uint4*)hits,          \
-                         (float2*)uv, d_stats);                                                                   \
-    else                                                                                                          \
-      hipLaunchKernelGGL((k_trace_rays<A, S, C>), grid, dim3(kBlock), lds, s, sc, r, n, (uint4*)hits, (float2*)uv, \
-                         d_stats);                                                                                \
-  } while (0)
-  if (any_hit) {
-    if (cull) { if (stats) RT_LAUNCH_RAYS(true, true, true); else RT_LAUNCH_RAYS(true, true, false); }
-    else { if (stats) RT_LAUNCH_RAYS(true, false, true); else RT_LAUNCH_RAYS(true, false, false); }
-  } else {
-    if (cull) { if (stats) RT_LAUNCH_RAYS(false, true, true); else RT_LAUNCH_RAYS(false, true, false); }
-    else { if (stats) RT_LAUNCH_RAYS(false, false, true); else RT_LAUNCH_RAYS(false, false, false); }
-  }
-#undef RT_LAUNCH_RAYS
+  // any-hit, culling, counters and the triangle test (sc.tri_test set: the watertight TT = 1 instantiations) are
+  // compile-time choices
+  lift(
+      [&](auto A, auto C, auto S, auto T) {
+        hipLaunchKernelGGL((k_trace_rays<A.value, S.value, C.value, T.value>), grid, dim3(kBlock), lds, s, sc, r, n,
+                           (uint4*)hits, (float2*)uv, d_stats);
+      },
+      Flag{any_hit}, Flag{cull}, Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
   return hipGetLastError();
 }
 
@@ -2564,47 +2513,33 @@ bool gbuffer_packet(const SceneView& sc, int schedule) {
 }
 
 // counters and the triangle test (sc.tri_test: the watertight instantiations on the vertex-form pool) are
-// compile-time choices, as for the frame kernels; P: the launch's parameter structure
-#define RT_LAUNCH_GBUF(K, GRID, BLOCK, LDS, P)                                                               \
-  do {                                                                                                       \
-    if (sc.tri_test) {                                                                                       \
-      if (stats) hipLaunchKernelGGL((K<true, 1>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);               \
-      else hipLaunchKernelGGL((K<false, 1>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);                    \
-    } else {                                                                                                 \
-      if (stats) hipLaunchKernelGGL((K<true, 0>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);               \
-      else hipLaunchKernelGGL((K<false, 0>), GRID, BLOCK, LDS, s, sc, P, d_rows, d_stats);                    \
-    }                                                                                                        \
-  } while (0)
-
-hipError_t launch_trace_gbuffer(const SceneView& sc, const GbufParams& gb, const uint32_t* d_rows,
-                                unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
-  if (gbuffer_packet(sc, schedule)) {
-    const uint32_t tw = 8u * (uint32_t)packet_wx(1), th = 8u * (uint32_t)packet_wy(1);
-    const dim3 grid((gb.width + tw - 1) / tw, (gb.nrows + th - 1) / th);
-    RT_LAUNCH_GBUF(k_trace_gbuffer_packet, grid, dim3(packet_block(1)), 0, gb);
-  } else {
-    const dim3 grid((gb.width + 15) / 16, (gb.nrows + 15) / 16);
-    const size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
-    RT_LAUNCH_GBUF(k_trace_gbuffer, grid, dim3(kBlock), lds, gb);
-  }
+// compile-time choices, as for the frame kernels; P: the launch's parameter structure, which picks the kernels
+template <typename P>
+hipError_t launch_trace_gbuffer(const SceneView& sc, const P& p, const uint32_t* d_rows, unsigned long long* d_stats,
+                                bool stats, int schedule, hipStream_t s) {
+  const GbufParams& gb = gbuf(p);
+  const bool packet = gbuffer_packet(sc, schedule);
+  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
+  const dim3 grid((gb.width + tw - 1) / tw, (gb.nrows + th - 1) / th);
+  lift(
+      [&](auto S, auto T) {
+        if (!packet)
+          hipLaunchKernelGGL((k_trace_gbuffer<S.value, T.value, P>), grid, dim3(kBlock),
+                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, p, d_rows, d_stats);
+        else if constexpr (std::is_same_v<P, GbufMotionParams>)
+          hipLaunchKernelGGL((k_trace_gbuffer_motion_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, p,
+                             d_rows, d_stats);
+        else
+          hipLaunchKernelGGL((k_trace_gbuffer_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, p,
+                             d_rows, d_stats);
+      },
+      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
   return hipGetLastError();
 }
-
-hipError_t launch_trace_gbuffer_motion(const SceneView& sc, const GbufMotionParams& mp, const uint32_t* d_rows,
-                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
-  const GbufParams& gb = mp.gb;  // the G-buffer launch's grids
-  if (gbuffer_packet(sc, schedule)) {
-    const uint32_t tw = 8u * (uint32_t)packet_wx(1), th = 8u * (uint32_t)packet_wy(1);
-    const dim3 grid((gb.width + tw - 1) / tw, (gb.nrows + th - 1) / th);
-    RT_LAUNCH_GBUF(k_trace_gbuffer_motion_packet, grid, dim3(packet_block(1)), 0, mp);
-  } else {
-    const dim3 grid((gb.width + 15) / 16, (gb.nrows + 15) / 16);
-    const size_t lds = (size_t)sc.lds_cap * kBlock * sizeof(int);
-    RT_LAUNCH_GBUF(k_trace_gbuffer_motion, grid, dim3(kBlock), lds, mp);
-  }
-  return hipGetLastError();
-}
-#undef RT_LAUNCH_GBUF
+template hipError_t launch_trace_gbuffer(const SceneView&, const GbufParams&, const uint32_t*, unsigned long long*, bool,
+                                         int, hipStream_t);
+template hipError_t launch_trace_gbuffer(const SceneView&, const GbufMotionParams&, const uint32_t*, unsigned long long*,
+                                         bool, int, hipStream_t);
 
 hipError_t launch_assemble_strips(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
                                   const void* gathered, void* out, hipStream_t s, uint32_t rank_stride_rows,

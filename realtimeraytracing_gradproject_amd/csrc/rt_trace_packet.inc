@@ -10,14 +10,7 @@ __global__ __launch_bounds__(packet_block(KS)) __attribute__((amdgpu_waves_per_e
 void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows, uint32_t* __restrict__ rgba8,
                 float4* __restrict__ rgba32f, unsigned long long* __restrict__ stats) {
   static_assert(KS <= 1 || R == 1, "sample lanes need one ray per lane");
-#if RT_LDS_TOP
-  {  // every thread, before any wave may leave (the work list's end): the barrier needs the whole workgroup
-    const RT_GLOBAL f4v* src = (const RT_GLOBAL f4v*)((const RT_GLOBAL char*)sc.pool_nodes + ((uint32_t)sc.lds_root << 7));
-    const uint32_t nrow = (uint32_t)sc.lds_n * 8u;
-    for (uint32_t i = threadIdx.x; i < nrow; i += packet_block(KS)) g_top[i] = src[i];
-    __syncthreads();
-  }
-#endif
+  stage_top_nodes<packet_block(KS)>(sc);  // RT_LDS_TOP only
 #if RT_WAVE_TIMES
   const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
 #endif
