@@ -152,10 +152,24 @@ $(ASAN)/liboracle.so: oracle/rt_oracle.c oracle/rt_raster_oracle.c oracle/rt_ora
 $(ASAN)/obj_ingest_fuzz: tools/obj_ingest_fuzz.cpp $(ASAN)/rt_host.o | $(ASAN)
 	g++ -O1 -g -std=c++17 $(SANFLAGS) -o $@ $^
 
+# a standalone driver of rt_host_ao_rays (rt_api.cpp: it needs the HIP compiler, so its HOST side is compiled with
+# clang's sanitizers and the program linked by hipcc; no Python in the process, no GPU call; CPU only):
+#   make asan-ao && build/asan/ao_rays_check
+asan-ao: $(ASAN)/ao_rays_check
+
+$(ASAN)/rt_api.o: $(SRC)/rt_api.cpp $(HDRS) | $(ASAN)
+	$(HIPCC) $(HIPFLAGS) -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -c $< -o $@
+
+$(ASAN)/ao_rays_asan.o: tools/ao_rays_asan.cpp include/rt_api.h | $(ASAN)
+	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
+
+$(ASAN)/ao_rays_check: $(ASAN)/ao_rays_asan.o $(ASAN)/rt_api.o $(BUILD)/rt_comm.o $(BUILD)/rt_host.o $(BUILD)/rt_lbvh.o $(BUILD)/rt_trace.o $(BUILD)/rt_raster.o
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
+
 $(ASAN):
 	mkdir -p $@
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VDIR)
 
-.PHONY: all clean ref asan
+.PHONY: all clean ref asan asan-ao

@@ -81,6 +81,12 @@ class rt_gbuffer_motion(ctypes.Structure):
                 ("object", ctypes.c_void_p), ("motion", ctypes.c_void_p)]
 
 
+class rt_ao_params(ctypes.Structure):
+    """include/rt_api.h rt_ao_params: samples (1..64), seed, radius (the rays' tmax), tmin of rt_dispatch_ao."""
+    _fields_ = [("samples", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("radius", ctypes.c_float),
+                ("tmin", ctypes.c_float)]
+
+
 class rt_manipulator(ctypes.Structure):
     """include/rt_api.h rt_manipulator: nv_helpers_dx12::Manipulator state (manipulator.h:124-144)."""
     _fields_ = [("pos", ctypes.c_float * 3), ("interest", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
@@ -128,6 +134,7 @@ SIGNATURES = [
     ("rt_dispatch_gbuffer", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer), _P]),
     ("rt_set_motion_history", _I, [_P, _I]),
     ("rt_dispatch_gbuffer_motion", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer_motion), _FP, _P]),
+    ("rt_dispatch_ao", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
     ("rt_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _P]),
     ("rt_raster_draw", _I, [_P, _UP, _U32, _FP, _U32, _U32, _P, _P, _P]),
     ("rt_assemble_strips", _I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P]),
@@ -171,6 +178,7 @@ SIGNATURES = [
     ("rt_host_shading_normals", _I, [_P, _U32, _U32, _P, _U32, _P, _U32, _P, _P, _U32, _P]),
     ("rt_host_motion_project", _I, [_P, _P, _U32, _P, _P, _U32, _U32, _P]),
     ("rt_host_motion_vectors", _I, [_P, _P, _U32, _U32, _P, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
+    ("rt_host_ao_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
     ("rt_manip_init", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_update", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_set_lookat", None, [ctypes.POINTER(rt_manipulator), _FP, _FP, _FP]),
@@ -406,6 +414,30 @@ def host_motion_vectors(vertices, indices, prims, uv, camera, width: int, height
     if st != RT_OK:
         raise RtError(st, "rt_host_motion_vectors")
     return out
+
+
+def host_ao_rays(cam_rays, t, normal, px, py, samples: int, radius: float, tmin: float = 0.01, seed: int = 0):
+    """rt_host_ao_rays: the rays rt_dispatch_ao traces, on the host (no GPU). cam_rays: (n, 8) camera rays in
+    trace_rays' layout; t: n hit distances; normal: (n, 4) G-buffer normals; px, py: the pixels' global coordinates.
+    Returns (rays, valid): (n, samples, 8) float32 (P, tmin, d, radius) and (n,) uint8; a pixel whose normal is not
+    valid has zero rays and valid 0."""
+    cr = np.ascontiguousarray(cam_rays, dtype=np.float32).reshape(-1, 8)
+    n = cr.shape[0]
+    tt = _f32(t, n)
+    nr = _f32(normal, 4 * n)
+    x = np.ascontiguousarray(px, dtype=np.uint32).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if x.size != n or y.size != n:
+        raise ValueError(f"expected {n} pixel coordinates, got {x.size} and {y.size}")
+    if not 1 <= int(samples) <= 64:  # rt_host_ao_rays' own limit, checked before the output is sized by it
+        raise RtError(RT_E_INVALID, f"rt_host_ao_rays: samples {samples} outside 1..64")
+    p = rt_ao_params(samples, seed, radius, tmin)
+    rays = np.zeros((n, int(samples), 8), np.float32)
+    valid = np.zeros(n, np.uint8)
+    st = lib.rt_host_ao_rays(_vp(cr), _vp(tt), _vp(nr), _vp(x), _vp(y), n, ctypes.byref(p), _vp(rays), _vp(valid))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_ao_rays")
+    return rays, valid
 
 
 class Manipulator:
@@ -949,6 +981,21 @@ class Context:
         self._check(self._lib.rt_dispatch_gbuffer_motion(self._h, width, height, rp, nr, ctypes.byref(g),
                                                          None if pcb is None else _fptr(pcb), stream),
                     "rt_dispatch_gbuffer_motion")
+
+    def dispatch_ao(self, width: int, height: int, ao, samples: int, radius: float, tmin: float = 0.01, seed: int = 0,
+                    rows: Optional[np.ndarray] = None, stream: Optional[int] = None):
+        """rt_dispatch_ao: ambient occlusion of the frame dispatch_gbuffer describes, one float per pixel (nrows *
+        width entries in dispatch()'s compact row order; a device tensor or a raw address): the share of `samples`
+        (1..64) cosine-weighted rays from the primary hit over [tmin, radius] that hit nothing; 1.0 on a miss. The
+        same seed gives the same plane bit for bit; host_ao_rays gives the rays."""
+        rp, nr, _keep = self._rows_arg(rows, height)
+        if ao is not None and not isinstance(ao, int):
+            if ao.element_size() != 4 or ao.numel() != nr * width or not ao.is_contiguous():
+                raise ValueError(f"dispatch_ao: ao must be a contiguous tensor of {nr * width} 32-bit elements, got "
+                                 f"{ao.numel()} of {ao.element_size()} bytes")
+        p = rt_ao_params(samples, seed, radius, tmin)
+        self._check(self._lib.rt_dispatch_ao(self._h, width, height, rp, nr, ctypes.byref(p), _ptr(ao), stream),
+                    "rt_dispatch_ao")
 
     def pick(self, width: int, height: int, x: int, y: int) -> Optional[dict]:
         """What the camera ray through the centre of pixel (x, y) of a width x height frame hits: None on a miss, else

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <functional>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -1942,6 +1943,49 @@ static void motion_cams(const float* cb, const float* prev_cb, rt::MotionCams& m
   std::memcpy(m.prev_proj, pcb + 16, sizeof(m.prev_proj));
 }
 
+// What every pass on the G-buffer's pixel grid (rt_dispatch_gbuffer, rt_dispatch_gbuffer_motion, rt_dispatch_ao) checks
+// after its own outputs: the size, the row list (*nrows becomes H without one), a traceable scene, a camera.
+static rt_status grid_pass_check(rt_ctx* c, const std::string& fn, uint32_t W, uint32_t H, const uint32_t* rows,
+                                 uint32_t* nrows) {
+  if (W == 0 || H == 0) return fail(c, RT_E_INVALID, fn + ": bad size");
+  rt_status st = check_rows(c, fn.c_str(), H, rows, nrows);
+  if (st != RT_OK || (st = check_scene_ready(c, fn.c_str())) != RT_OK) return st;
+  if (!c->have_camera) return fail(c, RT_E_INVALID, fn + ": camera not set");
+  return RT_OK;
+}
+
+// ... and what every such pass does once its checks are through: the pixel-count limit, the camera and the frame size
+// into gb (the launch's GbufParams: its planes are the caller's business), the row list's and the overflow stack's
+// slots, launch(scene view, device rows, stream) -> hipError_t, the launch record and the host-side counters.
+using GridLaunch = std::function<hipError_t(const rt::SceneView&, const uint32_t*, hipStream_t)>;
+static rt_status grid_pass_launch(rt_ctx* c, const std::string& fn, uint32_t W, uint32_t H, const uint32_t* rows,
+                                  uint32_t nrows, void* stream, rt::GbufParams& gb, const char* what,
+                                  const GridLaunch& launch) {
+  // the kernels index a plane's entries with 32 bits, as the frame kernels index their pixels
+  if ((uint64_t)nrows * W >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, fn + ": more than 2^32 pixels");
+  (void)hipSetDevice(c->device);
+  TraceLaunch L{c, fn.c_str(), pick_stream(c, stream)};
+  rt_status st = L.open();
+  if (st != RT_OK) return st;
+  rt::frame_cam(c->cam_cb, gb.cam);
+  gb.width = W;
+  gb.nrows = nrows;
+  gb.fwidth = (float)W;  // exact: W, H < 2^24
+  gb.fheight = (float)H;
+  const uint32_t* d_rows = nullptr;
+  uint64_t rows_gen = 0;
+  if ((st = L.take_rows(rows, nrows, &d_rows, &rows_gen)) != RT_OK) return st;
+  // the per-lane kernel's overflow stack: 16 x 16 pixel workgroups
+  const size_t lanes = rt::gbuffer_packet(L.sv, c->schedule) ? 0 : (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256;
+  if ((st = L.take_overflow_and_order(lanes)) != RT_OK) return st;
+  if ((st = L.finish(launch(L.sv, d_rows, L.s), what)) != RT_OK) return st;
+  if (c->stats_on) {
+    c->dispatches += 1;
+    c->pixels += (uint64_t)W * nrows;
+  }
+  return RT_OK;
+}
+
 // rt_dispatch_gbuffer (fn names it in the messages; out.motion null, the four-plane kernels) and
 // rt_dispatch_gbuffer_motion (the motion kernels: the same four planes and out.motion, which may be null too).
 static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion_kernels, uint32_t W, uint32_t H,
@@ -1952,26 +1996,14 @@ static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion
   if (((uintptr_t)out.hits | (uintptr_t)out.normal) % 16u || ((uintptr_t)out.uv | (uintptr_t)out.object) % 8u)
     return fail(c, RT_E_INVALID, fn + ": output plane not aligned (hits, normal: 16 bytes; uv, object: 8)");
   if ((uintptr_t)out.motion % 16u) return fail(c, RT_E_INVALID, fn + ": motion plane not aligned to 16 bytes");
-  if (W == 0 || H == 0) return fail(c, RT_E_INVALID, fn + ": bad size");
-  rt_status st = check_rows(c, fn.c_str(), H, rows, &nrows);
-  if (st != RT_OK || (st = check_scene_ready(c, fn.c_str())) != RT_OK) return st;
-  if (!c->have_camera) return fail(c, RT_E_INVALID, fn + ": camera not set");
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  if (st != RT_OK) return st;
   if (out.motion && !c->motion_on)
     return fail(c, RT_E_INVALID, fn + ": motion plane asked for, but motion history is off (rt_set_motion_history)");
   if (out.motion && !c->ver[c->cur].motion)
     return fail(c, RT_E_INVALID, fn + ": the current TLAS was built before motion history was switched on");
-  // the kernels index a plane's entries with 32 bits, as the frame kernels index their pixels
-  if ((uint64_t)nrows * W >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, fn + ": more than 2^32 pixels");
-  (void)hipSetDevice(c->device);
-  TraceLaunch L{c, fn.c_str(), pick_stream(c, stream)};
-  if ((st = L.open()) != RT_OK) return st;
   rt::GbufMotionParams mp;
   rt::GbufParams& gb = mp.gb;
-  rt::frame_cam(c->cam_cb, gb.cam);
-  gb.width = W;
-  gb.nrows = nrows;
-  gb.fwidth = (float)W;  // exact: W, H < 2^24
-  gb.fheight = (float)H;
   gb.hits = out.hits;
   gb.uv = out.uv;
   gb.normal = out.normal;
@@ -1979,22 +2011,12 @@ static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion
   motion_cams(c->cam_cb, prev_cb, mp.cams);
   mp.motion = out.motion;
   mp.recs = c->ver[c->cur].motion;
-  const uint32_t* d_rows = nullptr;
-  uint64_t rows_gen = 0;
-  if ((st = L.take_rows(rows, nrows, &d_rows, &rows_gen)) != RT_OK) return st;
-  // the per-lane kernel's overflow stack: 16 x 16 pixel workgroups
-  const size_t lanes = rt::gbuffer_packet(L.sv, c->schedule) ? 0 : (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256;
-  if ((st = L.take_overflow_and_order(lanes)) != RT_OK) return st;
-  st = L.finish(motion_kernels
-                    ? rt::launch_trace_gbuffer(L.sv, mp, d_rows, c->d_stats, c->stats_on, c->schedule, L.s)
-                    : rt::launch_trace_gbuffer(L.sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, L.s),
-                "G-buffer launch");
-  if (st != RT_OK) return st;
-  if (c->stats_on) {
-    c->dispatches += 1;
-    c->pixels += (uint64_t)W * nrows;
-  }
-  return RT_OK;
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, gb, "G-buffer launch",
+                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
+                            return motion_kernels
+                                       ? rt::launch_trace_gbuffer(sv, mp, d_rows, c->d_stats, c->stats_on, c->schedule, s)
+                                       : rt::launch_trace_gbuffer(sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, s);
+                          });
 }
 
 rt_status rt_dispatch_gbuffer(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
@@ -2010,6 +2032,38 @@ rt_status rt_dispatch_gbuffer_motion(rt_ctx_t c, uint32_t W, uint32_t H, const u
   if (!c) return RT_E_INVALID;
   if (!out) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer_motion: null output structure");
   return gbuffer_dispatch(c, "rt_dispatch_gbuffer_motion", true, W, H, rows, nrows, *out, prev_cb, stream);
+}
+
+// What is wrong with an rt_ao_params, or null (rt_dispatch_ao and rt_host_ao_rays check alike).
+static const char* ao_params_error(const rt_ao_params* p) {
+  if (!p) return "null params";
+  if (p->samples < 1 || p->samples > 64) return "samples outside 1..64";
+  if (!std::isfinite(p->radius) || !(p->radius > 0.0f)) return "radius not finite and > 0";
+  if (!std::isfinite(p->tmin) || !(p->tmin >= 0.0f)) return "tmin not finite and >= 0";
+  if (!(p->tmin < p->radius)) return "tmin not below radius";
+  return nullptr;
+}
+
+// The G-buffer passes' shared checks and launch sequence (grid_pass_check, grid_pass_launch) around the AO kernels.
+rt_status rt_dispatch_ao(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                         const rt_ao_params* params, float* ao_dev, void* stream) {
+  if (!c) return RT_E_INVALID;
+  const std::string fn = "rt_dispatch_ao";
+  if (const char* why = ao_params_error(params)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (!ao_dev) return fail(c, RT_E_INVALID, fn + ": null output plane");
+  if ((uintptr_t)ao_dev % 4u) return fail(c, RT_E_INVALID, fn + ": output plane not aligned to 4 bytes");
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  if (st != RT_OK) return st;
+  rt::AoParams ap = {};
+  ap.samples = params->samples;
+  ap.seed = params->seed;
+  ap.radius = params->radius;
+  ap.tmin = params->tmin;
+  ap.ao = ao_dev;
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, ap.gb, "AO launch",
+                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
+                            return rt::launch_trace_ao(sv, ap, d_rows, c->d_stats, c->stats_on, c->schedule, s);
+                          });
 }
 
 rt_status rt_set_motion_history(rt_ctx_t c, int enable) {
@@ -2238,6 +2292,37 @@ rt_status rt_host_motion_vectors(const void* vtx, const void* prev_vtx, uint32_t
     rt::V3 oc, op;
     rt::motion_object_points(v, pv, vstride, idx, prims[i], uv[2 * (size_t)i], uv[2 * (size_t)i + 1], oc, op);
     rt::motion_entry(cams, rt::xform_point(m, oc), rt::xform_point(pm, op), (float)W, (float)H, out + 4 * (size_t)i);
+  }
+  return RT_OK;
+}
+
+// Host service: the rays rt_dispatch_ao traces for n pixels, from the sample generator of rt_device.hpp the AO kernels
+// call, in the kernels' order of operations. Here for rt_host_shading_normals' reason. No context, no GPU call.
+rt_status rt_host_ao_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
+                          const uint32_t* py, uint32_t n, const rt_ao_params* params, float* rays_out,
+                          uint8_t* valid_out) {
+  if (ao_params_error(params) || (n && (!cam_rays || !t || !normal || !px || !py || !rays_out))) return RT_E_INVALID;
+  const uint32_t S = params->samples;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* cr = cam_rays + 8 * (size_t)i;
+    const float* nr = normal + 4 * (size_t)i;
+    float* out = rays_out + 8 * (size_t)i * S;
+    const rt::V3 O = rt::v3(cr[0], cr[1], cr[2]), D = rt::v3(cr[4], cr[5], cr[6]), nv = rt::v3(nr[0], nr[1], nr[2]);
+    const bool valid = rt::ao_normal_valid(nv);
+    if (valid_out) valid_out[i] = valid ? 1 : 0;
+    if (!valid) {
+      std::memset(out, 0, sizeof(float) * 8 * (size_t)S);
+      continue;
+    }
+    const rt::V3 nf = rt::ao_facing_normal(nv, D);
+    const rt::V3 P = rt::add(O, rt::muls(D, t[i]));
+    const uint32_t base = rt::ao_base(px[i], py[i], params->seed);
+    for (uint32_t k = 0; k < S; ++k) {
+      const rt::V3 d = rt::ao_direction(nf, rt::ao_sphere(base, k));
+      float* r = out + 8 * (size_t)k;
+      r[0] = P.x, r[1] = P.y, r[2] = P.z, r[3] = params->tmin;
+      r[4] = d.x, r[5] = d.y, r[6] = d.z, r[7] = params->radius;
+    }
   }
   return RT_OK;
 }

@@ -267,6 +267,16 @@ struct GbufMotionParams {
   const MotionRec* recs;
 };
 
+// rt_dispatch_ao: the G-buffer launch's camera and frame size (gb's planes stay null: the pass stores none of them),
+// rt_ao_params' four values as checked by the entry point, and the output plane (one float per pixel, entry
+// orow * width + x as for a G-buffer plane).
+struct AoParams {
+  GbufParams gb;
+  uint32_t samples, seed;
+  float radius, tmin;
+  float* ao;
+};
+
 // Tile-balance split codes (FrameParams::plan): parts per tile. The costliest quadrant of the costliest C4 tiles
 // takes 0.55 of the whole packet's fetches, the costliest 2 x 2 cell 0.35 (tools/split_study.py): the kernel's
 // estimate of a whole tile from one part's time, and the plan's estimate of a part from the whole.
@@ -810,6 +820,83 @@ RT_HD void motion_entry(const MotionCams& cams, V3 cur, V3 prev, float fwidth, f
   out[1] = behind ? __builtin_inff() : yp - yc;
   out[2] = wp;
   out[3] = wc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Ambient occlusion (rt_dispatch_ao): the sample generator, called by the AO kernels per lane and by
+// rt_host_ao_rays per pixel. float32, no contraction, only + - * / sqrt, comparisons, floorf and integer operations
+// (det_log2's rule), so the device and the host agree to the bit; tests/ao_reference.py restates it in numpy.
+// ------------------------------------------------------------------------------------------
+
+// PCG's RXS-M-XS output function over one LCG step, uint32 (wrapping)
+RT_HD uint32_t ao_hash(uint32_t v) {
+  v = v * 747796405u + 2891336453u;
+  const uint32_t w = ((v >> ((v >> 28) + 4u)) ^ v) * 277803737u;
+  return (w >> 22) ^ w;
+}
+// The hash base of a pixel: px, py are the frame's GLOBAL pixel coordinates (py = rows[r], not the compact row), so a
+// row-list launch draws the samples the full frame draws.
+RT_HD uint32_t ao_base(uint32_t px, uint32_t py, uint32_t seed) { return ao_hash(px + ao_hash(py + ao_hash(seed))); }
+
+// (cos, sin) of 2 pi u for u in [0, 1). q = floorf(4u + 0.5f) is the nearest quadrant boundary, f = u - 0.25 q is exact
+// (both are multiples of 2^-24 of nearby magnitude) with |2 pi f| <= pi / 4 (+ one rounding of 4u + 0.5), where the
+// Taylor polynomials of degree 9 (sin) and 8 (cos) truncate at 1.8e-9 and 2.5e-8; the rest of the error is rounding.
+// The coefficients are 1 / k! rounded to float32, and 2 pi likewise: pinned here, restated by the tests. Max absolute
+// error against float64 over all 2^24 inputs u = k 2^-24: 9.304034753743196e-08 (measured on the CPU, asserted by
+// tests/test_ao_host.py).
+RT_HD void det_sincos_2pi(float u, float& c, float& s) {
+  const float q = floorf(4.0f * u + 0.5f);
+  const float f = u - 0.25f * q;
+  const float x = 6.2831855f * f;
+  const float x2 = x * x;
+  float ps = 2.7557319e-06f;
+  ps = ps * x2 + -0.0001984127f;
+  ps = ps * x2 + 0.008333334f;
+  ps = ps * x2 + -0.16666667f;
+  ps = ps * x2 + 1.0f;
+  const float sn = x * ps;
+  float pc = 2.4801588e-05f;
+  pc = pc * x2 + -0.0013888889f;
+  pc = pc * x2 + 0.041666668f;
+  pc = pc * x2 + -0.5f;
+  const float cs = pc * x2 + 1.0f;
+  const uint32_t k = (uint32_t)(int)q & 3u;  // q in 0 .. 4: rotate by k quarter turns
+  c = k == 0u ? cs : k == 1u ? -sn : k == 2u ? -cs : sn;
+  s = k == 0u ? sn : k == 1u ? cs : k == 2u ? -sn : -cs;
+}
+
+// Sample k of the pixel with hash base `base`: a point uniform on the unit sphere (z uniform in (-1, 1], the angle
+// uniform), from two 24-bit uniforms.
+RT_HD V3 ao_sphere(uint32_t base, uint32_t k) {
+  const uint32_t a = ao_hash(base + 2u * k), b = ao_hash(base + 2u * k + 1u);
+  const float u1 = (float)(a >> 8) * 5.9604644775390625e-08f;  // 2^-24: exact
+  const float u2 = (float)(b >> 8) * 5.9604644775390625e-08f;
+  const float z = 1.0f - 2.0f * u1;
+  const float r = sqrtf(maxf(0.0f, 1.0f - z * z));
+  float c, s;
+  det_sincos_2pi(u2, c, s);
+  return v3(r * c, r * s, z);
+}
+
+// Whether the G-buffer normal n can orient a hemisphere: every component finite, dot(n, n) finite and > 0.
+RT_HD bool ao_normal_valid(V3 n) {
+  const float big = 3.402823466e+38f;
+  const float d = dot(n, n);
+  return fabsf(n.x) <= big && fabsf(n.y) <= big && fabsf(n.z) <= big && d <= big && d > 0.0f;
+}
+
+// The unit normal on the viewer's side of the surface: the plane group's G-buffer normal is not unit length, the model
+// group's is un-negated (it points along the camera ray D on a front face).
+RT_HD V3 ao_facing_normal(V3 n, V3 D) {
+  const V3 nn = normalize(n);
+  return dot(nn, D) > 0.0f ? neg(nn) : nn;
+}
+
+// Cosine-weighted direction about the unit normal nf from a uniform sphere point: normalize(nf + sph); the antipodal
+// point (|nf + sph| < 1e-2) falls back to nf.
+RT_HD V3 ao_direction(V3 nf, V3 sph) {
+  const V3 v = add(nf, sph);
+  return dot(v, v) < 1e-4f ? nf : normalize(v);
 }
 
 }  // namespace rt

@@ -194,6 +194,10 @@ bool gbuffer_packet(const SceneView& scene, int schedule);
 template <typename P>
 hipError_t launch_trace_gbuffer(const SceneView& scene, const P& params, const uint32_t* d_rows,
                                 unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
+// The ambient-occlusion pass (rt_dispatch_ao): launch_trace_gbuffer's schedule rule (gbuffer_packet) and grids on
+// the AO kernels; params.ao is written, params.gb's planes are not read.
+hipError_t launch_trace_ao(const SceneView& scene, const AoParams& params, const uint32_t* d_rows,
+                           unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
 
 // rank_stride_rows: rows from one rank's block of `gathered` to the next (0: rows_per_rank, one frame per block;
 // a batched gather holds several frames per rank block and passes their total)

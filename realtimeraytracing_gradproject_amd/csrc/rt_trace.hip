@@ -1886,6 +1886,123 @@ __global__ __launch_bounds__(kBlock) void k_trace_gbuffer(SceneView sc, P p, con
   if (STATS) flush_stats<false>(cnt, stats);
 }
 
+// ------------------------------------------------------------------------------------------
+// Ambient-occlusion pass (rt_dispatch_ao): the G-buffer kernels' launch shapes and camera ray
+// (gbuffer_ray), the G-buffer's normal (ao_normal: gbuffer_store's two calls, so the normal plane's bits), then S
+// cosine-weighted any-hit rays per pixel from the frame's hit point over [tmin, radius] (rt_device.hpp's sample
+// generator, shared with rt_host_ao_rays) and one float per pixel: the share of them that hit nothing. A miss, or a
+// hit whose normal cannot orient a hemisphere, is 1.0f with no rays traced. No reference counterpart (Hit.hlsl:165:
+// "Constant ambient light for now").
+// ------------------------------------------------------------------------------------------
+
+// The hit's normal as gbuffer_store computes it for the normal plane.
+__device__ __forceinline__ V3 ao_normal(const SceneView& sc, const HitRec& hit) {
+  const HitInstance ir = load_hit_instance(sc, hit.inst);
+  return ir.hit_group == 2u ? face_world_normal(ir, hit.prim) : interpolated_world_normal(ir, hit.prim, hit.u, hit.v);
+}
+
+// The packet kernel's SGPR budget: the plain kernels' cap (8 waves per SIMD; the two walks' uniform state then spills
+// 12 - 34 SGPRs to VGPR lanes, none to scratch), or with RT_AO_PLAIN_SGPRS=0 the compiler's own; DESIGN §3.9 has the
+// A/B of the two builds.
+#ifndef RT_AO_PLAIN_SGPRS
+#define RT_AO_PLAIN_SGPRS 1
+#endif
+#if RT_AO_PLAIN_SGPRS
+#define RT_AO_SGPR_ATTR RT_PLAIN_SGPR_ATTR
+#else
+#define RT_AO_SGPR_ATTR
+#endif
+
+// Packet schedule: gbuffer_packet_body's layout (a wave = an 8 x 8 pixel tile on the plain grid) and its closest-hit
+// walk, then a wave-uniform loop over the samples: every lane generates its ray k and the wave walks the 64 of them
+// as one any-hit packet; lanes that missed, or whose normal is invalid, join every packet dead (a wave with no live
+// lane skips the loop). One 4-B store per lane: an 8-pixel tile row is 32 contiguous bytes.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_AO_SGPR_ATTR
+void k_trace_ao_packet(SceneView sc, AoParams ap, const uint32_t* __restrict__ rows,
+                       unsigned long long* __restrict__ stats) {
+  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
+  const GbufParams& gb = ap.gb;
+  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
+  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
+  const bool inimg = x < gb.width && orow < gb.nrows;
+  uint32_t py = 0;
+  if (inimg) py = rows ? rows[orow] : orow;
+  V3 O, D;
+  gbuffer_ray(gb, x, py, O, D);
+  Counters cnt;
+  if (STATS && inimg) ++cnt.primary;
+  HitRec hit;
+  bool found;
+  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  bool need = false;
+  V3 nf = v3(0.0f, 0.0f, 1.0f), P = O;  // a dead lane's ray: finite, never traced
+  if (inimg && found) {
+    const V3 n = ao_normal(sc, hit);
+    if (ao_normal_valid(n)) {
+      need = true;
+      nf = ao_facing_normal(n, D);
+      P = add(O, muls(D, hit.t));  // GetWorldHitPoint, the frame's expression
+    }
+  }
+  const uint32_t base = ao_base(x, py, ap.seed);
+  const uint32_t ns = wave_ballot(need) ? ap.samples : 0u;  // uniform
+  uint32_t clear = 0;
+  for (uint32_t k = 0; k < ns; ++k) {
+    V3 d = ao_direction(nf, ao_sphere(base, k));
+    if (STATS && need) ++cnt.shadow;
+    HitRec h;
+    bool occ;
+    trace_packet<true, STATS, 1, false, TT>(sc, &P, &d, ap.tmin, ap.radius, &need, &occ, &h, cnt);
+    clear += need && !occ ? 1u : 0u;
+  }
+  if (inimg) ap.ao[orow * gb.width + x] = need ? (float)clear / (float)ap.samples : 1.0f;  // < 2^32 pixels (rt_api.cpp)
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_gbuffer's indexing, LDS stack
+// and per-launch HBM overflow; each lane loops over its own samples.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_ao(SceneView sc, AoParams ap, const uint32_t* __restrict__ rows,
+                                                     unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const GbufParams& gb = ap.gb;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  Counters cnt;
+  if (px < gb.width && orow < gb.nrows) {
+    const uint32_t py = rows ? rows[orow] : orow;
+    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+    V3 O, D;
+    gbuffer_ray(gb, px, py, O, D);
+    HitRec hit;
+    if (STATS) ++cnt.primary;
+    float ao = 1.0f;
+    if (trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt)) {
+      const V3 n = ao_normal(sc, hit);
+      if (ao_normal_valid(n)) {
+        const V3 nf = ao_facing_normal(n, D);
+        const V3 P = add(O, muls(D, hit.t));
+        const uint32_t base = ao_base(px, py, ap.seed);
+        uint32_t clear = 0;
+        for (uint32_t k = 0; k < ap.samples; ++k) {
+          const V3 d = ao_direction(nf, ao_sphere(base, k));
+          if (STATS) ++cnt.shadow;
+          HitRec h;
+          clear += trace<true, STATS, false, TT>(sc, P, d, ap.tmin, ap.radius, h, stk, cnt) ? 0u : 1u;
+        }
+        ao = (float)clear / (float)ap.samples;
+      }
+    }
+    ap.ao[orow * gb.width + px] = ao;
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
 // Un-interleaves the gathered strips (rank-major blocks; rank k holds strips s % nranks == k) into the RGBA8 frame.
 // in_bpp 3: the strips are RGB8 and the constant alpha 255 is restored here (RayGen.hlsl:42 writes float4(c, 1)).
 __global__ void k_assemble(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
@@ -2540,6 +2657,25 @@ template hipError_t launch_trace_gbuffer(const SceneView&, const GbufParams&, co
                                          int, hipStream_t);
 template hipError_t launch_trace_gbuffer(const SceneView&, const GbufMotionParams&, const uint32_t*, unsigned long long*,
                                          bool, int, hipStream_t);
+
+// The AO pass: launch_trace_gbuffer's schedule rule, grids and compile-time choices, on the AO kernels.
+hipError_t launch_trace_ao(const SceneView& sc, const AoParams& ap, const uint32_t* d_rows, unsigned long long* d_stats,
+                           bool stats, int schedule, hipStream_t s) {
+  const bool packet = gbuffer_packet(sc, schedule);
+  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
+  const dim3 grid((ap.gb.width + tw - 1) / tw, (ap.gb.nrows + th - 1) / th);
+  lift(
+      [&](auto S, auto T) {
+        if (!packet)
+          hipLaunchKernelGGL((k_trace_ao<S.value, T.value>), grid, dim3(kBlock),
+                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, ap, d_rows, d_stats);
+        else
+          hipLaunchKernelGGL((k_trace_ao_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, ap, d_rows,
+                             d_stats);
+      },
+      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
+  return hipGetLastError();
+}
 
 hipError_t launch_assemble_strips(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
                                   const void* gathered, void* out, hipStream_t s, uint32_t rank_stride_rows,
