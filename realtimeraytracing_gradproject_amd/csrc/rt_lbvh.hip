@@ -6,11 +6,11 @@
 //
 // Four schedules of the same tree (all deterministic, so oracle/rt_oracle.c rebuilds the bit-identical
 // tree; build_path() picks one, RT_BUILD_PATH forces one for A/B):
+//   n = 1             k_build_one: the single leaf's node, one thread
 //   2 <= n <= 512     k_build_tiny: one 512-thread workgroup, everything in LDS (rank sort, Apetrei
 //                     climb, DP, expansion, BFS numbering), one launch
 //   513 .. 8192       k_mid_*: rank sort, Apetrei climb with in-block LDS hand-offs, expansion, a
 //                     one-workgroup top climb + BFS numbering, parallel node writes: four launches + one
-//   n = 1             k_build_small: the multi-kernel stages in one 1024-thread workgroup
 //   larger n          the multi-kernel pipeline:
 //   1. centroid bounds      one 1024-thread workgroup, LDS min/max reduction (exact)
 //   2. Morton codes         30-bit (10 bits/axis) of box centroids
@@ -18,8 +18,8 @@
 //                           exclusive scan, stable scatter with wave64 ballot match + popcount
 //                           ranks (keys tie-break on primitive index: stable)
 //   4. Karras hierarchy     Karras 2012 over key64 = morton << 32 | leaf position
-//   5. bottom-up refit      one thread per leaf, agent-scope release/acquire arrival counters,
-//                           with the SAH collapse DP at each node
+//   5. bottom-up refit      one thread per leaf, agent-scope arrival counters behind write-through
+//                           stores, with the SAH collapse DP at each node
 //   6. pack                 64-B child-pair nodes (both child boxes per node)
 //   7. DP expansion + collapse into 4-wide BFS nodes, triangle gather into leaf order
 #include <hip/hip_runtime.h>
@@ -29,34 +29,6 @@
 #include <vector>
 
 #include "rt_internal.hpp"
-
-#ifndef RT_FUSED_BUILD
-#define RT_FUSED_BUILD 1  // n <= kFusedMax: the whole build in one workgroup (k_build_small)
-#endif
-#ifndef RT_FUSED_MAX_N
-#define RT_FUSED_MAX_N 3072  // largest n built by k_build_small (measured crossover; capacity kFusedMax)
-#endif
-#ifndef RT_TINY_BUILD
-#define RT_TINY_BUILD 1  // 2 <= n <= RT_TINY_MAX_N: the one-launch LDS build (k_build_tiny)
-#endif
-#ifndef RT_TINY_MAX_N
-#define RT_TINY_MAX_N 512  // largest n built by k_build_tiny (capacity kTinyMax)
-#endif
-#ifndef RT_MID_BUILD
-#define RT_MID_BUILD 1  // RT_MID_MIN_N <= n <= kMidMax: the five-launch build (k_mid_*)
-#endif
-#ifndef RT_MID_MIN_N
-#define RT_MID_MIN_N 2  // smallest n built by k_mid_* (measured crossover against k_build_small)
-#endif
-#ifndef RT_REFIT_WT
-#define RT_REFIT_WT 1  // multi-kernel refit: write-through hand-off instead of agent release/acquire fences
-#endif
-#ifndef RT_BUILD_TIMING
-#define RT_BUILD_TIMING 0  // 1: k_build_small prints per-phase shader-clock counts (diagnostics)
-#endif
-#ifndef RT_SAH_COLLAPSE
-#define RT_SAH_COLLAPSE 1  // SAH-optimal binary -> BVH4 collapse (DP); 0: greedy largest-area opening
-#endif
 
 namespace rt {
 namespace {
@@ -262,22 +234,14 @@ __global__ void k_karras(const uint32_t* __restrict__ keys, int n, int* __restri
   if (i == 0) parent_int[0] = -1;
 }
 
-__device__ __forceinline__ void load_box(int c, const float* __restrict__ nbox,
-                                         const float* __restrict__ primbox,
-                                         const uint32_t* __restrict__ sorted, float b[6]) {
-  const float* p = c >= 0 ? nbox + (size_t)c * 6 : primbox + (size_t)sorted[~c] * 6;
-  for (int k = 0; k < 6; ++k) b[k] = p[k];
-}
-
-// 5. bottom-up refit. The second arrival at a node computes its box. Hand-off follows the
-// agent-scope release -> counter -> acquire protocol (node boxes may be cached on other XCDs).
+// Half surface area of a box (the SAH weight), summed in a fixed order (mirrored by the oracle).
 __device__ __forceinline__ float half_area6(const float* b) {
   const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
   return (dx * dy + dy * dz) + dz * dx;
 }
 
-// SAH-optimal collapse DP at binary node `node` with box bb and children c0, c1 (>= 0: internal,
-// DP already final; < 0: a triangle / instance leaf, cost 0). The cost of a collapse is the sum of
+// SAH-optimal collapse DP at a binary node n with box bb and children c0, c1, whose DP costs are l and r
+// (an internal child's are final; a triangle / instance leaf's are 0). The cost of a collapse is the sum of
 // its wide nodes' half areas: a wide node's visit tests all four slots, and every triangle is tested
 // under the same conditions whatever the collapse. C(n, i) = least cost of n's subtree as at most i
 // slot roots: D(n, i) = min_j C(c0, j) + C(c1, i - j), C(n, 1) = A(n) + D(n, 4) (n is a wide node),
@@ -312,17 +276,6 @@ __device__ __forceinline__ void sah_dp_vals(const float* bb, float4 l, float4 r,
   out_s = S;
 }
 
-__device__ __forceinline__ void sah_dp(int node, const float* bb, int c0, int c1, float4* __restrict__ dpc,
-                                       uint32_t* __restrict__ dps) {
-  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  const float4 l = c0 >= 0 ? dpc[c0] : zero, r = c1 >= 0 ? dpc[c1] : zero;
-  float4 c;
-  uint32_t sj;
-  sah_dp_vals(bb, l, r, c, sj);
-  dpc[node] = c;
-  dps[node] = sj;
-}
-
 // Write-through hand-off (MI355X_MICROARCH.md, handoff-flag: sc1 payload -> vmcnt(0) -> flag):
 // agent-scope relaxed stores / loads are the sc1 forms, coherent across the XCDs' L2s without the
 // L2 write-back an agent-scope release fence issues at every level of the climb.
@@ -333,6 +286,7 @@ __device__ __forceinline__ void st_wt(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// 5. bottom-up refit with the collapse DP. The second arrival at a node computes its box and DP record.
 __global__ void k_refit(int n, const int* __restrict__ parent_leaf, const int* __restrict__ parent_int,
                         const int* __restrict__ child, const float* __restrict__ primbox,
                         const uint32_t* __restrict__ sorted, float* nbox, uint32_t* flags,
@@ -340,7 +294,6 @@ __global__ void k_refit(int n, const int* __restrict__ parent_leaf, const int* _
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int node = parent_leaf[i];
-#if RT_REFIT_WT
   // the node records of the climb (box, DP costs, DP choices) move by write-through stores and
   // coherent loads; a climbing thread's stores are complete (vmcnt(0)) before its arrival counts
   while (node >= 0) {
@@ -355,10 +308,8 @@ __global__ void k_refit(int n, const int* __restrict__ parent_leaf, const int* _
       if (c[k] >= 0) {
         const float* p = nbox + (size_t)c[k] * 6;
         for (int q = 0; q < 6; ++q) cb[k][q] = ld_wt(p + q);
-        if (dpc) {
-          const float* d = (const float*)(dpc + c[k]);
-          cd[k] = make_float4(ld_wt(d), ld_wt(d + 1), ld_wt(d + 2), ld_wt(d + 3));
-        }
+        const float* d = (const float*)(dpc + c[k]);
+        cd[k] = make_float4(ld_wt(d), ld_wt(d + 1), ld_wt(d + 2), ld_wt(d + 3));
       } else {
         const float* p = primbox + (size_t)sorted[~c[k]] * 6;
         for (int q = 0; q < 6; ++q) cb[k][q] = p[q];
@@ -371,41 +322,17 @@ __global__ void k_refit(int n, const int* __restrict__ parent_leaf, const int* _
     }
     float* o = nbox + (size_t)node * 6;
     for (int k = 0; k < 6; ++k) st_wt(o + k, bb[k]);
-    if (dpc) {
-      float4 dc;
-      uint32_t sj;
-      sah_dp_vals(bb, cd[0], cd[1], dc, sj);
-      float* d = (float*)(dpc + node);
-      st_wt(d, dc.x);
-      st_wt(d + 1, dc.y);
-      st_wt(d + 2, dc.z);
-      st_wt(d + 3, dc.w);
-      dps[node] = sj;  // read only by later kernels
-    }
+    float4 dc;
+    uint32_t sj;
+    sah_dp_vals(bb, cd[0], cd[1], dc, sj);
+    float* d = (float*)(dpc + node);
+    st_wt(d, dc.x);
+    st_wt(d + 1, dc.y);
+    st_wt(d + 2, dc.z);
+    st_wt(d + 3, dc.w);
+    dps[node] = sj;  // read only by later kernels
     node = parent_int[node];
   }
-#else
-  while (node >= 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    uint32_t old = __hip_atomic_fetch_add(&flags[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == 0) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    float a[6], b[6];
-    load_box(child[2 * node], nbox, primbox, sorted, a);
-    load_box(child[2 * node + 1], nbox, primbox, sorted, b);
-    float* o = nbox + (size_t)node * 6;
-    float bb[6];
-    for (int k = 0; k < 3; ++k) {
-      bb[k] = fminf(a[k], b[k]);
-      bb[3 + k] = fmaxf(a[3 + k], b[3 + k]);
-    }
-    for (int k = 0; k < 6; ++k) o[k] = bb[k];
-    if (dpc) sah_dp(node, bb, child[2 * node], child[2 * node + 1], dpc, dps);
-    node = parent_int[node];
-  }
-#endif
 }
 
 // 6. pack child-pair nodes.
@@ -417,7 +344,10 @@ __global__ void k_pack(int n, const int* __restrict__ child, const float* __rest
   BinNode nd;
   int c[2] = {child[2 * i], child[2 * i + 1]};
   float b[2][6];
-  for (int k = 0; k < 2; ++k) load_box(c[k], nbox, primbox, sorted, b[k]);
+  for (int k = 0; k < 2; ++k) {
+    const float* p = c[k] >= 0 ? nbox + (size_t)c[k] * 6 : primbox + (size_t)sorted[~c[k]] * 6;
+    for (int q = 0; q < 6; ++q) b[k][q] = p[q];
+  }
   for (int k = 0; k < 3; ++k) {
     nd.lo0[k] = b[0][k];
     nd.hi0[k] = b[0][3 + k];
@@ -432,8 +362,8 @@ __global__ void k_pack(int n, const int* __restrict__ child, const float* __rest
   nodes[i] = nd;
 }
 
-// n == 1: a root whose two children are the single leaf (tested twice; ties keep the result).
-__global__ void k_single(const float* __restrict__ primbox, bool leaf_ref_is_prim, BinNode* nodes) {
+// n == 1: a binary root with the single leaf as its first child and no second child (both boxes the leaf's).
+__device__ __forceinline__ BinNode single_root(const float* __restrict__ primbox) {
   BinNode nd;
   for (int k = 0; k < 3; ++k) {
     nd.lo0[k] = nd.lo1[k] = primbox[k];
@@ -441,131 +371,13 @@ __global__ void k_single(const float* __restrict__ primbox, bool leaf_ref_is_pri
   }
   nd.c0 = ~0;  // ~slot 0 == ~prim 0
   nd.c1 = kEmptyChild;
-  (void)leaf_ref_is_prim;
   nd.pad0 = nd.pad1 = 0;
-  nodes[0] = nd;
+  return nd;
 }
 
-// 7. collapse the binary tree into 4-wide nodes in BFS order (children chosen by gather4_dp from
-// the SAH DP of k_refit; gather4, the greedy largest-area opening, with RT_SAH_COLLAPSE=0). One
-// workgroup walks the levels; each level's new node indices come from a block-wide exclusive
-// scan of per-node internal-child counts (deterministic, no atomics), so the oracle's sequential
-// BFS yields the same array. Unused slots get kEmptyChild and the box lo = hi = +inf, which
-// every slab test rejects (min/max and near/far forms alike: t is +inf or -inf on every axis),
-// so traversal needs no per-slot validity mask.
-// It also bounds the traversal stack: a visited node pushes (count - 1) siblings, so the most a
-// root-to-node path can leave on the stack is ps[node] + count(node) - 1, ps = sum over the
-// ancestors. info[0] = node count, info[1] = levels, info[2] = that maximum.
-// Half surface area of a box (the SAH weight), summed in a fixed order (mirrored by the oracle).
-__device__ __forceinline__ float half_area(const float* b) {
-  const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
-  return (dx * dy + dy * dz) + dz * dx;
-}
-
-// Children of one 4-wide node rooted at binary node `root`: start from its two children and
-// open the internal candidate with the largest surface area (lowest slot on ties) until there
-// are four, so the wide nodes come out full and the large boxes are split first.
-__device__ __forceinline__ int gather4(const BinNode* __restrict__ bin, int root, int ref[4], float box[4][6]) {
-  const BinNode& b = bin[root];
-  ref[0] = b.c0;
-  ref[1] = b.c1;
-  for (int a = 0; a < 3; ++a) {
-    box[0][a] = b.lo0[a];
-    box[0][3 + a] = b.hi0[a];
-    box[1][a] = b.lo1[a];
-    box[1][3 + a] = b.hi1[a];
-  }
-  int cnt = 2;
-  while (cnt < 4) {
-    int best = -1;
-    float bsa = 0.0f;
-    for (int j = 0; j < cnt; ++j) {
-      if (ref[j] < 0) continue;
-      const float sa = half_area(box[j]);
-      if (best < 0 || sa > bsa) {
-        best = j;
-        bsa = sa;
-      }
-    }
-    if (best < 0) break;
-    const BinNode& g = bin[ref[best]];
-    ref[best] = g.c0;
-    ref[cnt] = g.c1;
-    for (int a = 0; a < 3; ++a) {
-      box[best][a] = g.lo0[a];
-      box[best][3 + a] = g.hi0[a];
-      box[cnt][a] = g.lo1[a];
-      box[cnt][3 + a] = g.hi1[a];
-    }
-    ++cnt;
-  }
-  return cnt;
-}
-
-// Children of the 4-wide node rooted at binary node `root` under the collapse DP: the root's four
-// slots split between its children as D(root, 4) chose, each child expanded while its choice for
-// its slot count is a split (left first; mirrors oracle gather4_dp / dp_expand).
-__device__ __forceinline__ int gather4_dp(const BinNode* __restrict__ bin, const float4* __restrict__ dpc,
-                                          const uint32_t* __restrict__ dps, int root, int ref[4], float box[4][6]) {
-  const BinNode& b = bin[root];
-  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  const float4 l = b.c0 >= 0 ? dpc[b.c0] : zero, r = b.c1 >= 0 ? dpc[b.c1] : zero;
-  const float cl[4] = {l.x, l.y, l.z, l.w}, cr[4] = {r.x, r.y, r.z, r.w};
-  int bj = 1;
-  float bc = INFINITY;
-  for (int j = 1; j < 4; ++j) {
-    const float c = cl[j - 1] + cr[4 - j - 1];
-    if (c < bc) {
-      bc = c;
-      bj = j;
-    }
-  }
-  // explicit stack of (ref, slots, box); right pushed before left so slots come out left first
-  int sref[4], sk[4];
-  float sbox[4][6];
-  int top = 0;
-  sref[top] = b.c1;
-  sk[top] = 4 - bj;
-  for (int a = 0; a < 3; ++a) {
-    sbox[top][a] = b.lo1[a];
-    sbox[top][3 + a] = b.hi1[a];
-  }
-  ++top;
-  sref[top] = b.c0;
-  sk[top] = bj;
-  for (int a = 0; a < 3; ++a) {
-    sbox[top][a] = b.lo0[a];
-    sbox[top][3 + a] = b.hi0[a];
-  }
-  ++top;
-  int cnt = 0;
-  while (top > 0) {
-    --top;
-    const int c = sref[top], k = sk[top];
-    const uint32_t j = c >= 0 ? (dps[c] >> (8 * (k - 1))) & 0xffu : 0u;
-    if (j == 0) {
-      ref[cnt] = c;
-      for (int a = 0; a < 6; ++a) box[cnt][a] = sbox[top][a];
-      ++cnt;
-      continue;
-    }
-    const BinNode& g = bin[c];
-    sref[top] = g.c1;
-    sk[top] = k - (int)j;
-    for (int a = 0; a < 3; ++a) {
-      sbox[top][a] = g.lo1[a];
-      sbox[top][3 + a] = g.hi1[a];
-    }
-    ++top;
-    sref[top] = g.c0;
-    sk[top] = (int)j;
-    for (int a = 0; a < 3; ++a) {
-      sbox[top][a] = g.lo0[a];
-      sbox[top][3 + a] = g.hi0[a];
-    }
-    ++top;
-  }
-  return cnt;
+__global__ void k_single(const float* __restrict__ primbox, bool leaf_ref_is_prim, BinNode* nodes) {
+  (void)leaf_ref_is_prim;
+  nodes[0] = single_root(primbox);
 }
 
 // BLAS nodes keep their internal children in the lowest slots (stable: ascending half area within
@@ -591,6 +403,124 @@ __device__ __forceinline__ void inner_first(int (&ref)[M], float (&box)[M][6]) {
       }
 }
 
+// Children of the 4-wide node rooted at a binary node under the collapse DP: the DP hands each child of the
+// root k of the root's four slots (left first), and a child given k > 1 slots is split as dps chose for k
+// (0: kept whole), recursively (the oracle's DP expansion is the same recursion in the same order). Held in
+// registers, no local stack: a slot is (ref, parent binary node, side), and its box is read from the parent
+// afterwards.
+struct Slots4 {
+  int ref[4], par[4], side[4];
+  int cnt;
+};
+__device__ __forceinline__ void put_slot(Slots4& s, int ref, int par, int side) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (s.cnt == q) {
+      s.ref[q] = ref;
+      s.par[q] = par;
+      s.side[q] = side;
+    }
+  ++s.cnt;
+}
+template <int K>
+__device__ __forceinline__ void expand_slots(const BinNode* __restrict__ bin, const uint32_t* __restrict__ dps, int c,
+                                             int par, int side, Slots4& s) {
+  if (K == 1 || c < 0) {
+    put_slot(s, c, par, side);
+    return;
+  }
+  const uint32_t j = (dps[c] >> (8 * (K - 1))) & 0xffu;
+  if (j == 0) {
+    put_slot(s, c, par, side);
+    return;
+  }
+  const int2 g = *reinterpret_cast<const int2*>(&bin[c].c0);
+  if (K == 2) {
+    expand_slots<1>(bin, dps, g.x, c, 0, s);
+    expand_slots<1>(bin, dps, g.y, c, 1, s);
+  } else if (j == 1) {
+    expand_slots<1>(bin, dps, g.x, c, 0, s);
+    expand_slots<(K > 2 ? K - 1 : 1)>(bin, dps, g.y, c, 1, s);
+  } else {
+    expand_slots<(K > 2 ? K - 1 : 1)>(bin, dps, g.x, c, 0, s);
+    expand_slots<1>(bin, dps, g.y, c, 1, s);
+  }
+}
+
+// The wide node rooted at binary node `root`: its slots' refs and boxes by ascending half area (stable), so
+// nearest-first ties (rays starting inside several child boxes) and the any-hit lowest-slot order visit the
+// tighter box first; unused slots get kEmptyChild; a BLAS node's internal children then move to the lowest
+// slots (inner_first). Returns the number of slots used.
+__device__ __forceinline__ int wide_slots_dp(const BinNode* __restrict__ bin, const float4* __restrict__ dpc,
+                                             const uint32_t* __restrict__ dps, int root, int (&ref)[4],
+                                             float (&box)[4][6], bool blas) {
+  const int2 rc = *reinterpret_cast<const int2*>(&bin[root].c0);
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const float4 l = rc.x >= 0 ? dpc[rc.x] : zero, r = rc.y >= 0 ? dpc[rc.y] : zero;
+  const float cl[4] = {l.x, l.y, l.z, l.w}, cr[4] = {r.x, r.y, r.z, r.w};
+  int bj = 1;
+  float bc = INFINITY;
+#pragma unroll
+  for (int j = 1; j < 4; ++j) {
+    const float c = cl[j - 1] + cr[4 - j - 1];
+    if (c < bc) {
+      bc = c;
+      bj = j;
+    }
+  }
+  Slots4 s;
+  s.cnt = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s.ref[q] = s.par[q] = s.side[q] = 0;
+  if (bj == 1) {
+    expand_slots<1>(bin, dps, rc.x, root, 0, s);
+    expand_slots<3>(bin, dps, rc.y, root, 1, s);
+  } else if (bj == 2) {
+    expand_slots<2>(bin, dps, rc.x, root, 0, s);
+    expand_slots<2>(bin, dps, rc.y, root, 1, s);
+  } else {
+    expand_slots<3>(bin, dps, rc.x, root, 0, s);
+    expand_slots<1>(bin, dps, rc.y, root, 1, s);
+  }
+  float a[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    ref[q] = s.ref[q];
+    const BinNode& pb = bin[s.par[q]];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      box[q][k] = q < s.cnt ? (s.side[q] ? pb.lo1[k] : pb.lo0[k]) : 0.0f;
+      box[q][3 + k] = q < s.cnt ? (s.side[q] ? pb.hi1[k] : pb.hi0[k]) : 0.0f;
+    }
+    a[q] = half_area6(box[q]);
+  }
+  // ascending half area, stable (an insertion sort with every comparison unrolled: once an element
+  // stops, the comparisons below it find the prefix sorted and swap nothing)
+#pragma unroll
+  for (int x = 1; x < 4; ++x)
+#pragma unroll
+    for (int y = x; y > 0; --y)
+      if (x < s.cnt && a[y] < a[y - 1]) {
+        const float ta = a[y];
+        a[y] = a[y - 1];
+        a[y - 1] = ta;
+        const int tr = ref[y];
+        ref[y] = ref[y - 1];
+        ref[y - 1] = tr;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+          const float t = box[y][q];
+          box[y][q] = box[y - 1][q];
+          box[y - 1][q] = t;
+        }
+      }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (j >= s.cnt) ref[j] = kEmptyChild;
+  if (blas) inner_first(ref, box);
+  return s.cnt;
+}
+
 // The DP expansion of every binary node, in parallel (only wide-node roots are read): k_collapse
 // then takes one record per node instead of walking dependent loads level by level.
 struct alignas(128) Exp4 {
@@ -604,30 +534,12 @@ __global__ void k_dp_expand(int nbin, const BinNode* __restrict__ bin, const flo
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nbin) return;
   Exp4 e;
-  e.cnt = gather4_dp(bin, dpc, dps, i, e.ref, e.box);
-  // slots by ascending half area (stable): nearest-first ties (rays starting inside several child
-  // boxes) and the any-hit lowest-slot order then visit the tighter box first
-  for (int a = 1; a < e.cnt; ++a)
-    for (int b = a; b > 0 && half_area6(e.box[b]) < half_area6(e.box[b - 1]); --b) {
-      const int tr = e.ref[b];
-      e.ref[b] = e.ref[b - 1];
-      e.ref[b - 1] = tr;
-      for (int q = 0; q < 6; ++q) {
-        const float t = e.box[b][q];
-        e.box[b][q] = e.box[b - 1][q];
-        e.box[b - 1][q] = t;
-      }
-    }
-  for (int j = e.cnt; j < 4; ++j) e.ref[j] = kEmptyChild;
-  if (blas) inner_first(e.ref, e.box);
+  e.cnt = wide_slots_dp(bin, dpc, dps, i, e.ref, e.box, blas);
   e.pad[0] = e.pad[1] = e.pad[2] = 0;
   exp[i] = e;
 }
 
-constexpr int kFusedThreads = 1024;
-constexpr int kFusedWaves = kFusedThreads / 64;
-constexpr uint32_t kFusedMax = 8192;  // keys + values, double-buffered in LDS: 128 KiB
-static_assert(RT_FUSED_MAX_N <= kFusedMax, "the one-workgroup build holds at most kFusedMax keys");
+constexpr int kBlockWaves = 1024 / 64;  // waves of the 1024-thread one-workgroup stages
 
 // Exclusive prefix sum of one value per thread over the workgroup, in thread order; *total gets
 // the sum. Two barriers (a wave scan by shuffles, then the 16 wave totals through LDS).
@@ -643,7 +555,7 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, u
   __syncthreads();
   uint32_t pre = 0, tot = 0;
 #pragma unroll
-  for (int k = 0; k < kFusedWaves; ++k) {
+  for (int k = 0; k < kBlockWaves; ++k) {
     const uint32_t c = s_w[k];
     pre += (uint32_t)k < w ? c : 0u;
     tot += c;
@@ -653,11 +565,18 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, u
   return pre + x - v;
 }
 
-__global__ __launch_bounds__(1024) void k_collapse(const BinNode* __restrict__ bin, const Exp4* __restrict__ exp,
-                                                   Bvh4Node* __restrict__ out,
-                                                   int* la, int* lb, int* ps, uint32_t* __restrict__ info,
-                                                   bool blas) {
-  __shared__ uint32_t s_w[kFusedWaves];
+// 7. collapse the binary tree into 4-wide nodes in BFS order (children as k_dp_expand left them, chosen
+// by the SAH DP of k_refit). One workgroup walks the levels; each level's new node indices come from
+// a block-wide exclusive scan of per-node internal-child counts (deterministic, no atomics), so the
+// oracle's sequential BFS yields the same array. Unused slots get kEmptyChild and the box lo = hi =
+// +inf, which every slab test rejects (min/max and near/far forms alike: t is +inf or -inf on every
+// axis), so traversal needs no per-slot validity mask.
+// It also bounds the traversal stack: a visited node pushes (count - 1) siblings, so the most a
+// root-to-node path can leave on the stack is ps[node] + count(node) - 1, ps = sum over the
+// ancestors. info[0] = node count, info[1] = levels, info[2] = that maximum.
+__global__ __launch_bounds__(1024) void k_collapse(const Exp4* __restrict__ exp, Bvh4Node* __restrict__ out,
+                                                   int* la, int* lb, int* ps, uint32_t* __restrict__ info) {
+  __shared__ uint32_t s_w[kBlockWaves];
   __shared__ int s_maxstack;
   const int tid = threadIdx.x;
   int* cur = la;
@@ -680,17 +599,11 @@ __global__ __launch_bounds__(1024) void k_collapse(const BinNode* __restrict__ b
       float box[4][6];
       int cnt = 0;
       if (valid) {
-        if (exp) {
-          const Exp4& e = exp[cur[i]];
-          cnt = e.cnt;
-          for (int j = 0; j < 4; ++j) {
-            ref[j] = e.ref[j];
-            for (int a = 0; a < 6; ++a) box[j][a] = e.box[j][a];
-          }
-        } else {
-          cnt = gather4(bin, cur[i], ref, box);
-          for (int j = cnt; j < 4; ++j) ref[j] = kEmptyChild;
-          if (blas) inner_first(ref, box);
+        const Exp4& e = exp[cur[i]];
+        cnt = e.cnt;
+        for (int j = 0; j < 4; ++j) {
+          ref[j] = e.ref[j];
+          for (int a = 0; a < 6; ++a) box[j][a] = e.box[j][a];
         }
       }
       uint32_t m = 0;
@@ -756,496 +669,7 @@ __global__ __launch_bounds__(1024) void k_collapse(const BinNode* __restrict__ b
 }
 
 // ------------------------------------------------------------------------------------------
-// Fused small-N build: every stage above in ONE 1024-thread workgroup (n <= kFusedMax), the
-// per-stage launches and the device-scope hand-offs replaced by workgroup barriers and LDS.
-// Same arithmetic in the same order as the multi-kernel path, so the tree is bitwise the same:
-//   bounds      the k_bounds reduction (exact min / max)
-//   morton      keys and values straight into LDS
-//   radix sort  4 x 8-bit LSD passes LDS -> LDS; each wave owns a contiguous chunk, ranks its
-//               64 keys per round with 8 ballots; one block scan of the (digit, wave) counts per
-//               pass orders digits, then waves, then rounds, then lanes: stable, like k_rs_*
-//   Karras      from the sorted keys in LDS
-//   refit + DP  the leaf-to-root climb with the arrival counters in LDS (workgroup-scope
-//               atomics: no L2 write-back per level as the agent-scope hand-off of k_refit needs)
-//   pack, DP expansion, collapse (level lists and stack sums in LDS, wave-scan prefix sums)
-//   + the triangle gather into leaf order (BLAS).
-// Teapot (6320 triangles): ~20 launches -> 1.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int delta_lds(const uint32_t* keys, int n, int i, int j) {
-  if (j < 0 || j >= n) return -1;
-  const uint64_t a = ((uint64_t)keys[i] << 32) | (uint32_t)i;
-  const uint64_t b = ((uint64_t)keys[j] << 32) | (uint32_t)j;
-  return __clzll(a ^ b);
-}
-
-// gather4_dp without a local stack (registers only: the one-workgroup build cannot hide scratch
-// latency). A slot is (ref, parent binary node, side); its box is read from the parent afterwards.
-// The expansion is the same recursion in the same left-to-right order: the DP hands a child k of
-// the root's four slots, and a child given k > 1 slots is split as dps chose (0: kept whole).
-struct Slots4 {
-  int ref[4], par[4], side[4];
-  int cnt;
-};
-__device__ __forceinline__ void put_slot(Slots4& s, int ref, int par, int side) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (s.cnt == q) {
-      s.ref[q] = ref;
-      s.par[q] = par;
-      s.side[q] = side;
-    }
-  ++s.cnt;
-}
-template <int K>
-__device__ __forceinline__ void expand_slots(const BinNode* __restrict__ bin, const uint32_t* __restrict__ dps, int c,
-                                             int par, int side, Slots4& s) {
-  if (K == 1 || c < 0) {
-    put_slot(s, c, par, side);
-    return;
-  }
-  const uint32_t j = (dps[c] >> (8 * (K - 1))) & 0xffu;
-  if (j == 0) {
-    put_slot(s, c, par, side);
-    return;
-  }
-  const int2 g = *reinterpret_cast<const int2*>(&bin[c].c0);
-  if (K == 2) {
-    expand_slots<1>(bin, dps, g.x, c, 0, s);
-    expand_slots<1>(bin, dps, g.y, c, 1, s);
-  } else if (j == 1) {
-    expand_slots<1>(bin, dps, g.x, c, 0, s);
-    expand_slots<(K > 2 ? K - 1 : 1)>(bin, dps, g.y, c, 1, s);
-  } else {
-    expand_slots<(K > 2 ? K - 1 : 1)>(bin, dps, g.x, c, 0, s);
-    expand_slots<1>(bin, dps, g.y, c, 1, s);
-  }
-}
-
-// The wide node rooted at binary node `root` (gather4_dp + the k_dp_expand slot order), in registers.
-__device__ __forceinline__ int wide_slots_dp(const BinNode* __restrict__ bin, const float4* __restrict__ dpc,
-                                             const uint32_t* __restrict__ dps, int root, int (&ref)[4],
-                                             float (&box)[4][6], bool blas) {
-  const int2 rc = *reinterpret_cast<const int2*>(&bin[root].c0);
-  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  const float4 l = rc.x >= 0 ? dpc[rc.x] : zero, r = rc.y >= 0 ? dpc[rc.y] : zero;
-  const float cl[4] = {l.x, l.y, l.z, l.w}, cr[4] = {r.x, r.y, r.z, r.w};
-  int bj = 1;
-  float bc = INFINITY;
-#pragma unroll
-  for (int j = 1; j < 4; ++j) {
-    const float c = cl[j - 1] + cr[4 - j - 1];
-    if (c < bc) {
-      bc = c;
-      bj = j;
-    }
-  }
-  Slots4 s;
-  s.cnt = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) s.ref[q] = s.par[q] = s.side[q] = 0;
-  if (bj == 1) {
-    expand_slots<1>(bin, dps, rc.x, root, 0, s);
-    expand_slots<3>(bin, dps, rc.y, root, 1, s);
-  } else if (bj == 2) {
-    expand_slots<2>(bin, dps, rc.x, root, 0, s);
-    expand_slots<2>(bin, dps, rc.y, root, 1, s);
-  } else {
-    expand_slots<3>(bin, dps, rc.x, root, 0, s);
-    expand_slots<1>(bin, dps, rc.y, root, 1, s);
-  }
-  float a[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    ref[q] = s.ref[q];
-    const BinNode& pb = bin[s.par[q]];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      box[q][k] = q < s.cnt ? (s.side[q] ? pb.lo1[k] : pb.lo0[k]) : 0.0f;
-      box[q][3 + k] = q < s.cnt ? (s.side[q] ? pb.hi1[k] : pb.hi0[k]) : 0.0f;
-    }
-    a[q] = half_area6(box[q]);
-  }
-  // ascending half area, stable (k_dp_expand's insertion sort with every comparison unrolled: once
-  // an element stops, the comparisons below it find the prefix sorted and swap nothing)
-#pragma unroll
-  for (int x = 1; x < 4; ++x)
-#pragma unroll
-    for (int y = x; y > 0; --y)
-      if (x < s.cnt && a[y] < a[y - 1]) {
-        const float ta = a[y];
-        a[y] = a[y - 1];
-        a[y - 1] = ta;
-        const int tr = ref[y];
-        ref[y] = ref[y - 1];
-        ref[y - 1] = tr;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-          const float t = box[y][q];
-          box[y][q] = box[y - 1][q];
-          box[y - 1][q] = t;
-        }
-      }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (j >= s.cnt) ref[j] = kEmptyChild;
-  if (blas) inner_first(ref, box);
-  return s.cnt;
-}
-
-__global__ __launch_bounds__(kFusedThreads) void k_build_small(
-    const float* __restrict__ primbox, uint32_t n, bool leaf_ref_is_prim, uint32_t* __restrict__ sorted,
-    float* __restrict__ cb_out, int* __restrict__ pleaf, float* nbox, float4* dpc, uint32_t* dps, BinNode* bin,
-    Bvh4Node* __restrict__ out,
-    uint32_t* __restrict__ info, const TriRec* __restrict__ tri_in, TriRec* __restrict__ tri_out) {
-  // LDS: sort buffers (keys A | values A | keys B | values B) + (digit, wave) counts; later
-  // phases reuse the same words: arrival flags (refit), level lists and stack sums (collapse)
-  __shared__ uint32_t s_mem[4 * kFusedMax + 256 * kFusedWaves];
-  __shared__ float s_red[12][kFusedWaves];
-  __shared__ float s_cb[12];
-  __shared__ uint32_t s_w[kFusedWaves];
-  __shared__ int s_maxstack;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-#if RT_BUILD_TIMING
-  uint64_t bt[9];
-  bt[0] = __builtin_amdgcn_s_memtime();
-#define RT_BT(k) bt[k] = __builtin_amdgcn_s_memtime()
-#else
-#define RT_BT(k) (void)0
-#endif
-  uint32_t* keyA = s_mem;
-  uint32_t* valA = s_mem + kFusedMax;
-  uint32_t* keyB = s_mem + 2 * kFusedMax;
-  uint32_t* valB = s_mem + 3 * kFusedMax;
-  uint32_t* cnt = s_mem + 4 * kFusedMax;  // [wave][digit]: a wave's lanes hit distinct banks
-
-  // 1. bounds (k_bounds)
-  {
-    float v[12];
-    for (int k = 0; k < 3; ++k) {
-      v[k] = INFINITY;
-      v[3 + k] = -INFINITY;
-      v[6 + k] = INFINITY;
-      v[9 + k] = -INFINITY;
-    }
-    for (uint32_t i = tid; i < n; i += kFusedThreads) {
-      const float* b = primbox + (size_t)i * 6;
-      for (int k = 0; k < 3; ++k) {
-        const float c = (b[k] + b[3 + k]) * 0.5f;
-        v[k] = fminf(v[k], c);
-        v[3 + k] = fmaxf(v[3 + k], c);
-        v[6 + k] = fminf(v[6 + k], b[k]);
-        v[9 + k] = fmaxf(v[9 + k], b[3 + k]);
-      }
-    }
-    for (int off = 32; off >= 1; off >>= 1)
-      for (int k = 0; k < 12; ++k) {
-        const float o = __shfl_xor(v[k], off, 64);
-        v[k] = (k % 6) < 3 ? fminf(v[k], o) : fmaxf(v[k], o);
-      }
-    if (lane == 0)
-      for (int k = 0; k < 12; ++k) s_red[k][w] = v[k];
-    __syncthreads();
-    if (tid < 12) {
-      const int k = (int)tid;
-      float r = s_red[k][0];
-      for (int j = 1; j < kFusedWaves; ++j) r = (k % 6) < 3 ? fminf(r, s_red[k][j]) : fmaxf(r, s_red[k][j]);
-      s_cb[k] = r;
-      cb_out[k] = r;
-    }
-    __syncthreads();
-  }
-  RT_BT(1);
-  // 2. Morton codes (k_morton)
-  for (uint32_t i = tid; i < n; i += kFusedThreads) {
-    const float* b = primbox + (size_t)i * 6;
-    uint32_t q[3];
-    for (int k = 0; k < 3; ++k) {
-      const float ext = s_cb[3 + k] - s_cb[k];
-      const float inv = ext > 0.0f ? 1.0f / ext : 0.0f;
-      const float c = (b[k] + b[3 + k]) * 0.5f;
-      q[k] = quantize10(c, s_cb[k], inv);
-    }
-    keyA[i] = (expand_bits10(q[0]) << 2) | (expand_bits10(q[1]) << 1) | expand_bits10(q[2]);
-    valA[i] = i;
-  }
-  // 3. radix sort, 4 passes: A -> B -> A -> B -> A
-  {
-    const uint32_t chunk = (((n + kFusedWaves - 1) / kFusedWaves) + 63u) & ~63u;  // keys per wave
-    const uint32_t c0 = w * chunk, c1 = min(c0 + chunk, n);
-    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64u - lane));
-    uint32_t *kin = keyA, *vin = valA, *kout = keyB, *vout = valB;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = pass * 8;
-      for (uint32_t k = tid; k < 256u * kFusedWaves; k += kFusedThreads) cnt[k] = 0;
-      __syncthreads();
-      // counts of each digit in this wave's chunk (one writer per (digit, wave): the rank-0 lane)
-      for (uint32_t b = c0; b < c1; b += 64) {
-        const uint32_t i = b + lane;
-        const bool valid = i < c1;
-        const uint32_t digit = valid ? (kin[i] >> shift) & 255u : 0u;
-        uint64_t peers = __ballot(valid);
-        for (int q = 0; q < 8; ++q) {
-          const bool bit = (digit >> q) & 1u;
-          const uint64_t m = __ballot(valid && bit);
-          peers &= bit ? m : ~m;
-        }
-        if (valid && (peers & lt) == 0) cnt[w * 256u + digit] += (uint32_t)__popcll(peers);
-      }
-      __syncthreads();
-      // exclusive scan over (digit, wave): 4 consecutive entries per thread
-      {
-        uint32_t e[4], s = 0;
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t si = tid * 4 + q;  // scan order: digit-major, wave-minor
-          e[q] = cnt[(si % kFusedWaves) * 256u + si / kFusedWaves];
-          s += e[q];
-        }
-        uint32_t tot;
-        uint32_t run = block_excl_scan(s, s_w, &tot);
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t si = tid * 4 + q;
-          cnt[(si % kFusedWaves) * 256u + si / kFusedWaves] = run;
-          run += e[q];
-        }
-      }
-      __syncthreads();
-      // stable scatter: the wave's rounds in order, lanes in order within a round
-      for (uint32_t b = c0; b < c1; b += 64) {
-        const uint32_t i = b + lane;
-        const bool valid = i < c1;
-        const uint32_t key = valid ? kin[i] : 0u, val = valid ? vin[i] : 0u;
-        const uint32_t digit = (key >> shift) & 255u;
-        uint64_t peers = __ballot(valid);
-        for (int q = 0; q < 8; ++q) {
-          const bool bit = (digit >> q) & 1u;
-          const uint64_t m = __ballot(valid && bit);
-          peers &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & lt);
-        const uint32_t base = valid ? cnt[w * 256u + digit] : 0u;  // every lane reads before the update
-        if (valid) {
-          kout[base + rank] = key;
-          vout[base + rank] = val;
-        }
-        if (valid && rank == 0) cnt[w * 256u + digit] = base + (uint32_t)__popcll(peers);
-      }
-      __syncthreads();
-      uint32_t* t = kin;
-      kin = kout;
-      kout = t;
-      t = vin;
-      vin = vout;
-      vout = t;
-    }
-  }
-  RT_BT(2);
-  // sorted permutation (values A) out; Karras from keys A
-  for (uint32_t i = tid; i < n; i += kFusedThreads) sorted[i] = valA[i];
-  __syncthreads();  // values A and buffers B take the hierarchy: parents of internal nodes, children
-  int* s_pint = (int*)s_mem + kFusedMax;
-  int* s_child = (int*)s_mem + 2 * kFusedMax;
-  if (n == 1) {
-    if (tid == 0) {  // k_single
-      BinNode nd;
-      for (int k = 0; k < 3; ++k) {
-        nd.lo0[k] = nd.lo1[k] = primbox[k];
-        nd.hi0[k] = nd.hi1[k] = primbox[3 + k];
-      }
-      nd.c0 = ~0;
-      nd.c1 = kEmptyChild;
-      nd.pad0 = nd.pad1 = 0;
-      bin[0] = nd;
-    }
-  } else {
-    // 4. Karras (k_karras)
-    for (int i = (int)tid; i < (int)n - 1; i += kFusedThreads) {
-      const int nn = (int)n;
-      const int d = (delta_lds(keyA, nn, i, i + 1) - delta_lds(keyA, nn, i, i - 1)) >= 0 ? 1 : -1;
-      const int dmin = delta_lds(keyA, nn, i, i - d);
-      int lmax = 2;
-      while (delta_lds(keyA, nn, i, i + lmax * d) > dmin) lmax <<= 1;
-      int l = 0;
-      for (int t = lmax >> 1; t >= 1; t >>= 1)
-        if (delta_lds(keyA, nn, i, i + (l + t) * d) > dmin) l += t;
-      const int j = i + l * d;
-      const int dnode = delta_lds(keyA, nn, i, j);
-      int s = 0, t = l;
-      while (true) {
-        t = (t + 1) >> 1;
-        if (delta_lds(keyA, nn, i, i + (s + t) * d) > dnode) s += t;
-        if (t <= 1) break;
-      }
-      const int gamma = i + s * d + (d < 0 ? d : 0);
-      const int lo = i < j ? i : j, hi = i < j ? j : i;
-      const int left = (lo == gamma) ? ~gamma : gamma;
-      const int right = (hi == gamma + 1) ? ~(gamma + 1) : gamma + 1;
-      s_child[2 * i] = left;
-      s_child[2 * i + 1] = right;
-      if (left >= 0) s_pint[left] = i; else pleaf[~left] = i;
-      if (right >= 0) s_pint[right] = i; else pleaf[~right] = i;
-      if (i == 0) s_pint[0] = -1;
-    }
-  RT_BT(3);
-    __syncthreads();  // keys no longer needed: the arrival flags take their words
-    uint32_t* flags = s_mem;
-    for (uint32_t i = tid; i < n - 1; i += kFusedThreads) flags[i] = 0;
-    __syncthreads();
-    // 5. refit + collapse DP (k_refit): the second arrival at a node computes it. Hand-off inside
-    // the workgroup: the child's box / DP stores complete (vmcnt(0)), then the LDS counter.
-    for (uint32_t i = tid; i < n; i += kFusedThreads) {
-      int node = pleaf[i];
-      while (node >= 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t old = __hip_atomic_fetch_add(&flags[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (old == 0) break;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        float a[6], b[6];
-        const int ca = s_child[2 * node], cbb = s_child[2 * node + 1];
-        load_box(ca, nbox, primbox, sorted, a);
-        load_box(cbb, nbox, primbox, sorted, b);
-        float bb[6];
-        for (int k = 0; k < 3; ++k) {
-          bb[k] = fminf(a[k], b[k]);
-          bb[3 + k] = fmaxf(a[3 + k], b[3 + k]);
-        }
-        float* o = nbox + (size_t)node * 6;
-        for (int k = 0; k < 6; ++k) o[k] = bb[k];
-        if (dpc) sah_dp(node, bb, ca, cbb, dpc, dps);
-        node = s_pint[node];
-      }
-    }
-    __syncthreads();
-  RT_BT(4);
-    // 6. pack (k_pack)
-    for (int i = (int)tid; i < (int)n - 1; i += kFusedThreads) {
-      BinNode nd;
-      int c[2] = {s_child[2 * i], s_child[2 * i + 1]};
-      float b[2][6];
-      for (int k = 0; k < 2; ++k) load_box(c[k], nbox, primbox, sorted, b[k]);
-      for (int k = 0; k < 3; ++k) {
-        nd.lo0[k] = b[0][k];
-        nd.hi0[k] = b[0][3 + k];
-        nd.lo1[k] = b[1][k];
-        nd.hi1[k] = b[1][3 + k];
-      }
-      for (int k = 0; k < 2; ++k)
-        if (c[k] < 0 && leaf_ref_is_prim) c[k] = ~(int)sorted[~c[k]];
-      nd.c0 = c[0];
-      nd.c1 = c[1];
-      nd.pad0 = nd.pad1 = 0;
-      bin[i] = nd;
-    }
-  }
-  __syncthreads();
-  RT_BT(5);
-  RT_BT(6);
-  // 8. collapse into BFS-ordered 4-wide nodes (k_collapse); level lists and stack sums in LDS
-  {
-    int* cur = (int*)s_mem;
-    int* nxt = (int*)s_mem + kFusedMax;
-    int* ps = (int*)s_mem + 2 * kFusedMax;
-    if (tid == 0) {
-      cur[0] = 0;
-      ps[0] = 0;
-      s_maxstack = 0;
-    }
-    __syncthreads();
-    int lmax = 0, cur_n = 1, base = 0, depth = 0;
-    while (cur_n > 0) {
-      ++depth;
-      int next_total = 0;
-      for (int cs = 0; cs < cur_n; cs += kFusedThreads) {
-        const int i = cs + (int)tid;
-        const bool valid = i < cur_n;
-        int ref[4];
-        float box[4][6];
-        int cnt4 = 0;
-        if (valid) {
-          if (dpc)  // the DP expansion of this wide node's root, in registers (no k_dp_expand pass)
-            cnt4 = wide_slots_dp(bin, dpc, dps, cur[i], ref, box, !leaf_ref_is_prim);
-          else {
-            cnt4 = gather4(bin, cur[i], ref, box);
-            for (int j = cnt4; j < 4; ++j) ref[j] = kEmptyChild;
-            if (!leaf_ref_is_prim) inner_first(ref, box);
-          }
-        }
-        uint32_t m = 0;
-        for (int j = 0; j < cnt4; ++j) m += ref[j] >= 0;
-        uint32_t chunk_total;
-        const int excl = (int)block_excl_scan(m, s_w, &chunk_total);
-        if (valid) {
-          Bvh4Node nd;
-          int o = excl;
-          const int below = ps[base + i] + cnt4 - 1;
-          lmax = below > lmax ? below : lmax;
-          uint32_t nvalid = 0, inner = 0;
-          nd.first_inner = 0;
-          for (int j = 0; j < 4; ++j) {
-            const float inf = __builtin_inff();
-            float b6[6] = {inf, inf, inf, inf, inf, inf};
-            int32_t r = kEmptyChild;
-            if (j < cnt4 && ref[j] != kEmptyChild) {
-              ++nvalid;
-              for (int a = 0; a < 6; ++a) b6[a] = box[j][a];
-              if (ref[j] >= 0) {
-                const int pos = next_total + o;
-                nxt[pos] = ref[j];
-                r = base + cur_n + pos;
-                ps[r] = below;
-                if (o == excl) nd.first_inner = r;
-                inner |= 1u << j;
-                ++o;
-              } else {
-                r = ref[j];
-              }
-            }
-            nd.lox[j] = b6[0];
-            nd.loy[j] = b6[1];
-            nd.loz[j] = b6[2];
-            nd.hix[j] = b6[3];
-            nd.hiy[j] = b6[4];
-            nd.hiz[j] = b6[5];
-            nd.child[j] = r;
-          }
-          nd.count = nvalid;
-          nd.inner_mask = inner;
-          nd.entry_base = ((uint32_t)nd.first_inner << 8) | (inner << 4);
-          out[base + i] = nd;
-        }
-        next_total += (int)chunk_total;
-      }
-      __syncthreads();  // the next level reads nxt / ps
-      int* t = cur;
-      cur = nxt;
-      nxt = t;
-      base += cur_n;
-      cur_n = next_total;
-    }
-    atomicMax(&s_maxstack, lmax);
-    __syncthreads();
-    if (tid == 0) {
-      info[0] = (uint32_t)base;
-      info[1] = (uint32_t)depth;
-      info[2] = (uint32_t)s_maxstack;
-    }
-  }
-  RT_BT(7);
-  // 9. triangles into leaf order (k_tri_reorder)
-  if (tri_in)
-    for (uint32_t i = tid; i < n; i += kFusedThreads) tri_out[i] = tri_in[sorted[i]];
-#if RT_BUILD_TIMING
-  RT_BT(8);
-  if (tid == 0)
-    printf("k_build_small n=%u cycles: bounds %lu morton+sort %lu karras %lu refit %lu pack %lu dpexp %lu collapse %lu reorder %lu\n",
-           n, bt[1] - bt[0], bt[2] - bt[1], bt[3] - bt[2], bt[4] - bt[3], bt[5] - bt[4], bt[6] - bt[5], bt[7] - bt[6],
-           bt[8] - bt[7]);
-#endif
-#undef RT_BT
-}
-
-// ------------------------------------------------------------------------------------------
-// Four-launch build for RT_MID_MIN_N <= n <= kMidMax (the teapot / rabbit BLASes, every TLAS of
+// Four-launch build for kTinyMax < n <= kMidMax (the teapot / rabbit BLASes, every TLAS of
 // the configs) instead of ~20 launches, none of them a long single-workgroup pipeline:
 //   k_mid_rank       bounds + Morton codes + sort by RANK, one launch: every workgroup reduces the
 //                    bounds of all n boxes itself (exact min / max: any order gives the same
@@ -1528,17 +952,10 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
   __shared__ __attribute__((aligned(16))) unsigned char s_raw[kA > kD ? kA : kD];
   __shared__ uint16_t s_top[kMidTopSlots];
   __shared__ uint32_t s_ntop, s_nslot, s_root;
-  __shared__ uint32_t s_w[2 * kFusedWaves];
+  __shared__ uint32_t s_w[2 * kBlockWaves];
   __shared__ int s_maxstack;
   const int tid = (int)threadIdx.x;
   const int nbin = (int)n - 1;
-#if RT_BUILD_TIMING
-  uint64_t bt[4];
-  bt[0] = __builtin_amdgcn_s_memtime();
-#define RT_BT(k) bt[k] = __builtin_amdgcn_s_memtime()
-#else
-#define RT_BT(k) (void)0
-#endif
   const uint32_t nf = info[4];
   // the child lists of every node k_mid_expand built, loaded now (into registers: the LDS they go to
   // holds the top climb's keys and slots first), in flight during the top climb
@@ -1577,10 +994,6 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
         mid_join(s, left, a, o, bin, dpc, dps);
         s_top[__hip_atomic_fetch_add(&s_ntop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)] = (uint16_t)s;
         if (a.l == 0 && a.r == (int)n - 1) s_root = (uint32_t)s;
-#if RT_BUILD_TIMING
-        if (a.l == 0 && a.r == (int)n - 1)
-          printf("  top climb: root thread %d done at %lu (start %lu)\n", tid, __builtin_amdgcn_s_memtime() - bt[0], 0ul);
-#endif
       }
     }
     __threadfence_block();
@@ -1590,7 +1003,6 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
     s_root = info[3];
   }
   __syncthreads();
-  RT_BT(1);
   uint2* s_e = (uint2*)s_raw;                                  // per binary node: its wide node's slot refs
   uint16_t* s_order = (uint16_t*)(s_raw + kMidMax * 8);        // BFS index -> binary node
   uint16_t* s_bfs = s_order + kMidMax;                         // binary node -> BFS index
@@ -1614,7 +1026,6 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
   const int root = min((int)s_root, nbin - 1);  // (a root outside the tree would be a bug)
   __threadfence_block();
   __syncthreads();
-  RT_BT(2);
   if (tid == 0) {
     s_order[0] = (uint16_t)root;
     s_bfs[root] = 0;
@@ -1626,10 +1037,6 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
   // nodes of the level; the exclusive sum of their internal-child counts (<= 32: six bits) is
   // formed from one ballot per bit (popcount of the lower lanes), the waves' totals through LDS.
   int lmax = 0, cur_n = 1, base = 0, depth = 0;
-#if RT_BUILD_TIMING
-  uint64_t lvt[16];
-  lvt[0] = __builtin_amdgcn_s_memtime();
-#endif
   const uint32_t lane = (uint32_t)tid & 63u, wv = (uint32_t)tid >> 6;
   const uint64_t lower = lane == 0 ? 0ull : (~0ull >> (64u - lane));
   while (cur_n > 0) {
@@ -1648,12 +1055,12 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
       pre += (uint32_t)__popcll(bal & lower) << bit;
       wtot += (uint32_t)__popcll(bal) << bit;
     }
-    uint32_t* s_wl = s_w + (depth & 1) * kFusedWaves;  // double-buffered: no barrier before the write
+    uint32_t* s_wl = s_w + (depth & 1) * kBlockWaves;  // double-buffered: no barrier before the write
     if (lane == 0) s_wl[wv] = wtot;
     __syncthreads();
     uint32_t woff = 0, total = 0;
 #pragma unroll
-    for (int k = 0; k < kFusedWaves; ++k) {
+    for (int k = 0; k < kBlockWaves; ++k) {
       const uint32_t c = s_wl[k];
       woff += (uint32_t)k < wv ? c : 0u;
       total += c;
@@ -1676,13 +1083,9 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
     }
     ++depth;
     __syncthreads();
-#if RT_BUILD_TIMING
-    if (depth < 16) lvt[depth] = __builtin_amdgcn_s_memtime();
-#endif
     base += cur_n;
     cur_n = (int)total;
   }
-  RT_BT(3);
   // the node writes run in k_mid_write (many workgroups): BFS order and index maps to HBM
   for (int k = tid; k < base; k += 1024) order_out[k] = s_order[k];
   for (int k = tid; k < nbin; k += 1024) bfs_out[k] = s_bfs[k];
@@ -1692,13 +1095,7 @@ __global__ __launch_bounds__(1024) void k_mid_collapse(uint32_t n, const uint32_
     info[0] = (uint32_t)base;
     info[1] = (uint32_t)depth;
     info[2] = (uint32_t)s_maxstack;
-#if RT_BUILD_TIMING
-    printf("k_mid_collapse n=%u frontier %u top %d levels %d cycles: top-climb %lu expand %lu bfs %lu\n", n, nf, ntop,
-           depth, bt[1] - bt[0], bt[2] - bt[1], bt[3] - bt[2]);
-    for (int k = 1; k < depth && k < 16; ++k) printf("  bfs level %d: %lu\n", k, lvt[k] - lvt[k - 1]);
-#endif
   }
-#undef RT_BT
 }
 
 // Every 4-wide node in parallel (BFS index k): its wide root's expansion with the slot refs mapped to
@@ -1972,6 +1369,33 @@ __global__ __launch_bounds__(kTinyMax) void k_build_tiny(const float* __restrict
   }
 }
 
+// n == 1, one thread: what the multi-kernel stages leave for a single primitive. k_bounds' twelve values
+// (the min / max of one box), the leaf order, k_single's root expanded by wide_slots_dp (both children are
+// leaves, so no DP record is read) and written as the tree's only node, k_collapse's info (one node, one
+// level; the root's two slots leave cnt - 1 on the stack) and the triangle in leaf order.
+__global__ void k_build_one(const float* __restrict__ primbox, bool leaf_ref_is_prim, uint32_t* __restrict__ sorted,
+                            float* __restrict__ cb_out, Bvh4Node* __restrict__ out, uint32_t* __restrict__ info,
+                            const TriRec* __restrict__ tri_in, TriRec* __restrict__ tri_out) {
+  __shared__ BinNode s_root;
+  for (int k = 0; k < 3; ++k) {
+    const float c = (primbox[k] + primbox[3 + k]) * 0.5f;
+    cb_out[k] = fminf(INFINITY, c);
+    cb_out[3 + k] = fmaxf(-INFINITY, c);
+    cb_out[6 + k] = fminf(INFINITY, primbox[k]);
+    cb_out[9 + k] = fmaxf(-INFINITY, primbox[3 + k]);
+  }
+  sorted[0] = 0;
+  s_root = single_root(primbox);
+  int ref[4];
+  float box[4][6];
+  const int cnt = wide_slots_dp(&s_root, nullptr, nullptr, 0, ref, box, !leaf_ref_is_prim);
+  write_wide_node(ref, box, cnt, nullptr, out);
+  info[0] = 1u;
+  info[1] = 1u;
+  info[2] = (uint32_t)(cnt - 1);
+  if (tri_in) tri_out[0] = tri_in[0];
+}
+
 __global__ void k_tri_setup(const float* __restrict__ vtx, const uint32_t* __restrict__ idx,
                             uint32_t ntri, TriRec* __restrict__ tris, float* __restrict__ box) {
   uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2052,27 +1476,6 @@ __global__ void k_inst_boxes(const InstanceRec* __restrict__ inst, const float* 
 
 inline unsigned grid1(uint32_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
-enum { kPathSmall = 0, kPathMid = 1, kPathMulti = 2, kPathTiny = 3 };
-
-// Which schedule builds n primitives (measured crossovers). RT_BUILD_PATH=small|mid|multi
-// in the environment forces one where it can hold n (A/B timing only; every schedule builds the
-// bitwise-identical tree).
-int build_path(uint32_t n) {
-  const char* f = getenv("RT_BUILD_PATH");
-  const bool small_ok = RT_FUSED_BUILD && n <= kFusedMax, mid_ok = RT_SAH_COLLAPSE && n >= 2 && n <= kMidMax;
-  const bool tiny_ok = RT_SAH_COLLAPSE && n >= 2 && n <= kTinyMax;
-  if (f) {
-    if (!strcmp(f, "tiny") && tiny_ok) return kPathTiny;
-    if (!strcmp(f, "small") && small_ok) return kPathSmall;
-    if (!strcmp(f, "mid") && mid_ok) return kPathMid;
-    if (!strcmp(f, "multi")) return kPathMulti;
-  }
-  if (RT_TINY_BUILD && tiny_ok && n <= (uint32_t)RT_TINY_MAX_N) return kPathTiny;
-  if (RT_MID_BUILD && mid_ok && n >= (uint32_t)RT_MID_MIN_N) return kPathMid;
-  if (small_ok && n <= (uint32_t)RT_FUSED_MAX_N) return kPathSmall;
-  return kPathMulti;
-}
-
 struct DevBuf {
   void* p = nullptr;
   ~DevBuf() {
@@ -2086,6 +1489,147 @@ struct DevBuf {
     if (e_ != hipSuccess) return e_;      \
   } while (0)
 
+enum { kPathOne = 0, kPathMid = 1, kPathMulti = 2, kPathTiny = 3 };
+
+// Which schedule builds n primitives (measured crossovers). RT_BUILD_PATH=tiny|mid|multi in
+// the environment forces one where it can hold n (A/B timing and tests; every schedule builds the
+// bitwise-identical tree); one that cannot hold n falls back to the default.
+int build_path(uint32_t n) {
+  const bool tiny_ok = n >= 2 && n <= kTinyMax, mid_ok = n >= 2 && n <= kMidMax;
+  if (const char* f = getenv("RT_BUILD_PATH")) {
+    if (!strcmp(f, "tiny") && tiny_ok) return kPathTiny;
+    if (!strcmp(f, "mid") && mid_ok) return kPathMid;
+    if (!strcmp(f, "multi")) return kPathMulti;
+  }
+  return n == 1 ? kPathOne : tiny_ok ? kPathTiny : mid_ok ? kPathMid : kPathMulti;
+}
+
+// A build's temporaries are parts of ONE allocation (hipMalloc costs ~0.1 ms each; a hot-reload rebuild
+// pays it). A schedule takes its parts in a fixed order, so lbvh_build runs it twice: over an arena
+// without a base, where it only adds up `total` and launches nothing, then over the allocation.
+struct Arena {
+  char* base = nullptr;
+  size_t total = 0;
+  template <class T>
+  T* take(size_t count) {
+    const size_t off = total;
+    total += (count * sizeof(T) + 255) & ~(size_t)255;
+    return base ? (T*)(base + off) : nullptr;
+  }
+};
+
+// What a schedule works on: lbvh_build's arguments, and the two parts it leaves for the readback (cb:
+// k_bounds' twelve floats; info: node count, levels, stack bound, then words of its own).
+struct BuildJob {
+  const float* primbox;
+  uint32_t n;
+  bool leaf_ref_is_prim;
+  Bvh4Node* nodes;
+  uint32_t* sorted;
+  const TriRec* tri_in;
+  TriRec* tri_out;
+  hipStream_t s;
+  float* cb;
+  uint32_t* info;
+};
+
+hipError_t build_one(Arena& a, const BuildJob& b) {
+  if (!a.base) return hipSuccess;  // no temporaries
+  k_build_one<<<1, 1, 0, b.s>>>(b.primbox, b.leaf_ref_is_prim, b.sorted, b.cb, b.nodes, b.info, b.tri_in, b.tri_out);
+  return hipGetLastError();
+}
+
+hipError_t build_tiny(Arena& a, const BuildJob& b) {
+  if (!a.base) return hipSuccess;  // no temporaries: everything in LDS
+  k_build_tiny<<<1, kTinyMax, 0, b.s>>>(b.primbox, b.n, b.leaf_ref_is_prim, b.sorted, b.cb, b.nodes, b.info, b.tri_in,
+                                        b.tri_out);
+  return hipGetLastError();
+}
+
+hipError_t build_mid(Arena& a, const BuildJob& b) {
+  const uint32_t n = b.n, nbin = n - 1;
+  uint64_t* k64 = a.take<uint64_t>(n);
+  uint32_t* keys = a.take<uint32_t>(n);
+  float* sbox = a.take<float>((size_t)n * 6);
+  MidSlot* frontier = a.take<MidSlot>(n);
+  BinNode* bin = a.take<BinNode>(nbin);
+  float4* dpc = a.take<float4>(nbin);
+  uint32_t* dps = a.take<uint32_t>(nbin);
+  Exp4* exp = a.take<Exp4>(nbin);
+  uint2* e16 = a.take<uint2>(nbin);
+  uint16_t* order = a.take<uint16_t>(nbin);
+  uint16_t* bfs = a.take<uint16_t>(nbin);
+  if (!a.base) return hipSuccess;
+  const bool blas = !b.leaf_ref_is_prim;
+  k_mid_rank<<<grid1(n, 64), 1024, 0, b.s>>>(b.primbox, n, b.cb, k64, keys, b.sorted, sbox, dps, b.info, b.tri_in,
+                                             b.tri_out);
+  k_mid_tree<<<grid1(n, kMidBlock), kMidBlock, 0, b.s>>>(n, keys, b.sorted, sbox, b.leaf_ref_is_prim, bin, dpc, dps,
+                                                         frontier, b.info);
+  k_mid_expand<<<grid1(nbin, 256), 256, 0, b.s>>>((int)nbin, bin, dpc, dps, exp, e16, blas);
+  k_mid_collapse<<<1, 1024, 0, b.s>>>(n, keys, frontier, bin, dpc, dps, exp, e16, order, bfs, b.info, blas);
+  k_mid_write<<<grid1(nbin, 256), 256, 0, b.s>>>(exp, order, bfs, b.info, b.nodes);
+  return hipGetLastError();
+}
+
+hipError_t build_multi(Arena& a, const BuildJob& b) {
+  const uint32_t n = b.n, nbin = n > 1 ? n - 1 : 1, nblocks = (n + kRsTile - 1) / kRsTile;
+  uint32_t* keys0 = a.take<uint32_t>(n);
+  uint32_t* keys1 = a.take<uint32_t>(n);
+  uint32_t* vals1 = a.take<uint32_t>(n);
+  uint32_t* hist = a.take<uint32_t>((size_t)256 * nblocks);
+  int* child = a.take<int>((size_t)nbin * 2);
+  int* pint = a.take<int>(nbin);
+  int* pleaf = a.take<int>(n);
+  float* nbox = a.take<float>((size_t)nbin * 6);
+  uint32_t* flags = a.take<uint32_t>(nbin);
+  float4* dpc = a.take<float4>(nbin);
+  uint32_t* dps = a.take<uint32_t>(nbin);
+  BinNode* bin = a.take<BinNode>(nbin);
+  Exp4* exp = a.take<Exp4>(nbin);
+  int* la = a.take<int>(nbin);
+  int* lb = a.take<int>(nbin);
+  int* ps = a.take<int>(nbin);
+  if (!a.base) return hipSuccess;
+  hipStream_t s = b.s;
+  k_bounds<<<1, 1024, 0, s>>>(b.primbox, n, b.cb);
+  RT_TRY(hipGetLastError());
+  uint32_t* ka = keys0;
+  uint32_t* va = b.sorted;  // values ping-pong between sorted and vals1; 4 passes end in sorted
+  uint32_t* kb = keys1;
+  uint32_t* vb = vals1;
+  k_morton<<<grid1(n, 256), 256, 0, s>>>(b.primbox, n, b.cb, ka, va);
+  RT_TRY(hipGetLastError());
+  for (int pass = 0; pass < 4; ++pass) {
+    int shift = pass * 8;
+    k_rs_hist<<<nblocks, kRsThreads, 0, s>>>(ka, n, shift, hist, nblocks);
+    k_rs_scan<<<1, 1024, 0, s>>>(hist, 256 * nblocks);
+    k_rs_scatter<<<nblocks, kRsThreads, 0, s>>>(ka, va, kb, vb, n, shift, hist, nblocks);
+    RT_TRY(hipGetLastError());
+    std::swap(ka, kb);
+    std::swap(va, vb);
+  }
+  // after 4 swaps: va == sorted, ka == keys0 (sorted keys)
+  if (n == 1) {
+    k_single<<<1, 1, 0, s>>>(b.primbox, b.leaf_ref_is_prim, bin);
+    RT_TRY(hipGetLastError());
+  } else {
+    RT_TRY(hipMemsetAsync(flags, 0, (size_t)(n - 1) * 4, s));
+    k_karras<<<grid1(n - 1, 256), 256, 0, s>>>(ka, (int)n, child, pint, pleaf);
+    k_refit<<<grid1(n, 256), 256, 0, s>>>((int)n, pleaf, pint, child, b.primbox, b.sorted, nbox, flags, dpc, dps);
+    k_pack<<<grid1(n - 1, 256), 256, 0, s>>>((int)n, child, nbox, b.primbox, b.sorted, b.leaf_ref_is_prim, bin);
+    RT_TRY(hipGetLastError());
+  }
+  k_dp_expand<<<grid1(nbin, 256), 256, 0, s>>>((int)nbin, bin, dpc, dps, exp, !b.leaf_ref_is_prim);
+  RT_TRY(hipGetLastError());
+  k_collapse<<<1, 1024, 0, s>>>(exp, b.nodes, la, lb, ps, b.info);
+  RT_TRY(hipGetLastError());
+  if (b.tri_in) {
+    k_tri_reorder<<<grid1(n, 256), 256, 0, s>>>(b.tri_in, b.sorted, n, b.tri_out);
+    RT_TRY(hipGetLastError());
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 hipError_t lbvh_build(const float* d_primbox, uint32_t n, Bvh4Node* d_nodes, uint32_t* d_sorted,
@@ -2093,32 +1637,21 @@ hipError_t lbvh_build(const float* d_primbox, uint32_t n, Bvh4Node* d_nodes, uin
                       float bounds[6], float* build_ms, hipStream_t s, const TriRec* d_tri_in, TriRec* d_tri_out,
                       BuildArena* keep) {
   if (n == 0) return hipErrorInvalidValue;
-  const uint32_t nblocks = (n + kRsTile - 1) / kRsTile;
-  const uint32_t nbin = n > 1 ? n - 1 : 1;
-  // all temporaries in ONE allocation (hipMalloc costs ~0.1 ms each; a hot-reload rebuild pays it)
-  struct Part {
-    size_t off, bytes;
+  BuildJob job{d_primbox, n, leaf_ref_is_prim, d_nodes, d_sorted, d_tri_in, d_tri_out, s, nullptr, nullptr};
+  const int path = build_path(n);
+  auto schedule = [&](Arena& a) {
+    job.cb = a.take<float>(12);  // stats and info first and adjacent: one readback copies both
+    job.info = a.take<uint32_t>(8);
+    return path == kPathOne    ? build_one(a, job)
+           : path == kPathTiny ? build_tiny(a, job)
+           : path == kPathMid  ? build_mid(a, job)
+                               : build_multi(a, job);
   };
-  size_t total = 0;
-  auto part = [&](size_t bytes) {
-    Part q{total, bytes};
-    total += (bytes + 255) & ~(size_t)255;
-    return q;
-  };
-  // stats and info first and adjacent: one readback copies both
-  const Part p_stats = part(12 * sizeof(float)), p_info = part(32), p_keys0 = part((size_t)n * 4),
-             p_keys1 = part((size_t)n * 4), p_vals1 = part((size_t)n * 4), p_hist = part((size_t)256 * nblocks * 4),
-             p_ps = part((size_t)nbin * 4), p_bin = part((size_t)nbin * sizeof(BinNode)), p_la = part((size_t)nbin * 4),
-             p_lb = part((size_t)nbin * 4), p_child = part((size_t)nbin * 8), p_pint = part((size_t)nbin * 4),
-             p_pleaf = part((size_t)n * 4), p_nbox = part((size_t)nbin * 24), p_flags = part((size_t)nbin * 4),
-             p_dpc = part(RT_SAH_COLLAPSE ? (size_t)nbin * sizeof(float4) : 0),
-             p_dps = part(RT_SAH_COLLAPSE ? (size_t)nbin * 4 : 0),
-             p_exp = part(RT_SAH_COLLAPSE ? (size_t)nbin * sizeof(Exp4) : 0),
-             p_gslot = part((size_t)n * sizeof(MidSlot)), p_e16 = part((size_t)nbin * sizeof(uint2)),
-             p_order = part((size_t)nbin * 2), p_bfs = part((size_t)nbin * 2),
-             p_k64 = part((size_t)n * 8), p_sbox = part((size_t)n * 24);
-  DevBuf arena;
-  char* A = nullptr;
+  Arena a;
+  RT_TRY(schedule(a));  // a.total: this schedule's temporaries
+  const size_t total = a.total;
+  a = Arena{};
+  DevBuf own;
   if (keep) {  // the caller's scratch, kept between builds (no hipMalloc / hipFree on the way)
     if (keep->cap < total) {
       RT_TRY(hipStreamSynchronize(s));  // the previous build on s is the only user
@@ -2128,20 +1661,11 @@ hipError_t lbvh_build(const float* d_primbox, uint32_t n, Bvh4Node* d_nodes, uin
       RT_TRY(hipMalloc(&keep->p, total));
       keep->cap = total;
     }
-    A = (char*)keep->p;
+    a.base = (char*)keep->p;
   } else {
-    RT_TRY(hipMalloc(&arena.p, total));
-    A = (char*)arena.p;
+    RT_TRY(hipMalloc(&own.p, total));
+    a.base = (char*)own.p;
   }
-  struct View {
-    void* p;
-  };
-  auto at = [&](const Part& q) { return View{q.bytes ? (void*)(A + q.off) : nullptr}; };
-  View stats = at(p_stats), keys0 = at(p_keys0), keys1 = at(p_keys1), vals1 = at(p_vals1), hist = at(p_hist),
-       info = at(p_info), ps = at(p_ps), bin = at(p_bin), la = at(p_la), lb = at(p_lb), child = at(p_child),
-       pint = at(p_pint), pleaf = at(p_pleaf), nbox = at(p_nbox), flags = at(p_flags), dpc = at(p_dpc),
-       dps = at(p_dps), expd = at(p_exp), gslot = at(p_gslot), e16 = at(p_e16), order = at(p_order),
-       bfsmap = at(p_bfs), k64 = at(p_k64), sbox = at(p_sbox);
   struct Events {  // destroyed on every return path
     hipEvent_t a = nullptr, b = nullptr;
     ~Events() {
@@ -2162,93 +1686,20 @@ hipError_t lbvh_build(const float* d_primbox, uint32_t n, Bvh4Node* d_nodes, uin
     e1 = ev.b;
   }
   RT_TRY(hipEventRecord(e0, s));
-  float* cb = (float*)stats.p;
-  const int path = build_path(n);
-  if (path == kPathTiny) {
-    k_build_tiny<<<1, kTinyMax, 0, s>>>(d_primbox, n, leaf_ref_is_prim, d_sorted, cb, d_nodes, (uint32_t*)info.p,
-                                        d_tri_in, d_tri_out);
-    RT_TRY(hipGetLastError());
-  } else if (path == kPathMid) {
-    k_mid_rank<<<grid1(n, 64), 1024, 0, s>>>(d_primbox, n, cb, (uint64_t*)k64.p, (uint32_t*)keys0.p, d_sorted,
-                                              (float*)sbox.p, (uint32_t*)dps.p, (uint32_t*)info.p, d_tri_in,
-                                              d_tri_out);
-    k_mid_tree<<<grid1(n, kMidBlock), kMidBlock, 0, s>>>(n, (const uint32_t*)keys0.p, d_sorted,
-                                                          (const float*)sbox.p,
-                                                          leaf_ref_is_prim, (BinNode*)bin.p, (float4*)dpc.p,
-                                                          (uint32_t*)dps.p, (MidSlot*)gslot.p, (uint32_t*)info.p);
-    k_mid_expand<<<grid1(nbin, 256), 256, 0, s>>>((int)nbin, (const BinNode*)bin.p, (const float4*)dpc.p,
-                                                  (const uint32_t*)dps.p, (Exp4*)expd.p, (uint2*)e16.p,
-                                                  !leaf_ref_is_prim);
-    k_mid_collapse<<<1, 1024, 0, s>>>(n, (const uint32_t*)keys0.p, (const MidSlot*)gslot.p, (BinNode*)bin.p,
-                                      (float4*)dpc.p, (uint32_t*)dps.p, (Exp4*)expd.p, (const uint2*)e16.p,
-                                      (uint16_t*)order.p, (uint16_t*)bfsmap.p, (uint32_t*)info.p, !leaf_ref_is_prim);
-    k_mid_write<<<grid1(nbin, 256), 256, 0, s>>>((const Exp4*)expd.p, (const uint16_t*)order.p,
-                                                 (const uint16_t*)bfsmap.p, (const uint32_t*)info.p, d_nodes);
-    RT_TRY(hipGetLastError());
-  } else if (path == kPathSmall) {
-    k_build_small<<<1, kFusedThreads, 0, s>>>(d_primbox, n, leaf_ref_is_prim, d_sorted, cb, (int*)pleaf.p,
-                                              (float*)nbox.p, (float4*)dpc.p, (uint32_t*)dps.p, (BinNode*)bin.p,
-                                              d_nodes, (uint32_t*)info.p, d_tri_in, d_tri_out);
-    RT_TRY(hipGetLastError());
-  } else {
-  k_bounds<<<1, 1024, 0, s>>>(d_primbox, n, cb);
-  RT_TRY(hipGetLastError());
-  uint32_t* ka = (uint32_t*)keys0.p;
-  uint32_t* va = d_sorted;  // values ping-pong between d_sorted and vals1; 4 passes end in d_sorted
-  uint32_t* kb = (uint32_t*)keys1.p;
-  uint32_t* vb = (uint32_t*)vals1.p;
-  k_morton<<<grid1(n, 256), 256, 0, s>>>(d_primbox, n, cb, ka, va);
-  RT_TRY(hipGetLastError());
-  for (int pass = 0; pass < 4; ++pass) {
-    int shift = pass * 8;
-    k_rs_hist<<<nblocks, kRsThreads, 0, s>>>(ka, n, shift, (uint32_t*)hist.p, nblocks);
-    k_rs_scan<<<1, 1024, 0, s>>>((uint32_t*)hist.p, 256 * nblocks);
-    k_rs_scatter<<<nblocks, kRsThreads, 0, s>>>(ka, va, kb, vb, n, shift, (uint32_t*)hist.p, nblocks);
-    RT_TRY(hipGetLastError());
-    std::swap(ka, kb);
-    std::swap(va, vb);
-  }
-  // after 4 swaps: va == d_sorted, ka == keys0 (sorted keys)
-  BinNode* d_bin = (BinNode*)bin.p;
-  if (n == 1) {
-    k_single<<<1, 1, 0, s>>>(d_primbox, leaf_ref_is_prim, d_bin);
-    RT_TRY(hipGetLastError());
-  } else {
-    RT_TRY(hipMemsetAsync(flags.p, 0, (size_t)(n - 1) * 4, s));
-    k_karras<<<grid1(n - 1, 256), 256, 0, s>>>(ka, (int)n, (int*)child.p, (int*)pint.p, (int*)pleaf.p);
-    k_refit<<<grid1(n, 256), 256, 0, s>>>((int)n, (int*)pleaf.p, (int*)pint.p, (int*)child.p, d_primbox,
-                                          d_sorted, (float*)nbox.p, (uint32_t*)flags.p, (float4*)dpc.p,
-                                          (uint32_t*)dps.p);
-    k_pack<<<grid1(n - 1, 256), 256, 0, s>>>((int)n, (int*)child.p, (float*)nbox.p, d_primbox, d_sorted,
-                                             leaf_ref_is_prim, d_bin);
-    RT_TRY(hipGetLastError());
-  }
-  if (RT_SAH_COLLAPSE) {
-    k_dp_expand<<<grid1(nbin, 256), 256, 0, s>>>((int)nbin, d_bin, (const float4*)dpc.p, (const uint32_t*)dps.p,
-                                                 (Exp4*)expd.p, !leaf_ref_is_prim);
-    RT_TRY(hipGetLastError());
-  }
-  k_collapse<<<1, 1024, 0, s>>>(d_bin, (const Exp4*)expd.p, d_nodes, (int*)la.p, (int*)lb.p, (int*)ps.p,
-                                (uint32_t*)info.p, !leaf_ref_is_prim);
-  RT_TRY(hipGetLastError());
-  if (d_tri_in) {
-    k_tri_reorder<<<grid1(n, 256), 256, 0, s>>>(d_tri_in, d_sorted, n, d_tri_out);
-    RT_TRY(hipGetLastError());
-  }
-  }
+  RT_TRY(schedule(a));
   RT_TRY(hipEventRecord(e1, s));
   float hb[12];
   uint32_t hinfo[3];
-  const size_t info_off = p_info.off - p_stats.off;  // 256: the parts are adjacent
+  const size_t info_off = (const char*)job.info - (const char*)job.cb;  // 256: the parts are adjacent
   if (keep) {  // one copy of both into the arena's pinned buffer (a pageable destination is staged by the runtime)
     if (!keep->host) RT_TRY(hipHostMalloc(&keep->host, info_off + 32, hipHostMallocDefault));
-    RT_TRY(hipMemcpyAsync(keep->host, cb, info_off + 12, hipMemcpyDeviceToHost, s));
+    RT_TRY(hipMemcpyAsync(keep->host, job.cb, info_off + 12, hipMemcpyDeviceToHost, s));
     RT_TRY(hipStreamSynchronize(s));
     std::memcpy(hb, keep->host, sizeof(hb));
     std::memcpy(hinfo, (const char*)keep->host + info_off, sizeof(hinfo));
   } else {
-    RT_TRY(hipMemcpyAsync(hb, cb, sizeof(hb), hipMemcpyDeviceToHost, s));
-    RT_TRY(hipMemcpyAsync(hinfo, info.p, 12, hipMemcpyDeviceToHost, s));
+    RT_TRY(hipMemcpyAsync(hb, job.cb, sizeof(hb), hipMemcpyDeviceToHost, s));
+    RT_TRY(hipMemcpyAsync(hinfo, job.info, 12, hipMemcpyDeviceToHost, s));
     RT_TRY(hipStreamSynchronize(s));
   }
   for (int k = 0; k < 6; ++k) bounds[k] = hb[6 + k];
@@ -2392,10 +1843,9 @@ __device__ __forceinline__ int slot_word(int q, int k) { return (q < 3 ? q * 8 :
 // arrivals as the parent has internal children) goes on there; every other thread returns. No thread waits for
 // another. The node's 128 bytes are written by that one thread only, with plain stores (nothing reads them before the
 // kernel ends); only the unions cross threads:
-//   kOneWg (the tree fits one workgroup): counters in LDS, workgroup-scope release / acquire around them, as the
-//     climb of k_build_small;
+//   kOneWg (the tree fits one workgroup): counters in LDS, workgroup-scope release / acquire around them;
 //   otherwise: write-through stores of the union, vmcnt(0), an agent-scope counter, coherent loads — the hand-off
-//     of k_refit (RT_REFIT_WT), with its fence form when RT_REFIT_WT is 0.
+//     of k_refit.
 // `pool` (null, or the BLAS's first node in the scene pool) gets the same box words: the rebased copy differs in
 // its refs only. root_out: the root's union (the BLAS bounds).
 template <bool kOneWg>
@@ -2424,7 +1874,7 @@ __global__ __launch_bounds__(kOneWg ? 1024 : 256) void k_refit_boxes(
       float bb[6];
       if (c >= 0) {
         const float* cu = ubox + (size_t)c * 6;
-        for (int q = 0; q < 6; ++q) bb[q] = (kOneWg || !RT_REFIT_WT) ? cu[q] : ld_wt(cu + q);
+        for (int q = 0; q < 6; ++q) bb[q] = kOneWg ? cu[q] : ld_wt(cu + q);
       } else {
         const uint32_t p = tris[~c].prim;
         const uint32_t i0 = idx ? idx[3 * p] : 3 * p, i1 = idx ? idx[3 * p + 1] : 3 * p + 1,
@@ -2463,20 +1913,10 @@ __global__ __launch_bounds__(kOneWg ? 1024 : 256) void k_refit_boxes(
       if (old + 1u != need) return;
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     } else {
-#if RT_REFIT_WT
       for (int q = 0; q < 6; ++q) st_wt(o + q, u[q]);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       old = __hip_atomic_fetch_add(&counters[up], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (old + 1u != need) return;
-#else
-      for (int q = 0; q < 6; ++q) o[q] = u[q];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      old = __hip_atomic_fetch_add(&counters[up], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (old + 1u != need) return;
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     }
     node = up;
   }

@@ -78,7 +78,7 @@ def test_blas_bitwise_equal_to_oracle(model):
     c.close()
 
 
-# 1: the one-workgroup build (k_build_small); 2 .. 512: the one-launch LDS build (k_build_tiny);
+# 1: the one-node kernel (k_build_one); 2 .. 512: the one-launch LDS build (k_build_tiny);
 # 513 .. 8192: the four-launch build (k_mid_*, block boundaries at 1024-leaf multiples); 8193 and
 # 20000: the multi-kernel build
 @pytest.mark.parametrize("ntri", [1, 2, 3, 7, 63, 64, 65, 512, 513, 1000, 1023, 1024, 1025, 2049, 5000, 8191, 8192,
@@ -99,11 +99,12 @@ def test_blas_edge_sizes(ntri):
     c.close()
 
 
-@pytest.mark.parametrize("ntri", [2, 100, 1025, 3000, 8192])
+@pytest.mark.parametrize("ntri", [1, 2, 100, 1025, 3000, 8192, 8193])
 def test_build_schedules_bitwise_equal(ntri, monkeypatch):
-    # every schedule that can hold n (RT_BUILD_PATH: one-launch LDS build for n <= 512, one workgroup,
-    # four launches, multi-kernel; a schedule that cannot hold n falls back to the default)
-    # builds the oracle's tree, BLAS and TLAS alike
+    # every schedule that can hold n (RT_BUILD_PATH: one-launch LDS build for 2 <= n <= 512, four launches
+    # for 2 <= n <= 8192, multi-kernel; a schedule that cannot hold n falls back to the default) builds the
+    # oracle's tree, BLAS and TLAS alike. n = 1: the one-node kernel (the fallback of tiny and mid) and the
+    # forced multi-kernel build, for a 1-triangle BLAS and a 1-instance TLAS; 8193: every value ends in multi
     rng = np.random.default_rng(77 + ntri)
     v = np.zeros((ntri * 3, 6), np.float32)
     c0 = rng.uniform(-5, 5, size=(ntri, 1, 3))
@@ -117,7 +118,7 @@ def test_build_schedules_bitwise_equal(ntri, monkeypatch):
             for k in range(ninst)]
     o.set_instances([(ob, x, iid, hg) for (_, x, iid, hg) in inst])
     otl = o.export_tlas()
-    for path in ("tiny", "small", "mid", "multi"):
+    for path in ("tiny", "mid", "multi"):
         monkeypatch.setenv("RT_BUILD_PATH", path)
         c = fresh_ctx()
         b = c.blas_build(v)
@@ -126,6 +127,50 @@ def test_build_schedules_bitwise_equal(ntri, monkeypatch):
         c.tlas_build([(b, x, iid, hg) for (_, x, iid, hg) in inst])
         assert np.array_equal(c.tlas_export(), otl), f"{path}: TLAS differs"
         c.close()
+
+
+def test_one_triangle_tree_traced_and_refitted():
+    # the consumers of the one-node tree: the walk (a 1-triangle BLAS under a 1-instance TLAS), the refit's parent
+    # table and its one-workgroup climb
+    v = np.zeros((3, 6), np.float32)
+    v[:, :3] = [[0, 0, 0], [1, 0, 0], [0, 1, 0]]
+    v[:, 4] = 1.0
+    x = scenes.translation(1.0, 2.0, 3.0)
+    rays = np.zeros((8, 8), np.float32)
+    # four rays down -z through the triangle, three beside it, one through it but pointing away
+    rays[:, :2] = [[0.2, 0.2], [0.1, 0.6], [0.6, 0.1], [0.3, 0.3], [0.8, 0.8], [-0.5, 0.2], [2.0, 2.0], [0.2, 0.2]]
+    rays[:, :3] += [1.0, 2.0, 8.0]
+    rays[:, 6] = -1.0
+    rays[7, 6] = 1.0
+    rays[:, 7] = 100000.0
+    o = oracle.Scene()
+    ob = o.add_blas(v)
+    o.set_instances([(ob, x, 0, 0)])
+    oh, ouv, _ = o.trace_rays(rays, any_hit=False)
+    assert oh[:, 3].tolist() == [1, 1, 1, 1, 0, 0, 0, 0]
+    c = fresh_ctx()
+    b = c.blas_build(v)
+    c.tlas_build([(b, x, 0, 0)])
+    d_rays = torch.from_numpy(rays).cuda()
+    d_hits = torch.zeros((8, 4), dtype=torch.int32, device="cuda")
+    d_uv = torch.zeros((8, 2), dtype=torch.float32, device="cuda")
+    c.trace_rays(d_rays, 8, False, d_hits, d_uv, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_hits.cpu().numpy().view(np.uint32), oh)
+    assert np.array_equal(d_uv.cpu().numpy(), ouv)
+    n0, t0 = c.blas_export(b)
+    c.blas_refit(b, v)  # the build's own vertices: the build's bytes
+    n1, t1 = c.blas_export(b)
+    assert n1.tobytes() == n0.tobytes() and t1.tobytes() == t0.tobytes()
+    moved = v.copy()
+    moved[:, :3] = [[0.5, -1.0, 2.0], [3.0, 0.25, -0.0], [-2.0, 4.0, 1.5]]
+    c.blas_refit(b, moved)
+    n2, t2 = c.blas_export(b)
+    c2 = fresh_ctx()
+    fn, ft = c2.blas_export(c2.blas_build(moved))
+    assert n2.tobytes() == fn.tobytes() and t2.tobytes() == ft.tobytes()
+    c2.close()
+    c.close()
 
 
 @pytest.mark.parametrize("mesh", ["soup", "point"])

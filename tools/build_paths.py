@@ -1,7 +1,8 @@
-"""Build time of the three LBVH schedules (one-workgroup `small`, five-launch `mid`, `multi`-kernel)
-on random triangle soups and the reference meshes, in one process (RT_BUILD_PATH selects the schedule
-per build), with the trees of the schedules checked bitwise equal:
-  python tools/build_paths.py --sizes 2,64,1024,3072,4968,6320,8192 --reps 15"""
+"""Build time of the LBVH schedules (one-launch `tiny`, five-launch `mid`, `multi`-kernel; `default`: the
+one build_path() picks, which is also what a forced schedule that cannot hold n falls back to) on random
+triangle soups and the reference meshes, in one process (RT_BUILD_PATH selects the schedule per build),
+with the trees of the schedules checked bitwise equal:
+  python tools/build_paths.py --sizes 1,2,64,1024,3072,4968,6320,8192 --reps 15"""
 import argparse
 import os
 import statistics
@@ -16,9 +17,9 @@ import realtimeraytracing_gradproject_amd as rt  # noqa: E402
 from realtimeraytracing_gradproject_amd import scenes  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--sizes", default="2,64,256,1024,2048,3072,4096,8192")
+ap.add_argument("--sizes", default="1,2,64,256,1024,2048,3072,4096,8192")
 ap.add_argument("--reps", type=int, default=15)
-ap.add_argument("--paths", default="tiny,small,mid,multi")
+ap.add_argument("--paths", default="tiny,mid,multi")
 ap.add_argument("--lib", default=rt.LIB_PATH)
 a = ap.parse_args()
 
@@ -37,7 +38,10 @@ c = rt.Context(0, library=rt._load(a.lib))
 for name, v, i in cases:
     row, ref = [f"{name:12s}"], None
     for p in a.paths.split(","):
-        os.environ["RT_BUILD_PATH"] = p
+        if p == "default":
+            os.environ.pop("RT_BUILD_PATH", None)
+        else:
+            os.environ["RT_BUILD_PATH"] = p
         b = c.blas_build(v, i)
         ms = []
         for _ in range(a.reps):
