@@ -30,7 +30,9 @@ extern "C" {
  * changing any existing entry point, structure or default (backward compatible additions); so were rt_blas_refit /
  * rt_blas_refit_device, rt_dispatch_gbuffer, rt_host_shading_normals and the rt_gbuffer structure, and
  * rt_set_motion_history, rt_dispatch_gbuffer_motion, rt_host_motion_project / _vectors and rt_gbuffer_motion, and
- * rt_dispatch_ao, rt_host_ao_rays and rt_ao_params. */
+ * rt_dispatch_ao, rt_host_ao_rays and rt_ao_params, and rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous, their host
+ * twins rt_host_denoise_guide, rt_host_ao_accumulate, rt_host_ao_atrous, rt_ao_temporal_params and
+ * rt_ao_atrous_params. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -432,6 +434,82 @@ typedef struct { uint32_t samples; uint32_t seed; float radius; float tmin; } rt
  * light for now"). */
 rt_status rt_dispatch_ao(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
                          const rt_ao_params* params, float* ao_dev, void* hip_stream);
+
+/* ---- AO filter: what turns a few AO rays per pixel into a usable plane ----------------------------
+ * Three passes over planes the caller owns (device memory): a guide plane from the G-buffer, a temporal accumulation
+ * through rt_gbuffer_motion.motion, and an edge-aware a-trous blur. All three are asynchronous on hip_stream (NULL =
+ * the context's stream), need a context only (no TLAS, no camera, no shading state), allocate nothing and change no
+ * other launch's results. Frames are WHOLE row-major W x H planes (entry y W + x): there are no row lists, because a
+ * reprojection reads anywhere in the previous frame; a tiled multi-GPU caller filters after assembly.
+ * Arithmetic of all three: float32, no contraction, IEEE quotients, only + - * /, sqrtf, floorf, fabsf and
+ * comparisons, dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, normalize(v) = v * (1 / sqrtf(dot(v, v))), minf(a, b) =
+ * a < b ? a : b, maxf(a, b) = a > b ? a : b, sums in the order written: the device and the rt_host_* twins agree to
+ * the bit.
+ * On every RT_E_INVALID nothing is written and rt_last_error says which argument failed. RT_E_UNSUPPORTED (nothing
+ * written) for W or H above 2^30, or W x H (rt_denoise_guide: n) >= 2^31.
+ * Aliasing is detected by pointer EQUALITY only (and a depth pointer inside the guide plane): planes that overlap at
+ * an offset pass the checks and give undefined results; keeping distinct planes disjoint is the caller's.
+ * Known limit: the depth tests are relative to the pixel's depth, not to its depth gradient, so a surface seen at a
+ * grazing angle (depth changing by more than depth_tol from one pixel to the next) is under-filtered. */
+
+/* The guide plane: guide[i] = (nn.x, nn.y, nn.z, z), the unit normal and a positive depth, or (0, 0, 0, 0) = "no
+ * surface". valid = rt_dispatch_ao's rule on normal[i].xyz (finite components, dot finite and > 0) and z =
+ * depth[i * depth_stride] finite and > 0; a valid pixel gets (normalize(n), z), any other four zeros.
+ * normal: n x 4 floats, 16-byte aligned (rt_gbuffer.normal); depth: any float plane with a stride in floats >= 1:
+ * motion + 3 with stride 4 (w_cur) or hits with stride 4 (t); guide: n x 4 floats, 16-byte aligned. For
+ * rt_ao_accumulate BOTH frames' guides must be built from their own frame's w_cur: its depth test compares the
+ * previous guide's depth with motion's w_prev, the view depth. n = 0 is RT_OK.
+ * RT_E_INVALID: a null or misaligned plane (n > 0), depth_stride 0, guide == normal, depth inside guide. */
+rt_status rt_denoise_guide(rt_ctx_t ctx, uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
+                           float* guide, void* hip_stream);
+
+/* max_history: 1..1024, the longest history a pixel counts (the blend factor's floor 1 / max_history); depth_tol:
+ * finite and > 0, relative; normal_cos: -1 <= normal_cos < 1. The Python binding's defaults: 32, 0.02, 0.9. */
+typedef struct { uint32_t max_history; float depth_tol; float normal_cos; } rt_ao_temporal_params;
+
+/* Temporal accumulation. ao_cur, ao_prev, hist_prev, ao_out, hist_out: W*H floats; motion, guide_cur, guide_prev:
+ * W*H x 4 floats, 16-byte aligned. ao_prev, hist_prev, guide_prev: the previous frame's ao_out, hist_out and guide, or
+ * all three NULL (the first frame: no history is sought). For pixel (x, y), i = y W + x, g = guide_cur[i], m = motion[i]:
+ *   g.w == 0: ao_out = ao_cur[i], hist_out = 0.
+ *   History is sought when the prev planes are given, m.x and m.y are finite, m.z > 0 and fx = (float)x + m.x,
+ *   fy = (float)y + m.y satisfy -1 < fx < W and -1 < fy < H (rt_gbuffer_motion's half-pixel rule: the centres' 0.5
+ *   cancel). x0 = floorf(fx), tx = fx - x0, likewise y. The taps (x0 + dx, y0 + dy) in the order (0,0), (1,0), (0,1),
+ *   (1,1) weigh (1-tx)(1-ty), tx(1-ty), (1-tx)ty, tx ty. A tap is skipped (not read) when its weight is 0, it lies
+ *   outside the frame, q = guide_prev[tap] has q.w == 0, fabsf(q.w - m.z) > depth_tol * m.z (m.z = w_prev, the depth
+ *   the surface point had in the previous frame), or dot(g.xyz, q.xyz) < normal_cos. An accepted tap adds
+ *   sw += w; sa += w * ao_prev[tap]; sh += w * hist_prev[tap].
+ *   sw >= 0.01f: a = sa / sw, n = minf(sh / sw + 1.0f, (float)max_history), ao_out = a + (1.0f / n) * (ao_cur[i] - a)
+ *   (n == 1, as with max_history 1: ao_cur[i] itself, which a + (ao_cur[i] - a) only is up to a rounding),
+ *   hist_out = n. Otherwise (a disocclusion) ao_out = ao_cur[i], hist_out = 1.
+ * ao_out == ao_cur is allowed (a pixel reads only its own ao_cur entry). RT_E_INVALID: an output equal to a prev
+ * plane, to motion, to guide_cur or to the other output, hist_out == ao_cur; a null or misaligned plane; only some of
+ * the prev planes; null or out-of-range params; W or H of 0. */
+rt_status rt_ao_accumulate(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_temporal_params* params,
+                           const float* ao_cur, const float* motion, const float* guide_cur, const float* ao_prev,
+                           const float* hist_prev, const float* guide_prev, float* ao_out, float* hist_out,
+                           void* hip_stream);
+
+/* iterations: 1..5; depth_tol: finite and > 0, relative, widened by the step; normal_cos: -1 <= normal_cos < 1. */
+typedef struct { uint32_t iterations; float depth_tol; float normal_cos; } rt_ao_atrous_params;
+
+/* Edge-aware a-trous filter: `iterations` passes of a 5 x 5 B3-spline kernel with holes. Iteration k = 0 ..
+ * iterations - 1 has step s = 1 << k and reads the previous iteration's plane (the first reads ao_in, which is never
+ * written); the planes ping-pong between tmp and ao_out so that the last iteration lands in ao_out. ao_in, ao_out,
+ * tmp: W*H floats (tmp may be NULL when iterations == 1); guide: W*H x 4, 16-byte aligned (either depth source).
+ * For pixel p with g = guide[p]: g.w == 0 copies the value. Else the taps (dx, dy) in {-2..2}^2 sit at (x + dx s,
+ * y + dy s), dy outer, dx inner, both ascending; h = {0.0625, 0.25, 0.375, 0.25, 0.0625}, k = h[dy+2] * h[dx+2]
+ * (exact). The centre tap has w = k. Another tap is skipped when it lies outside the frame or q = guide[tap] has
+ * q.w == 0; otherwise
+ *   wz = maxf(0, 1 - fabsf(q.w - g.w) / ((depth_tol * g.w) * (float)s))
+ *   wn = minf(1, maxf(0, (dot(g.xyz, q.xyz) - normal_cos) / (1 - normal_cos)))
+ *   e = wz * wn;  w = k * (e * e)
+ * and sw += w; sa += w * in[tap]; out = sa / sw. The weights are rational on purpose (expf is not reproducible
+ * between the host and the device).
+ * RT_E_INVALID: any two of the pointers equal, a null plane (tmp: only when iterations > 1), a misaligned plane, null
+ * or out-of-range params, W or H of 0. */
+rt_status rt_ao_atrous(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
+                       const float* guide, float* ao_out, float* tmp, void* hip_stream);
+
 /* Stream lifetime: the context notes (host-side, no event per launch) which streams launched with the current
  * TLAS version, and records one event on each of them when the next rt_tlas_build swaps that version out; the tile
  * balance likewise notes the streams that read a work list, and queries the stream of a shape's previous launch
@@ -687,6 +765,18 @@ rt_status rt_host_motion_vectors(const void* vtx, const void* prev_vtx, uint32_t
 rt_status rt_host_ao_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
                           const uint32_t* py, uint32_t n, const rt_ao_params* params, float* rays_out,
                           uint8_t* valid_out);
+
+/* rt_denoise_guide, rt_ao_accumulate and rt_ao_atrous on host arrays: the same arguments less the context and the
+ * stream, the same checks less the 16-byte alignment (4 bytes will do), the same per-pixel functions the kernels
+ * call, so the same bits: the check of the three passes, and the filter without a GPU. Errors as the device forms'
+ * (the status only: there is no context to hold a message); nothing is written then. */
+rt_status rt_host_denoise_guide(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
+                                float* guide);
+rt_status rt_host_ao_accumulate(uint32_t W, uint32_t H, const rt_ao_temporal_params* params, const float* ao_cur,
+                                const float* motion, const float* guide_cur, const float* ao_prev,
+                                const float* hist_prev, const float* guide_prev, float* ao_out, float* hist_out);
+rt_status rt_host_ao_atrous(uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
+                            const float* guide, float* ao_out, float* tmp);
 
 /* ---- Camera manipulator ------------------------------------------------------------------------
  * nv_helpers_dx12::Manipulator (include/manipulator.h:33-148, src/manipulator.cpp) as plain data the

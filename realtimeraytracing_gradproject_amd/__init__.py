@@ -87,6 +87,16 @@ class rt_ao_params(ctypes.Structure):
                 ("tmin", ctypes.c_float)]
 
 
+class rt_ao_temporal_params(ctypes.Structure):
+    """include/rt_api.h rt_ao_temporal_params: max_history (1..1024), depth_tol, normal_cos of rt_ao_accumulate."""
+    _fields_ = [("max_history", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
+
+
+class rt_ao_atrous_params(ctypes.Structure):
+    """include/rt_api.h rt_ao_atrous_params: iterations (1..5), depth_tol, normal_cos of rt_ao_atrous."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
+
+
 class rt_manipulator(ctypes.Structure):
     """include/rt_api.h rt_manipulator: nv_helpers_dx12::Manipulator state (manipulator.h:124-144)."""
     _fields_ = [("pos", ctypes.c_float * 3), ("interest", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
@@ -135,6 +145,10 @@ SIGNATURES = [
     ("rt_set_motion_history", _I, [_P, _I]),
     ("rt_dispatch_gbuffer_motion", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer_motion), _FP, _P]),
     ("rt_dispatch_ao", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
+    ("rt_denoise_guide", _I, [_P, _U32, _P, _P, _U32, _P, _P]),
+    ("rt_ao_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P,
+                              _P]),
+    ("rt_ao_atrous", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P, _P]),
     ("rt_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _P]),
     ("rt_raster_draw", _I, [_P, _UP, _U32, _FP, _U32, _U32, _P, _P, _P]),
     ("rt_assemble_strips", _I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P]),
@@ -179,6 +193,9 @@ SIGNATURES = [
     ("rt_host_motion_project", _I, [_P, _P, _U32, _P, _P, _U32, _U32, _P]),
     ("rt_host_motion_vectors", _I, [_P, _P, _U32, _U32, _P, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
     ("rt_host_ao_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
+    ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
+    ("rt_host_ao_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rt_host_ao_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P]),
     ("rt_manip_init", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_update", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_set_lookat", None, [ctypes.POINTER(rt_manipulator), _FP, _FP, _FP]),
@@ -438,6 +455,57 @@ def host_ao_rays(cam_rays, t, normal, px, py, samples: int, radius: float, tmin:
     if st != RT_OK:
         raise RtError(st, "rt_host_ao_rays")
     return rays, valid
+
+
+def host_denoise_guide(normal, depth):
+    """rt_host_denoise_guide: the AO filter's guide plane on the host (no GPU). normal: (n, 4) G-buffer normals; depth:
+    n floats, or any strided view of a float32 array (motion[:, 3]: w_cur; hits.view(float32)[:, 0]: t). Returns (n, 4)
+    float32: (unit normal, depth), or four zeros where the normal is not valid or the depth is not finite and > 0."""
+    nr = np.ascontiguousarray(normal, dtype=np.float32).reshape(-1, 4)
+    n = nr.shape[0]
+    d = np.asarray(depth)
+    if d.dtype != np.float32 or d.ndim != 1 or (n and (d.strides[0] <= 0 or d.strides[0] % 4)):
+        d = np.ascontiguousarray(depth, dtype=np.float32).ravel()
+    if d.size != n:
+        raise ValueError(f"expected {n} depths, got {d.size}")
+    out = np.zeros((n, 4), np.float32)
+    st = lib.rt_host_denoise_guide(n, _vp(nr), _vp(d), d.strides[0] // 4 if n else 1, _vp(out))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_denoise_guide")
+    return out
+
+
+def host_ao_accumulate(width: int, height: int, ao_cur, motion, guide_cur, ao_prev=None, hist_prev=None,
+                       guide_prev=None, max_history: int = 32, depth_tol: float = 0.02, normal_cos: float = 0.9):
+    """rt_host_ao_accumulate: the AO filter's temporal pass on the host (no GPU). ao_cur: width * height floats; motion,
+    guide_cur: (width * height, 4); ao_prev, hist_prev, guide_prev: the previous frame's outputs and guide, or all
+    None (the first frame). Returns (ao_out, hist_out), width * height float32 each."""
+    n = width * height
+    cur, mo, gc = _f32(ao_cur, n), _f32(motion, 4 * n), _f32(guide_cur, 4 * n)
+    ap = None if ao_prev is None else _f32(ao_prev, n)
+    hp = None if hist_prev is None else _f32(hist_prev, n)
+    gp = None if guide_prev is None else _f32(guide_prev, 4 * n)
+    p = rt_ao_temporal_params(max_history, depth_tol, normal_cos)
+    ao, hist = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    st = lib.rt_host_ao_accumulate(width, height, ctypes.byref(p), _vp(cur), _vp(mo), _vp(gc), _vp(ap), _vp(hp),
+                                   _vp(gp), _vp(ao), _vp(hist))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_ao_accumulate")
+    return ao, hist
+
+
+def host_ao_atrous(width: int, height: int, ao_in, guide, iterations: int = 3, depth_tol: float = 0.02,
+                   normal_cos: float = 0.9):
+    """rt_host_ao_atrous: the AO filter's edge-aware a-trous blur on the host (no GPU). ao_in: width * height floats;
+    guide: (width * height, 4); iterations: 1..5 (steps 1, 2, 4, 8, 16). Returns width * height float32."""
+    n = width * height
+    a, g = _f32(ao_in, n), _f32(guide, 4 * n)
+    p = rt_ao_atrous_params(iterations, depth_tol, normal_cos)
+    out, tmp = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    st = lib.rt_host_ao_atrous(width, height, ctypes.byref(p), _vp(a), _vp(g), _vp(out), _vp(tmp))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_ao_atrous")
+    return out
 
 
 class Manipulator:
@@ -997,10 +1065,56 @@ class Context:
         self._check(self._lib.rt_dispatch_ao(self._h, width, height, rp, nr, ctypes.byref(p), _ptr(ao), stream),
                     "rt_dispatch_ao")
 
+    @staticmethod
+    def _plane(method: str, name: str, t, words: int):
+        """A filter plane's address: a contiguous tensor of exactly `words` 32-bit elements, a raw address, or None."""
+        if t is not None and not isinstance(t, int):
+            if t.element_size() != 4 or t.numel() != words or not t.is_contiguous():
+                raise ValueError(f"{method}: {name} must be a contiguous tensor of {words} 32-bit elements, got "
+                                 f"{t.numel()} of {t.element_size()} bytes")
+        return _ptr(t)
+
+    def denoise_guide(self, n: int, normal, depth, guide, depth_stride: int = 4, stream: Optional[int] = None):
+        """rt_denoise_guide: the AO filter's guide plane, (unit normal, depth) or four zeros per pixel. normal: n x 4
+        floats (dispatch_gbuffer's normal plane); depth: a raw address, or a tensor whose element 0 is the first
+        depth (motion.view(-1)[3:] for w_cur, hits.view(torch.float32) for t), read every depth_stride floats; guide: n
+        x 4 floats. Both frames' guides must come from w_cur when they feed ao_accumulate."""
+        d = depth if depth is None or isinstance(depth, int) else depth.data_ptr()
+        self._check(self._lib.rt_denoise_guide(self._h, n, self._plane("denoise_guide", "normal", normal, 4 * n), d,
+                                               depth_stride, self._plane("denoise_guide", "guide", guide, 4 * n),
+                                               stream), "rt_denoise_guide")
+
+    def ao_accumulate(self, width: int, height: int, ao_cur, motion, guide_cur, ao_out, hist_out, ao_prev=None,
+                      hist_prev=None, guide_prev=None, max_history: int = 32, depth_tol: float = 0.02,
+                      normal_cos: float = 0.9, stream: Optional[int] = None):
+        """rt_ao_accumulate: the current AO plane blended into the previous frame's, fetched through the motion plane
+        and tested against the previous guide; hist_out counts the frames a pixel has accumulated (0: no surface).
+        ao_prev, hist_prev, guide_prev all None: the first frame. ao_out may be ao_cur."""
+        n, m = width * height, "ao_accumulate"
+        p = rt_ao_temporal_params(max_history, depth_tol, normal_cos)
+        self._check(self._lib.rt_ao_accumulate(
+            self._h, width, height, ctypes.byref(p), self._plane(m, "ao_cur", ao_cur, n),
+            self._plane(m, "motion", motion, 4 * n), self._plane(m, "guide_cur", guide_cur, 4 * n),
+            self._plane(m, "ao_prev", ao_prev, n), self._plane(m, "hist_prev", hist_prev, n),
+            self._plane(m, "guide_prev", guide_prev, 4 * n), self._plane(m, "ao_out", ao_out, n),
+            self._plane(m, "hist_out", hist_out, n), stream), "rt_ao_accumulate")
+
+    def ao_atrous(self, width: int, height: int, ao_in, guide, ao_out, tmp=None, iterations: int = 3,
+                  depth_tol: float = 0.02, normal_cos: float = 0.9, stream: Optional[int] = None):
+        """rt_ao_atrous: `iterations` (1..5) passes of the edge-aware 5 x 5 a-trous filter, steps 1, 2, 4, ...; the
+        result lands in ao_out, ao_in is not written; tmp (width * height floats) is needed from two iterations on."""
+        n, m = width * height, "ao_atrous"
+        p = rt_ao_atrous_params(iterations, depth_tol, normal_cos)
+        self._check(self._lib.rt_ao_atrous(self._h, width, height, ctypes.byref(p), self._plane(m, "ao_in", ao_in, n),
+                                           self._plane(m, "guide", guide, 4 * n), self._plane(m, "ao_out", ao_out, n),
+                                           self._plane(m, "tmp", tmp, n), stream), "rt_ao_atrous")
+
     def pick(self, width: int, height: int, x: int, y: int) -> Optional[dict]:
         """What the camera ray through the centre of pixel (x, y) of a width x height frame hits: None on a miss, else
         t, instance_id, instance (index in the tlas_build list), hit_group, primitive, uv and the world normal (see
-        rt_gbuffer). One one-row G-buffer launch on torch's current stream, synchronised."""
+        rt_gbuffer). One one-row G-buffer launch on torch's current stream, synchronised. (torch's default stream has
+        the handle 0, which the library reads as "the context's stream", a non-blocking one: so the wait is for the
+        device, not for torch's stream, which the launch may not be on.)"""
         if not (0 <= x < width and 0 <= y < height):
             raise ValueError(f"pick: pixel ({x}, {y}) outside {width} x {height}")
         dev = f"cuda:{self.device}"
@@ -1011,7 +1125,7 @@ class Context:
         stream = torch.cuda.current_stream(self.device)
         self.dispatch_gbuffer(width, height, hits, uv, nrm, obj, rows=np.array([y], np.uint32),
                               stream=stream.cuda_stream)
-        stream.synchronize()
+        torch.cuda.synchronize(self.device)
         h = hits[x].cpu().numpy().view(np.uint32)
         if h[3] == 0:
             return None

@@ -335,6 +335,9 @@ struct rt_ctx {
   bool tlas_refit = false;
   // rt_set_motion_history: TLAS versions carry MotionRecs and refits snapshot the vertices they overwrite
   bool motion_on = false;
+  // rt_ao_atrous: which form of the iteration kernel runs (RT_ATROUS_FORM = direct | lds at context creation, for the
+  // A/B of tools/denoise_study.py and the tests; unset: the per-step choice of launch_ao_atrous)
+  int atrous_form = rt::kAtrousAuto;
   // rt_blas_refit: staging of the host variant's vertices (pinned, then device; grown on demand), the pinned
   // readback of the root box, the timing events of the refit's kernels
   void* refit_stage_host = nullptr;
@@ -664,6 +667,10 @@ rt_status rt_create(int hip_device, rt_ctx_t* out) {
   // the context's initial triangle test (rt_set_triangle_test): existing tools run in the watertight mode unchanged
   if (const char* ev = std::getenv("RT_TRIANGLE_TEST"))
     if (std::strcmp(ev, "watertight") == 0) c->tri_test = RT_TRIANGLE_TEST_WATERTIGHT;
+  if (const char* ev = std::getenv("RT_ATROUS_FORM"))
+    c->atrous_form = std::strcmp(ev, "direct") == 0 ? rt::kAtrousDirect
+                     : std::strcmp(ev, "lds") == 0  ? rt::kAtrousLds
+                                                    : rt::kAtrousAuto;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&c->d_stats, RT_STAT_COUNT * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(c->d_stats, 0, RT_STAT_COUNT * sizeof(unsigned long long)) != hipSuccess) {
@@ -2066,6 +2073,166 @@ rt_status rt_dispatch_ao(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* row
                           });
 }
 
+// ---- AO filter: the argument checks, shared by the device entry points and their host twins (align:
+// the device forms' 16-byte rule for 4-float planes; the host twins pass false) ---------------------------------
+namespace {
+
+bool misaligned(const void* p, size_t a) { return (uintptr_t)p % a != 0; }
+
+// W x H planes the filter's int tap coordinates and one-dimensional grids can address
+const char* denoise_frame_error(uint32_t W, uint32_t H, rt_status* st) {
+  *st = RT_E_INVALID;
+  if (W == 0 || H == 0) return "W or H is 0";
+  *st = RT_E_UNSUPPORTED;
+  if (W > (1u << 30) || H > (1u << 30) || (uint64_t)W * H >= (1ull << 31)) return "frame of 2^31 pixels or more";
+  return nullptr;
+}
+
+const char* guide_args_error(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
+                             const float* guide, bool align, rt_status* st) {
+  *st = RT_E_INVALID;
+  if (depth_stride < 1) return "depth_stride is 0";
+  if (n == 0) return nullptr;
+  if (n >= (1u << 31)) {  // the other passes' bound on W x H: the guide's one-dimensional grid stays in 32 bits
+    *st = RT_E_UNSUPPORTED;
+    return "2^31 pixels or more";
+  }
+  if (!normal) return "null normal plane";
+  if (!depth) return "null depth plane";
+  if (!guide) return "null guide plane";
+  if (misaligned(normal, align ? 16 : 4)) return "normal plane misaligned";
+  if (misaligned(depth, 4)) return "depth plane misaligned";
+  if (misaligned(guide, align ? 16 : 4)) return "guide plane misaligned";
+  // the normal plane may not be the output; the depth may lie inside either (motion + 3, hits), never inside the guide
+  if ((const void*)normal == (const void*)guide) return "guide is the normal plane";
+  const float* ge = guide + 4 * (size_t)n;
+  if (depth >= guide && depth < ge) return "depth lies inside the guide plane";
+  return nullptr;
+}
+
+const char* accumulate_args_error(uint32_t W, uint32_t H, const rt_ao_temporal_params* p, const float* ao_cur,
+                                  const float* motion, const float* guide_cur, const float* ao_prev,
+                                  const float* hist_prev, const float* guide_prev, const float* ao_out,
+                                  const float* hist_out, bool align, rt_status* st) {
+  if (const char* why = denoise_frame_error(W, H, st)) return why;
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (p->max_history < 1 || p->max_history > 1024) return "max_history outside 1..1024";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!(p->normal_cos >= -1.0f && p->normal_cos < 1.0f)) return "normal_cos outside [-1, 1)";
+  if (!ao_cur) return "null ao_cur";
+  if (!motion) return "null motion plane";
+  if (!guide_cur) return "null guide_cur";
+  if (!ao_out) return "null ao_out";
+  if (!hist_out) return "null hist_out";
+  const int nprev = (ao_prev != nullptr) + (hist_prev != nullptr) + (guide_prev != nullptr);
+  if (nprev != 0 && nprev != 3) return "ao_prev, hist_prev and guide_prev must be all given or all NULL";
+  const size_t a4 = align ? 16 : 4;
+  if (misaligned(motion, a4)) return "motion plane misaligned";
+  if (misaligned(guide_cur, a4)) return "guide_cur misaligned";
+  if (misaligned(guide_prev, a4)) return "guide_prev misaligned";
+  if (misaligned(ao_cur, 4) || misaligned(ao_prev, 4) || misaligned(hist_prev, 4) || misaligned(ao_out, 4) ||
+      misaligned(hist_out, 4))
+    return "a float plane is not aligned to 4 bytes";
+  if (ao_out == hist_out) return "ao_out is hist_out";
+  for (const float* o : {ao_out, hist_out}) {
+    if (nprev && (o == ao_prev || o == hist_prev || o == guide_prev)) return "an output is a previous-frame plane";
+    if (o == motion || o == guide_cur) return "an output is the motion plane or guide_cur";
+  }
+  if (hist_out == ao_cur) return "hist_out is ao_cur";
+  return nullptr;
+}
+
+const char* atrous_args_error(uint32_t W, uint32_t H, const rt_ao_atrous_params* p, const float* ao_in,
+                              const float* guide, const float* ao_out, const float* tmp, bool align, rt_status* st) {
+  if (const char* why = denoise_frame_error(W, H, st)) return why;
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (p->iterations < 1 || p->iterations > 5) return "iterations outside 1..5";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!(p->normal_cos >= -1.0f && p->normal_cos < 1.0f)) return "normal_cos outside [-1, 1)";
+  if (!ao_in) return "null ao_in";
+  if (!guide) return "null guide";
+  if (!ao_out) return "null ao_out";
+  if (!tmp && p->iterations > 1) return "null tmp with more than one iteration";
+  if (misaligned(guide, align ? 16 : 4)) return "guide misaligned";
+  if (misaligned(ao_in, 4) || misaligned(ao_out, 4) || misaligned(tmp, 4)) return "a float plane is not aligned to 4 bytes";
+  if (ao_in == guide || ao_in == ao_out || guide == ao_out) return "two planes are the same";
+  if (tmp && (tmp == ao_in || tmp == guide || tmp == ao_out)) return "tmp is another plane";
+  return nullptr;
+}
+
+rt::AoTemporal temporal_of(uint32_t W, uint32_t H, const rt_ao_temporal_params* p, const float* ao_cur,
+                           const float* motion, const float* guide_cur, const float* ao_prev, const float* hist_prev,
+                           const float* guide_prev, float* ao_out, float* hist_out) {
+  rt::AoTemporal a = {};
+  a.W = W, a.H = H;
+  a.max_history = (float)p->max_history;
+  a.depth_tol = p->depth_tol, a.normal_cos = p->normal_cos;
+  a.ao_cur = ao_cur, a.motion = motion, a.guide_cur = guide_cur;
+  a.ao_prev = ao_prev, a.hist_prev = hist_prev, a.guide_prev = guide_prev;
+  a.ao_out = ao_out, a.hist_out = hist_out;
+  return a;
+}
+
+// Where a-trous iteration k of n reads and writes: the planes ping-pong so that the last one lands in ao_out.
+void atrous_planes(uint32_t k, uint32_t n, const float* ao_in, float* ao_out, float* tmp, const float** src,
+                   float** dst) {
+  auto plane = [&](uint32_t it) { return (n - 1u - it) % 2u == 0u ? ao_out : tmp; };
+  *src = k == 0 ? ao_in : plane(k - 1u);
+  *dst = plane(k);
+}
+
+}  // namespace
+
+rt_status rt_denoise_guide(rt_ctx_t c, uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
+                           float* guide, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = guide_args_error(n, normal, depth, depth_stride, guide, true, &st))
+    return fail(c, st, std::string("rt_denoise_guide: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_denoise_guide(n, normal, depth, depth_stride, guide, pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "guide launch");
+  return RT_OK;
+}
+
+rt_status rt_ao_accumulate(rt_ctx_t c, uint32_t W, uint32_t H, const rt_ao_temporal_params* params,
+                           const float* ao_cur, const float* motion, const float* guide_cur, const float* ao_prev,
+                           const float* hist_prev, const float* guide_prev, float* ao_out, float* hist_out,
+                           void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = accumulate_args_error(W, H, params, ao_cur, motion, guide_cur, ao_prev, hist_prev, guide_prev,
+                                              ao_out, hist_out, true, &st))
+    return fail(c, st, std::string("rt_ao_accumulate: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_ao_accumulate(
+      temporal_of(W, H, params, ao_cur, motion, guide_cur, ao_prev, hist_prev, guide_prev, ao_out, hist_out),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "accumulate launch");
+  return RT_OK;
+}
+
+rt_status rt_ao_atrous(rt_ctx_t c, uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
+                       const float* guide, float* ao_out, float* tmp, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = atrous_args_error(W, H, params, ao_in, guide, ao_out, tmp, true, &st))
+    return fail(c, st, std::string("rt_ao_atrous: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipStream_t s = pick_stream(c, stream);
+  for (uint32_t k = 0; k < params->iterations; ++k) {
+    const float* src;
+    float* dst;
+    atrous_planes(k, params->iterations, ao_in, ao_out, tmp, &src, &dst);
+    const hipError_t e = rt::launch_ao_atrous(W, H, 1u << k, params->depth_tol, params->normal_cos, src, guide, dst,
+                                              c->atrous_form, s);
+    if (e != hipSuccess) return hip_fail(c, e, "a-trous launch");
+  }
+  return RT_OK;
+}
+
 rt_status rt_set_motion_history(rt_ctx_t c, int enable) {
   if (!c) return RT_E_INVALID;
   const bool on = enable != 0;
@@ -2323,6 +2490,74 @@ rt_status rt_host_ao_rays(const float* cam_rays, const float* t, const float* no
       r[0] = P.x, r[1] = P.y, r[2] = P.z, r[3] = params->tmin;
       r[4] = d.x, r[5] = d.y, r[6] = d.z, r[7] = params->radius;
     }
+  }
+  return RT_OK;
+}
+
+// Host services: the AO filter's three passes on host arrays, pixel by pixel through the functions of rt_device.hpp
+// the kernels of rt_denoise.hip call, after the device entry points' argument checks (less the 16-byte alignment).
+// Here for rt_host_shading_normals' reason. No context, no GPU call.
+rt_status rt_host_denoise_guide(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
+                                float* guide) {
+  rt_status st = RT_OK;
+  if (guide_args_error(n, normal, depth, depth_stride, guide, false, &st)) return st;
+  for (uint32_t i = 0; i < n; ++i) {
+    float nv[4], g[4];
+    rt::ld4(normal + 4 * (size_t)i, nv);
+    rt::denoise_guide_entry(rt::v3(nv[0], nv[1], nv[2]), depth[(size_t)i * depth_stride], g);
+    rt::st4(guide + 4 * (size_t)i, g);
+  }
+  return RT_OK;
+}
+
+rt_status rt_host_ao_accumulate(uint32_t W, uint32_t H, const rt_ao_temporal_params* params, const float* ao_cur,
+                                const float* motion, const float* guide_cur, const float* ao_prev,
+                                const float* hist_prev, const float* guide_prev, float* ao_out, float* hist_out) {
+  rt_status st = RT_OK;
+  if (accumulate_args_error(W, H, params, ao_cur, motion, guide_cur, ao_prev, hist_prev, guide_prev, ao_out, hist_out,
+                            false, &st))
+    return st;
+  const rt::AoTemporal a =
+      temporal_of(W, H, params, ao_cur, motion, guide_cur, ao_prev, hist_prev, guide_prev, ao_out, hist_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::ao_accumulate_pixel(a, x, y);
+  return RT_OK;
+}
+
+namespace {
+struct HostTap {  // rt_denoise.hip's GlobalTap on host arrays
+  const float* guide;
+  const float* in;
+  int x, y, s, W, H;
+  bool operator()(int dx, int dy, float q[4], float& v) const {
+    const int xx = x + dx * s, yy = y + dy * s;
+    if (xx < 0 || yy < 0 || xx >= W || yy >= H) return false;
+    const size_t t = (size_t)yy * (size_t)W + (size_t)xx;
+    rt::ld4(guide + 4 * t, q);
+    v = in[t];
+    return true;
+  }
+};
+}  // namespace
+
+rt_status rt_host_ao_atrous(uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
+                            const float* guide, float* ao_out, float* tmp) {
+  rt_status st = RT_OK;
+  if (atrous_args_error(W, H, params, ao_in, guide, ao_out, tmp, false, &st)) return st;
+  for (uint32_t k = 0; k < params->iterations; ++k) {
+    const float* src;
+    float* dst;
+    atrous_planes(k, params->iterations, ao_in, ao_out, tmp, &src, &dst);
+    const uint32_t s = 1u << k;
+    for (uint32_t y = 0; y < H; ++y)
+      for (uint32_t x = 0; x < W; ++x) {
+        const size_t i = (size_t)y * W + x;
+        float g[4];
+        rt::ld4(guide + 4 * i, g);
+        dst[i] = g[3] == 0.0f ? src[i]
+                              : rt::atrous_pixel(g, s, params->depth_tol, params->normal_cos,
+                                                 HostTap{guide, src, (int)x, (int)y, (int)s, (int)W, (int)H});
+      }
   }
   return RT_OK;
 }

@@ -1,0 +1,173 @@
+// rt_denoise.hip — the AO filter: what consumes the G-buffer's motion and normal planes.
+//
+//   k_denoise_guide     one pixel per lane: (normal, depth) -> the guide entry (unit normal, depth) or "no surface",
+//                       one 16-byte load and one 16-byte store.
+//   k_ao_accumulate     one pixel per lane over 32 x 8 tiles: the previous frame's AO and history length fetched
+//                       bilinearly at the reprojected position (rt_gbuffer_motion.motion), each tap tested against the
+//                       previous guide (one 16-byte load per tap), blended 1 / n into the current AO.
+//   k_ao_atrous_direct  one a-trous iteration, one pixel per lane over 32 x 8 tiles: each lane loads its 25 taps'
+//                       guide entries (16 bytes) and values (4 bytes) through L1 / L2.
+//   k_ao_atrous_lds     the same iteration with the taps staged: a workgroup takes a dense 32 x 8 tile of the step's
+//                       residue-class lattice (the pixels with x = rx, y = ry mod s: all 25 taps of such a pixel are
+//                       lattice neighbours), loads that tile's guide and values with a two-entry halo once (36 x 12
+//                       entries of 20 bytes), and filters from LDS. The guide is a [12][36] array of 16-byte entries
+//                       and the values a [12][36] array of floats: a half-wave reads 32 consecutive entries of one row
+//                       (512 contiguous bytes by ds_read_b128, every 16-lane group of which covers the 64 banks once;
+//                       128 contiguous bytes by ds_read_b32), whatever the tap offset, so no read conflicts.
+//
+// The arithmetic of all four is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel), which the
+// host twins in rt_api.cpp call too: the kernels differ from them in where a value is read, never in how it is used.
+// Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
+#include "rt_internal.hpp"
+
+namespace rt {
+
+namespace {
+
+constexpr uint32_t kTileW = 32, kTileH = 8, kHalo = 2;
+constexpr uint32_t kStageW = kTileW + 2 * kHalo, kStageH = kTileH + 2 * kHalo;  // 36 x 12
+
+__global__ __launch_bounds__(256) void k_denoise_guide(uint32_t n, const float* __restrict__ normal,
+                                                       const float* __restrict__ depth, uint32_t depth_stride,
+                                                       float* __restrict__ guide) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  float nv[4], g[4];
+  ld4(normal + 4 * (size_t)i, nv);
+  denoise_guide_entry(v3(nv[0], nv[1], nv[2]), depth[(size_t)i * depth_stride], g);
+  st4(guide + 4 * (size_t)i, g);
+}
+
+__global__ __launch_bounds__(256) void k_ao_accumulate(AoTemporal a, uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= a.W || y >= a.H) return;
+  ao_accumulate_pixel(a, x, y);
+}
+
+struct GlobalTap {  // a tap read from the planes, bounds-checked
+  const float* guide;
+  const float* in;
+  int x, y, s, W, H;
+  __device__ __forceinline__ bool operator()(int dx, int dy, float q[4], float& v) const {
+    const int xx = x + dx * s, yy = y + dy * s;
+    if (xx < 0 || yy < 0 || xx >= W || yy >= H) return false;
+    const size_t t = (size_t)yy * (size_t)W + (size_t)xx;
+    ld4(guide + 4 * t, q);
+    v = in[t];
+    return true;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_ao_atrous_direct(uint32_t W, uint32_t H, uint32_t s, float depth_tol,
+                                                          float normal_cos, const float* __restrict__ in,
+                                                          const float* __restrict__ guide, float* __restrict__ out,
+                                                          uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= W || y >= H) return;
+  const size_t i = (size_t)y * W + x;
+  float g[4];
+  ld4(guide + 4 * i, g);
+  if (g[3] == 0.0f) {
+    out[i] = in[i];
+    return;
+  }
+  out[i] = atrous_pixel(g, s, depth_tol, normal_cos, GlobalTap{guide, in, (int)x, (int)y, (int)s, (int)W, (int)H});
+}
+
+struct LdsTap {  // a tap read from the staged tile: an entry outside the frame was staged as "no surface"
+  const float4* g;
+  const float* v;
+  int at;  // the pixel's own entry
+  __device__ __forceinline__ bool operator()(int dx, int dy, float q[4], float& val) const {
+    const int e = at + dy * (int)kStageW + dx;
+    const float4 t = g[e];
+    q[0] = t.x, q[1] = t.y, q[2] = t.z, q[3] = t.w;
+    val = v[e];
+    return true;
+  }
+};
+
+// shift = log2(s); nbx = (lattice tiles per row) * s: block b is tile (b % nbx >> shift, b / nbx >> shift) of the
+// residue class (b % nbx & (s - 1), b / nbx & (s - 1)), so neighbouring blocks share the cache lines they stage from.
+__global__ __launch_bounds__(256) void k_ao_atrous_lds(uint32_t W, uint32_t H, uint32_t shift, float depth_tol,
+                                                       float normal_cos, const float* __restrict__ in,
+                                                       const float* __restrict__ guide, float* __restrict__ out,
+                                                       uint32_t nbx) {
+  __shared__ float4 sg[kStageH * kStageW];
+  __shared__ float sv[kStageH * kStageW];
+  const uint32_t s = 1u << shift;
+  const uint32_t bx = blockIdx.x % nbx, by = blockIdx.x / nbx;
+  const uint32_t rx = bx & (s - 1u), ry = by & (s - 1u);
+  const int lx0 = (int)((bx >> shift) * kTileW), ly0 = (int)((by >> shift) * kTileH);  // the tile's lattice origin
+  if ((uint32_t)lx0 * s + rx >= W || (uint32_t)ly0 * s + ry >= H) return;  // block-uniform: an empty tile
+  for (uint32_t e = threadIdx.x; e < kStageH * kStageW; e += 256u) {
+    const int li = lx0 + (int)(e % kStageW) - (int)kHalo, lj = ly0 + (int)(e / kStageW) - (int)kHalo;
+    const long long X = (long long)li * s + rx, Y = (long long)lj * s + ry;
+    float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float v = 0.0f;
+    if (li >= 0 && lj >= 0 && X < (long long)W && Y < (long long)H) {
+      const size_t t = (size_t)Y * W + (size_t)X;
+      q = *reinterpret_cast<const float4*>(guide + 4 * t);
+      v = in[t];
+    }
+    sg[e] = q;
+    sv[e] = v;
+  }
+  __syncthreads();
+  const uint32_t tx = threadIdx.x & 31u, ty = threadIdx.x >> 5;
+  const uint32_t x = ((uint32_t)lx0 + tx) * s + rx, y = ((uint32_t)ly0 + ty) * s + ry;
+  if (x >= W || y >= H) return;
+  const int at = (int)((ty + kHalo) * kStageW + tx + kHalo);
+  const size_t i = (size_t)y * W + x;
+  const float4 c = sg[at];
+  if (c.w == 0.0f) {
+    out[i] = sv[at];
+    return;
+  }
+  const float g[4] = {c.x, c.y, c.z, c.w};
+  out[i] = atrous_pixel(g, s, depth_tol, normal_cos, LdsTap{sg, sv, at});
+}
+
+uint32_t tiles(uint32_t n, uint32_t t) { return (n + t - 1u) / t; }
+
+}  // namespace
+
+hipError_t launch_denoise_guide(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
+                                float* guide, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_denoise_guide, dim3(tiles(n, 256u)), dim3(256), 0, stream, n, normal, depth, depth_stride,
+                     guide);
+  return hipGetLastError();
+}
+
+hipError_t launch_ao_accumulate(const AoTemporal& a, hipStream_t stream) {
+  const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
+  hipLaunchKernelGGL(k_ao_accumulate, dim3(tx * ty), dim3(256), 0, stream, a, tx);
+  return hipGetLastError();
+}
+
+hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol, float normal_cos, const float* in,
+                            const float* guide, float* out, int form, hipStream_t stream) {
+  // Measured per step on C2 at 1080p (tools/denoise_study.py): the staged form takes 0.75 - 0.90 x the
+  // direct form's time at steps 1 .. 8, beyond both p10 - p90 spreads; at step 16 its staging loads are 256 B apart
+  // (a cache line per entry) and it takes 1.31 x.
+  if (form == kAtrousAuto) form = s <= 8u ? kAtrousLds : kAtrousDirect;
+  if (form == kAtrousDirect) {
+    const uint32_t tx = tiles(W, kTileW), ty = tiles(H, kTileH);
+    hipLaunchKernelGGL(k_ao_atrous_direct, dim3(tx * ty), dim3(256), 0, stream, W, H, s, depth_tol, normal_cos, in,
+                       guide, out, tx);
+    return hipGetLastError();
+  }
+  uint32_t shift = 0;
+  while ((1u << shift) < s) ++shift;
+  // every residue class gets the tile count of the largest one; a class's tiles past its last pixel leave at once
+  const uint64_t nbx = (uint64_t)tiles(tiles(W, s), kTileW) * s, nby = (uint64_t)tiles(tiles(H, s), kTileH) * s;
+  if (nbx * nby > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(k_ao_atrous_lds, dim3((uint32_t)(nbx * nby)), dim3(256), 0, stream, W, H, shift, depth_tol,
+                     normal_cos, in, guide, out, (uint32_t)nbx);
+  return hipGetLastError();
+}
+
+}  // namespace rt

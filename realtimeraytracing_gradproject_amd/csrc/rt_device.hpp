@@ -899,4 +899,132 @@ RT_HD V3 ao_direction(V3 nf, V3 sph) {
   return dot(v, v) < 1e-4f ? nf : normalize(v);
 }
 
+// ------------------------------------------------------------------------------------------
+// AO filter (rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous): the per-pixel arithmetic, called by
+// the kernels of rt_denoise.hip per lane and by the rt_host_* twins per pixel. The AO section's rule: float32, no
+// contraction, IEEE quotients, only + - * / sqrtf, floorf, fabsf and comparisons, sums in the written order, so the
+// device and the host agree to the bit; tests/denoise_reference.py restates it in numpy.
+// ------------------------------------------------------------------------------------------
+
+// One 4-float entry of a guide, motion or normal plane: a single 16-byte load on the device (the device entry points
+// check the alignment), four floats on the host (host arrays need not be aligned to 16).
+RT_HD void ld4(const float* p, float o[4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float4 v = *reinterpret_cast<const float4*>(p);
+  o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
+#else
+  o[0] = p[0], o[1] = p[1], o[2] = p[2], o[3] = p[3];
+#endif
+}
+RT_HD void st4(float* p, const float v[4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+#else
+  p[0] = v[0], p[1] = v[1], p[2] = v[2], p[3] = v[3];
+#endif
+}
+
+// The guide entry of a pixel with G-buffer normal n and depth z: (normalize(n), z) where the AO pass's rule accepts n
+// and z is finite and > 0, else four zeros ("no surface").
+RT_HD void denoise_guide_entry(V3 n, float z, float out[4]) {
+  const bool valid = ao_normal_valid(n) && z <= 3.402823466e+38f && z > 0.0f;
+  const V3 nn = valid ? normalize(n) : v3(0.0f, 0.0f, 0.0f);
+  out[0] = nn.x, out[1] = nn.y, out[2] = nn.z, out[3] = valid ? z : 0.0f;
+}
+
+struct AoTemporal {  // rt_ao_accumulate's launch: rt_ao_temporal_params and the planes (prev planes all null or none)
+  uint32_t W, H;
+  float max_history, depth_tol, normal_cos;
+  const float *ao_cur, *motion, *guide_cur, *ao_prev, *hist_prev, *guide_prev;
+  float *ao_out, *hist_out;
+};
+
+// Pixel (x, y) of rt_ao_accumulate: the previous frame's AO and history length fetched bilinearly at the reprojected
+// position from the taps whose previous guide agrees with the expected previous depth (motion's w_prev) and with this
+// pixel's normal, then blended 1 / n into it. Reads its own ao_cur entry before it writes (ao_out may be ao_cur).
+RT_HD void ao_accumulate_pixel(const AoTemporal& a, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * a.W + x;
+  const float cur = a.ao_cur[i];
+  float g[4], m[4];
+  ld4(a.guide_cur + 4 * i, g);
+  if (g[3] == 0.0f) {
+    a.ao_out[i] = cur;
+    a.hist_out[i] = 0.0f;
+    return;
+  }
+  ld4(a.motion + 4 * i, m);
+  const float big = 3.402823466e+38f;
+  float sw = 0.0f, sa = 0.0f, sh = 0.0f;
+  if (a.ao_prev && fabsf(m[0]) <= big && fabsf(m[1]) <= big && m[2] > 0.0f) {
+    const float fx = (float)x + m[0], fy = (float)y + m[1];
+    if (fx > -1.0f && fx < (float)a.W && fy > -1.0f && fy < (float)a.H) {  // before any conversion to integer
+      const float xf = floorf(fx), yf = floorf(fy);
+      const float tx = fx - xf, ty = fy - yf;
+      const int x0 = (int)xf, y0 = (int)yf;
+      const V3 gn = v3(g[0], g[1], g[2]);
+      const float lim = a.depth_tol * m[2];
+      for (int k = 0; k < 4; ++k) {
+        const int dx = k & 1, dy = k >> 1;
+        const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
+        const int xx = x0 + dx, yy = y0 + dy;
+        if (w == 0.0f || xx < 0 || yy < 0 || xx >= (int)a.W || yy >= (int)a.H) continue;
+        const size_t t = (size_t)yy * a.W + (size_t)xx;
+        float q[4];
+        ld4(a.guide_prev + 4 * t, q);
+        if (q[3] == 0.0f || fabsf(q[3] - m[2]) > lim || dot(gn, v3(q[0], q[1], q[2])) < a.normal_cos) continue;
+        sw += w;
+        sa += w * a.ao_prev[t];
+        sh += w * a.hist_prev[t];
+      }
+    }
+  }
+  if (sw >= 0.01f) {
+    const float av = sa / sw;
+    const float n = minf(sh / sw + 1.0f, a.max_history);
+    // n == 1 (max_history 1, or a history of length 0): the current value itself, not av + (cur - av), which rounds
+    a.ao_out[i] = n == 1.0f ? cur : av + (1.0f / n) * (cur - av);
+    a.hist_out[i] = n;
+  } else {
+    a.ao_out[i] = cur;
+    a.hist_out[i] = 1.0f;
+  }
+}
+
+// The a-trous kernel's 1-D weights (B3 spline); the products of two of them are exact in float32.
+RT_HD float atrous_h(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
+
+// One iteration's value for a pixel with guide g (g[3] != 0). s: the step, a power of two; tap(dx, dy, q, v) gives the
+// guide entry and the input value of the tap at (x + dx s, y + dy s) and returns false where that lies outside the
+// frame (the kernels' two forms and the host twin differ in nothing but where it reads). dy outer, dx inner, ascending.
+template <typename Tap>
+RT_HD float atrous_pixel(const float g[4], uint32_t s, float depth_tol, float normal_cos, Tap tap) {
+  const V3 gn = v3(g[0], g[1], g[2]);
+  const float zden = (depth_tol * g[3]) * (float)s;
+  const float nden = 1.0f - normal_cos;
+  float sw = 0.0f, sa = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int dy = -2; dy <= 2; ++dy) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dx = -2; dx <= 2; ++dx) {
+      float q[4], v;
+      if (!tap(dx, dy, q, v)) continue;
+      float w = atrous_h(dy) * atrous_h(dx);
+      if (dx != 0 || dy != 0) {
+        if (q[3] == 0.0f) continue;
+        const float wz = maxf(0.0f, 1.0f - fabsf(q[3] - g[3]) / zden);
+        const float wn = minf(1.0f, maxf(0.0f, (dot(gn, v3(q[0], q[1], q[2])) - normal_cos) / nden));
+        const float e = wz * wn;
+        w = w * (e * e);
+      }
+      sw += w;
+      sa += w * v;
+    }
+  }
+  return sa / sw;
+}
+
 }  // namespace rt

@@ -199,6 +199,17 @@ hipError_t launch_trace_gbuffer(const SceneView& scene, const P& params, const u
 hipError_t launch_trace_ao(const SceneView& scene, const AoParams& params, const uint32_t* d_rows,
                            unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
 
+// --- AO filter (rt_denoise.hip) -----------------------------------------------
+// One launch each; no scene, no scratch. Their per-pixel arithmetic is rt_device.hpp's, shared with the host twins.
+hipError_t launch_denoise_guide(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
+                                float* guide, hipStream_t stream);
+hipError_t launch_ao_accumulate(const AoTemporal& a, hipStream_t stream);
+// One a-trous iteration of step s from `in` to `out`. form: kAtrousDirect (each lane loads its 25 taps) or
+// kAtrousLds (a workgroup stages a 36 x 12 tile of the step's residue-class lattice in LDS); kAtrousAuto picks per step.
+enum { kAtrousAuto = 0, kAtrousDirect = 1, kAtrousLds = 2 };
+hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol, float normal_cos, const float* in,
+                            const float* guide, float* out, int form, hipStream_t stream);
+
 // rank_stride_rows: rows from one rank's block of `gathered` to the next (0: rows_per_rank, one frame per block;
 // a batched gather holds several frames per rank block and passes their total)
 // in_bpp: bytes per pixel of the gathered strips (4 RGBA8, 3 RGB8: the alpha byte restored as 255); out is RGBA8
