@@ -32,7 +32,7 @@ extern "C" {
  * rt_set_motion_history, rt_dispatch_gbuffer_motion, rt_host_motion_project / _vectors and rt_gbuffer_motion, and
  * rt_dispatch_ao, rt_host_ao_rays and rt_ao_params, and rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous, their host
  * twins rt_host_denoise_guide, rt_host_ao_accumulate, rt_host_ao_atrous, rt_ao_temporal_params and
- * rt_ao_atrous_params. */
+ * rt_ao_atrous_params, and rt_tile_plan_probe with rt_tile_plan_args. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -252,7 +252,8 @@ rt_status rt_tile_balance_info_n(rt_ctx_t ctx, uint32_t* out, uint32_t n);
 rt_status rt_tile_balance_info(rt_ctx_t ctx, uint32_t out[RT_BALANCE_INFO_COUNT_V1]);
 /* Context diagnostics: out[0] device-wide synchronisations so far (builds, rebuilds, buffer growth: never a frame
  * launch on a steady pipeline), [1] tile-balance maps recycled for a new launch shape (only once every stream that
- * used them is idle and none of them was used in the last 64 shape lookups: host queries, no synchronisation), [2]
+ * used them is idle and the map was not used in the last 64 shape lookups — every launch that looks a shape up
+ * counts, whether it finds its map or not: host queries, no synchronisation), [2]
  * launches that ran the plain grid because no map was free (after a miss the table is rescanned only every 16 such
  * launches), [3] maps held, [4] recycled maps that went on to start a plan (recycling that paid off).
  * rt_ctx_counters_n fills min(n, RT_CTX_COUNTERS_V2) words; rt_ctx_counters exactly its 4 ([0..3]). */
@@ -260,6 +261,33 @@ rt_status rt_tile_balance_info(rt_ctx_t ctx, uint32_t out[RT_BALANCE_INFO_COUNT_
 #define RT_CTX_COUNTERS_V2 5
 rt_status rt_ctx_counters_n(rt_ctx_t ctx, uint64_t* out, uint32_t n);
 rt_status rt_ctx_counters(rt_ctx_t ctx, uint64_t out[RT_CTX_COUNTERS]);
+/* Diagnostics (tests): one run of the tile balance's plan kernel on given costs, so the plan can be compared with a
+ * restatement of its rule (tests/plan_reference.py). The knobs are the plan's own: ntiles wave slots of the plain
+ * grid (1 .. 32768), extra_cap items the list may add, slots the GPU's wave slots the load bound divides by,
+ * kmax_code the finest layout (0 .. 3: none, 4, 16, 64 parts), force 0 adaptive or 1 .. 4 the forced layouts of
+ * rt_set_tile_balance 2 .. 5, split / front / prio / min_gain as RT_BALANCE_SPLIT, RT_BALANCE_FRONT,
+ * RT_BALANCE_PRIO and the plan's own time in ticks, and the plain grid's geometry (used by forced layout 3 only). */
+typedef struct {
+  uint32_t ntiles, extra_cap, slots, kmax_code, force, split, front, prio, min_gain;
+  uint32_t waves_per_frame, grid_x, wx, wy, wl;
+} rt_tile_plan_args;
+/* The summary of one plan: [0] items, [1] tiles split, [2] the extra items the first threshold asked for, [3] the
+ * costliest and [4] the mean tile (10-ns ticks), [5] the split threshold (0xffffffff: none), [6] plans (1), [7] pays,
+ * [8] tiles the list fails to cover exactly once, [9] the first one, [10] its check word, [11..13] the kernel's
+ * phases in ticks, [14] coherent (every measured split useless: nothing split), [15] items refused for want of
+ * budget, [16] 1 if the plan therefore fell back to the plain list, [17] slots. */
+#define RT_TILE_PLAN_STATS 18
+/* cost: 2 * ntiles words in the recording kernel's format (per tile: the last whole wave's ticks, bit 31 "parts ran
+ * since"; the costliest part of the last split, ticks << 2 | layout 1 .. 3, or 0). The call uploads them, runs the
+ * plan once on the context's stream with the cover check on, waits for that stream only, and returns the list as
+ * stored (plan_out[0] the item count, item i at word 1 + its XCD-major address: 1 + 8 * wl * ceil(ceil((ntiles +
+ * extra_cap) / wl) / 8) words in all, the words no item occupies 0), the summary, and the cost words as the plan
+ * left them (cost_out, 2 * ntiles words: the part word of every tile it split is cleared). RT_E_INVALID, before any
+ * GPU work and with the outputs untouched: a null pointer, ntiles 0 or above 32768, extra_cap above 64 x 32768,
+ * wl 0 or above 16, kmax_code above 3, force above 4 (or 3 with waves_per_frame, grid_x or wx 0), plan_words or
+ * stats_words too small. Reads and changes nothing else of the context: no cost map, no counter, no launch. */
+rt_status rt_tile_plan_probe(rt_ctx_t ctx, const rt_tile_plan_args* args, const uint32_t* cost, uint32_t* plan_out,
+                             uint32_t plan_words, uint32_t* stats_out, uint32_t stats_words, uint32_t* cost_out);
 /* The ray / triangle test of the trace kernels. DXR's fixed-function TraceRay is watertight: no ray passes between
  * two triangles that share an edge. The default float32 Moller-Trumbore test is not (it stores v0, v1 - v0, v2 - v0,
  * and v0 + e1 is not v1 in float32: tests/golden/seam_leaks.json pins the gap); it is the pinned, bit-checked path

@@ -32,6 +32,10 @@ RT_SHADE_REF, RT_SHADE_LAMBERT_SHADOW, RT_SHADE_PRIMARY = 0, 1, 2
 RT_SCHED_PACKET, RT_SCHED_LANE = 0, 1
 RT_TRIANGLE_TEST_MOLLER_TRUMBORE, RT_TRIANGLE_TEST_WATERTIGHT = 0, 1
 RT_BALANCE_INFO_COUNT = 20
+RT_TILE_PLAN_STATS = 18
+TILE_PLAN_STAT_NAMES = ("nitems", "nsplit", "want_extra", "max_cost", "mean_cost", "threshold", "plans", "pays", "bad",
+                        "first_bad_tile", "first_bad_word", "phase_load_ticks", "phase_budget_ticks",
+                        "phase_place_ticks", "coherent", "refused", "refused_plans", "slots")
 RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH, RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES = 0x04, 0x10
 RT_RAY_FLAG_CULL_FRONT_FACING_TRIANGLES = 0x20
 STAT_NAMES = ("primary_rays", "shadow_rays", "aabb_tests", "tri_tests", "instance_entries",
@@ -97,6 +101,12 @@ class rt_ao_atrous_params(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
 
 
+class rt_tile_plan_args(ctypes.Structure):
+    """include/rt_api.h rt_tile_plan_args: the plan kernel's knobs for rt_tile_plan_probe."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("ntiles", "extra_cap", "slots", "kmax_code", "force", "split", "front",
+                                               "prio", "min_gain", "waves_per_frame", "grid_x", "wx", "wy", "wl")]
+
+
 class rt_manipulator(ctypes.Structure):
     """include/rt_api.h rt_manipulator: nv_helpers_dx12::Manipulator state (manipulator.h:124-144)."""
     _fields_ = [("pos", ctypes.c_float * 3), ("interest", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
@@ -137,6 +147,7 @@ SIGNATURES = [
     ("rt_tile_balance_info_n", _I, [_P, _UP, _U32]),
     ("rt_ctx_counters", _I, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("rt_ctx_counters_n", _I, [_P, ctypes.POINTER(ctypes.c_uint64), _U32]),
+    ("rt_tile_plan_probe", _I, [_P, ctypes.POINTER(rt_tile_plan_args), _UP, _UP, _U32, _UP, _U32, _UP]),
     ("rt_set_triangle_test", _I, [_P, _I]),
     ("rt_set_stats", _I, [_P, _I]),
     ("rt_dispatch_rays", _I, [_P, _U32, _U32, _P, _U32, _P, _P, _P]),
@@ -965,6 +976,23 @@ class Context:
         self._check(self._lib.rt_ctx_counters_n(self._h, out, 5), "rt_ctx_counters_n")
         return dict(zip(("device_syncs", "balance_recycled", "balance_full", "balance_maps", "balance_recycled_planned"),
                         list(out)))
+
+    def tile_plan_probe(self, costs, **knobs):
+        """rt_tile_plan_probe (diagnostics): the plan kernel once on `costs` (2 * ntiles words) with rt_tile_plan_args'
+        knobs as keywords. Returns (the list as stored: uint32 array, the summary: dict, the costs as the plan left
+        them: uint32 array)."""
+        a = rt_tile_plan_args(**knobs)
+        cost = np.ascontiguousarray(costs, dtype=np.uint32)
+        if cost.size != 2 * a.ntiles:
+            raise ValueError("tile_plan_probe: costs must hold 2 * ntiles words")
+        groups = -(-(a.ntiles + a.extra_cap) // max(1, a.wl))
+        plan = np.zeros(1 + -(-groups // 8) * 8 * a.wl, dtype=np.uint32)
+        stats = np.zeros(RT_TILE_PLAN_STATS, dtype=np.uint32)
+        left = np.zeros_like(cost)
+        self._check(self._lib.rt_tile_plan_probe(self._h, ctypes.byref(a), cost.ctypes.data_as(_UP),
+                                                 plan.ctypes.data_as(_UP), plan.size, stats.ctypes.data_as(_UP),
+                                                 stats.size, left.ctypes.data_as(_UP)), "rt_tile_plan_probe")
+        return plan, dict(zip(TILE_PLAN_STAT_NAMES, (int(x) for x in stats))), left
 
     def set_stats(self, on: bool):
         self._check(self._lib.rt_set_stats(self._h, 1 if on else 0), "rt_set_stats")

@@ -6,6 +6,8 @@
 #include <chrono>
 #include <cmath>
 #include <functional>
+#include <memory>
+#include <new>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -318,6 +320,7 @@ struct rt_ctx {
   uint32_t bal_backoff = 0;  // launches of unknown shapes left before the next recycling scan
   BalanceMap* bal_last = nullptr;
   ScratchRing plans;
+  ScratchSlot probe;  // rt_tile_plan_probe's device buffer (summary, costs, list; grown on demand)
   // scene pools read by the trace kernels (rebuilt by every rt_tlas_build)
   rt::Bvh4Node* pool_nodes = nullptr;
   rt::TriRec* pool_tris = nullptr;
@@ -693,6 +696,7 @@ rt_status rt_destroy(rt_ctx_t c) {
   for (auto& sl : c->rows.slots) slot_release(sl);
   for (auto& sl : c->ovf.slots) slot_release(sl);
   for (auto& sl : c->plans.slots) slot_release(sl);
+  slot_release(c->probe);
   for (auto& m : c->bal) m.release();
   if (c->raster_ev) (void)hipEventDestroy(c->raster_ev);
   if (c->pool_nodes) (void)hipFree(c->pool_nodes);
@@ -1447,11 +1451,14 @@ static uint32_t plan_slots(rt_ctx* c, const rt::SceneView& sv) {
 static BalanceMap* balance_map(rt_ctx* c, uint32_t W, uint32_t nrows, const uint32_t* d_rows, uint64_t rows_gen,
                                uint32_t nframes, uint32_t ntiles, hipStream_t s, bool forced, hipError_t* err) {
   *err = hipSuccess;
+  // every lookup counts on the clock, a miss on a full table too: a clock that stood still while new shapes missed
+  // left every map "recently used" for good, and the balance off for the rest of the context
+  ++c->bal_clock;
   BalanceMap* lru = nullptr;
   for (BalanceMap& m : c->bal) {
     if (m.W == W && m.nrows == nrows && m.rows == d_rows && m.rows_gen == rows_gen && m.nframes == nframes &&
         m.tile_rows == c->tile_rows && m.spp == c->fp.spp_side && m.ntiles == ntiles) {
-      m.tick = ++c->bal_clock;
+      m.tick = c->bal_clock;
       return &m;
     }
     if (!lru || m.tick < lru->tick) lru = &m;
@@ -1518,7 +1525,7 @@ static BalanceMap* balance_map(rt_ctx* c, uint32_t W, uint32_t nrows, const uint
   // every tile above max(L, 0.35 x the costliest): rank 0's C4 share of 4 went from 120 to 167 us per launch,
   // profiles/r04_share_trace_C4_n4.txt.)
   m->extra_cap = ntiles / c->bal_budget + 64u;
-  m->tick = ++c->bal_clock;
+  m->tick = c->bal_clock;
   if (recycled) {
     if ((*err = hipMemsetAsync(m->cost, 0, (size_t)ntiles * 8, s)) != hipSuccess) return nullptr;
     std::memset(m->stats, 0, sizeof(rt::PlanStats));
@@ -1907,6 +1914,70 @@ rt_status rt_raster_draw(rt_ctx_t c, const rt_blas_t* draws, uint32_t ndraws, co
   HIPCHK(c, hipEventRecord(c->raster_ev, s), "rt_raster_draw: record");
   c->raster_stream = s;
   c->raster_pending = true;
+  return RT_OK;
+}
+
+// Diagnostics: k_tile_plan once on the caller's costs, in a buffer of its own (the summary, the costs, the list and
+// the cover check's scratch). Nothing of the frame path is read or written: no cost map, no counter, not the last
+// launch shape that rt_tile_balance_info reports.
+rt_status rt_tile_plan_probe(rt_ctx_t c, const rt_tile_plan_args* p, const uint32_t* cost, uint32_t* plan_out,
+                             uint32_t plan_words, uint32_t* stats_out, uint32_t stats_words, uint32_t* cost_out) {
+  static_assert(sizeof(rt::PlanStats) == RT_TILE_PLAN_STATS * sizeof(uint32_t), "rt_tile_plan_probe's summary words");
+  if (!c) return RT_E_INVALID;
+  if (!p || !cost || !plan_out || !stats_out || !cost_out)
+    return fail(c, RT_E_INVALID, "rt_tile_plan_probe: null argument");
+  if (p->ntiles == 0 || p->ntiles > rt::kPlanMaxTiles || p->extra_cap > 64u * rt::kPlanMaxTiles || p->wl == 0 ||
+      p->wl > 16u || p->kmax_code > 3u || p->force > 4u)
+    return fail(c, RT_E_INVALID, "rt_tile_plan_probe: ntiles 1 .. 32768, extra_cap <= 64 x 32768, wl 1 .. 16, "
+                                 "kmax_code 0 .. 3, force 0 .. 4");
+  if (p->force == 3u && (p->waves_per_frame == 0 || p->grid_x == 0 || p->wx == 0))
+    return fail(c, RT_E_INVALID, "rt_tile_plan_probe: forced layout 3 needs the plain grid's geometry");
+  const uint32_t n = p->ntiles, xw = rt::plan_xwords(n + p->extra_cap, p->wl);
+  if (plan_words < 1u + xw || stats_words < RT_TILE_PLAN_STATS)
+    return fail(c, RT_E_INVALID, "rt_tile_plan_probe: output too short");
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  // [summary, padded to 32 words | costs, 2 n | list, 1 + xw | the cover check's scratch, 3 n]
+  const size_t list_words = 1u + (size_t)xw, words = 32u + 2u * (size_t)n + list_words + 3u * (size_t)n;
+  HIPCHK(c, slot_reserve(c->probe, words * 4), "hipMalloc(tile plan probe)");
+  uint32_t* d = (uint32_t*)c->probe.buf;
+  rt::PlanArgs a;
+  a.stats = (rt::PlanStats*)d;
+  a.cost = d + 32;
+  a.plan = a.cost + 2u * (size_t)n;
+  a.ntiles = n;
+  a.extra_cap = p->extra_cap;
+  a.slots = p->slots;
+  a.kmax_code = p->kmax_code;
+  a.force = p->force;
+  a.split = p->split;
+  a.front = p->front;
+  a.check = 1;
+  a.min_gain = p->min_gain;
+  a.prio = p->prio;
+  a.waves_per_frame = p->waves_per_frame;
+  a.grid_x = p->grid_x;
+  a.wx = p->wx;
+  a.wy = p->wy;
+  a.wl = p->wl;
+  // into a buffer of the call's own, so a failure leaves the caller's outputs untouched
+  const size_t back_words = 2u * (size_t)n + list_words;
+  std::unique_ptr<uint32_t[]> h(new (std::nothrow) uint32_t[RT_TILE_PLAN_STATS + back_words]);
+  if (!h) return fail(c, RT_E_OOM, "rt_tile_plan_probe: host buffer");
+  hipError_t e = hipMemsetAsync(d, 0, 32 * 4, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(a.cost, cost, (size_t)n * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(a.plan, 0, list_words * 4, s);
+  if (e == hipSuccess) e = rt::launch_tile_plan(a, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h.get(), d, RT_TILE_PLAN_STATS * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(h.get() + RT_TILE_PLAN_STATS, a.cost, back_words * 4, hipMemcpyDeviceToHost, s);
+  // this stream only; also after a failure, so nothing enqueued still reads `cost` or writes h
+  const hipError_t es = hipStreamSynchronize(s);
+  HIPCHK(c, e, "rt_tile_plan_probe: copies and plan launch");
+  HIPCHK(c, es, "rt_tile_plan_probe: wait for the plan");
+  std::memcpy(stats_out, h.get(), RT_TILE_PLAN_STATS * 4);
+  std::memcpy(cost_out, h.get() + RT_TILE_PLAN_STATS, (size_t)n * 8);
+  std::memcpy(plan_out, h.get() + RT_TILE_PLAN_STATS + 2u * (size_t)n, list_words * 4);
   return RT_OK;
 }
 

@@ -159,15 +159,15 @@ struct PlanStats {
 struct PlanArgs {
   uint32_t* cost;         // per wave slot of the plain grid, 2 words: the last whole wave's time (ticks), the
                           // costliest part of the last split (time << 2 | layout; cleared here when splitting)
-  uint32_t* plan;         // out: [0] item count, [1 ..] items (ntiles + extra_cap words), then the cover check's
-                          // scratch (3 ntiles words): 1 + 4 ntiles + extra_cap words in all
+  uint32_t* plan;         // out: [0] item count, [1 ..] items (plan_xwords(ntiles + extra_cap, wl) words, item i at
+                          // plan_xaddr(i)), then the cover check's scratch (3 ntiles words)
   PlanStats* stats;       // host-mapped, or null
   uint32_t ntiles;        // wave slots of the plain grid, every frame of the launch
   uint32_t extra_cap;     // items beyond ntiles the launch's grid has waves for
   uint32_t slots;         // wave slots of the GPU for the list's trace kernel: its occupancy (waves per CU, from the
                           // runtime for the instantiation launched) x CUs (trace_wave_slots)
   uint32_t kmax_code;
-  uint32_t force;         // 0 adaptive; 1 / 2 / 3 forced layouts (tests)
+  uint32_t force;         // 0 adaptive; 1 / 2 / 3 / 4 forced layouts (tests: plan_forced)
   uint32_t split;         // adaptive: split tiles (0: order only)
   uint32_t front;         // adaptive: items estimated above front / 16 x the load bound go first (0: tile order)
   uint32_t check;         // diagnostics: verify the list covers every tile once (PlanStats::bad)

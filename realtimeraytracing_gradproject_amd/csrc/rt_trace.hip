@@ -2238,17 +2238,23 @@ hipError_t launch_trace_frame(const SceneView& sc, const FrameParams& fp, const 
 // the frame, profiles/r03_wave_times_C4.txt). The packet kernel leaves two words per tile (FrameParams::cost): the
 // time of its last whole wave (w), and the costliest part of its last split (p, time << 2 | layout). From them:
 // the load bound L = sum(w) / the GPU's wave slots. The plan pays only while the costliest tile outlasts L (it
-// then forms the launch's tail); otherwise the list is the plain grid's order. When it pays, T = max(L, 0.35 x the
-// costliest tile): a tile above T is traced as 4 parts (2 x 2 sub-rectangles) when 0.55 x its time fits T, else
-// as 16 — unless its last split measured a part above 0.8 x the whole (coherent rays: the parts walk nearly the
-// whole tile's nodes each, so splitting only adds waves), which keeps it whole. The items are then laid out in two
+// then forms the launch's tail); otherwise the list is the plain grid's order. When it pays, T = max(L, the finest
+// split's floor: 0.35 x the costliest tile, 0.21 x where 64 parts are allowed): a tile above T is traced as 4 parts
+// (2 x 2 sub-rectangles) when 0.55 x its time fits T, else as 16 when 0.35 x fits or 16 is the finest allowed, else
+// as 64 — unless its last split measured a part above 0.8 x the whole (coherent rays: the parts walk nearly the
+// whole tile's nodes each, so splitting only adds waves), which keeps it whole. "The whole" there is the recorded
+// whole-wave time w (16 bits, capped) against the part as the snapshot keeps it (80-ns units, capped), also when
+// the tile's current cost is estimated from that part: the estimate is the part times a constant, so a ratio to it
+// would say nothing. The shape-wide census of useless splits (below) judges the raw ticks instead; the two can
+// differ by the quantisation and the caps (tests/plan_reference.py pins both). The items are then laid out in two
 // classes, those estimated above a fraction of L first, each class in tile order: the long waves start at the
 // front, and neighbouring waves still trace neighbouring tiles (they share the BVH nodes in the scalar cache and
 // L2; a strict longest-first order scattered them and lost more than the tail it saved, profiles/
 // r04_balance_ab_v1.txt). The list is always a valid cover (each tile once, or each of its parts once) whatever
 // the costs hold: the image never depends on it, only the schedule. Items beyond the grid's budget are refused by
 // raising T. (tools/split_study.py models the split on the oracle's packet fetches.) The north star's "wavefront
-// ballot/prefix-sum" appears here as the block scan that places each item.
+// ballot/prefix-sum" appears here as the block scan that places each item. tests/plan_reference.py restates all of
+// it one tile at a time, and tests/test_gpu_tile_plan.py holds this kernel to it word for word (rt_tile_plan_probe).
 // ------------------------------------------------------------------------------------------
 #ifndef RT_PLAN_THREADS
 #define RT_PLAN_THREADS 1024  // the plan workgroup (A/B: 512 needs 2 free wave slots per SIMD to dispatch, not 4)
@@ -2427,7 +2433,9 @@ __global__ __launch_bounds__(kPlanThreads) void k_tile_plan(PlanArgs a) {
       const uint64_t tot = block_sum64(ex, s_red);
       if (iter == 0) want = (uint32_t)(tot < 0xffffffffull ? tot : 0xffffffffull);
       if (tot <= a.extra_cap) break;
-      T = (iter < 23 && T < 65535u) ? T + T / 4u + 1u : 0xffffffffu;  // the last resort: no tile split
+      // the last resort (no tile split) is never taken: T starts at 0.21 x mx or above and 0.21 x 1.25^7 > 1, so after
+      // at most 7 raises no tile exceeds T and the count is 0 (the reference asserts it on every case)
+      T = (iter < 23 && T < 65535u) ? T + T / 4u + 1u : 0xffffffffu;
     }
   }
   const uint64_t t_budget = __builtin_amdgcn_s_memrealtime();

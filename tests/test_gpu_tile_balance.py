@@ -283,3 +283,39 @@ def test_load_bound_slots_match_the_hardware_residency():
     peak = int(np.cumsum(ev_d[order]).max())
     assert peak == slots, (peak, slots)
     c.close()
+
+
+def test_full_table_recycles_again_when_the_workload_moves_to_a_new_shape():
+    """a map is recycled only when it was not used in the last 64 shape lookups, and the clock behind that
+    count advanced only on hits and on new or recycled maps. With all 32 maps used once (ticks 1 .. 32) and the
+    workload moving to a 33rd shape, every lookup missed, the clock stood still, no map ever qualified and the
+    balance stayed off for the rest of the context. Every lookup counts now: the window of 64 lookups, a rescan of
+    the table every 16 misses and the 2 launches a fresh map needs before its first plan make under 100 launches;
+    the test allows 200. Each launch is synchronised, so every map is idle whenever the table is scanned."""
+    c = rt.Context(0)
+    base = scenes.config("C4")
+    scenes.upload(c, base.with_size(64, 32))
+    s = torch.cuda.Stream()
+    H = 32
+    # the 32 shapes that fill the table are all wider than the 33rd, so every map's cost buffer fits it
+    for k in range(1, 33):
+        spec = base.with_size(64 + 8 * k, H)
+        c.set_camera(spec.camera_buffer())
+        render(c, spec, stream=s)
+        s.synchronize()
+    filled = c.counters()
+    assert filled["balance_maps"] == 32 and filled["balance_recycled"] == 0, filled
+    spec = base.with_size(64, H)
+    c.set_camera(spec.camera_buffer())
+    launches = 0
+    for launches in range(1, 201):
+        g8, _ = render(c, spec, stream=s)
+        s.synchronize()
+        now = c.counters()
+        if now["balance_recycled"] >= 1 and now["balance_recycled_planned"] >= 1:
+            break
+    print("after", launches, "launches of the 33rd shape:", now)
+    assert now["balance_recycled"] >= 1 and now["balance_recycled_planned"] >= 1, (launches, now)
+    o8, _, _ = oracle.Scene(spec).render_spec(spec, nthreads=8, want_float=False, schedule=1)
+    assert np.array_equal(g8.cpu().numpy(), o8), bad_tiles(g8.cpu().numpy(), o8)
+    c.close()
