@@ -51,7 +51,7 @@ HDRS      := include/rt_api.h $(SRC)/rt_device.hpp $(SRC)/rt_internal.hpp $(SRC)
 #             device counters (both in tests/test_gpu_pop_cull.py)
 VDIR      := $(LIBDIR)/variants
 VSRCS     := $(SRC)/rt_api.cpp $(SRC)/rt_comm.cpp $(SRC)/rt_lbvh.hip $(SRC)/rt_trace.hip $(SRC)/rt_raster.hip \
-             $(SRC)/rt_denoise.hip $(SRC)/rt_host.cpp $(HDRS) tools/build_variant.sh
+             $(SRC)/rt_denoise.hip $(SRC)/rt_upscale.hip $(SRC)/rt_host.cpp $(HDRS) tools/build_variant.sh
 VARIANTS  := n1 n1root rays2 alt wavetimes ldstop popcullblas popcullstats
 VLIBS     := $(foreach v,$(VARIANTS),$(VDIR)/$(v)/librtamd.so)
 DEFS_n1        := -DRT_SHADOW_COMPACT=1 -DRT_HYBRID_T=8
@@ -91,7 +91,7 @@ $(BUILD)/rt_host.o: $(SRC)/rt_host.cpp include/rt_api.h | $(BUILD)
 	g++ $(CXXFLAGS) -c $< -o $@
 
 $(LIB): $(BUILD)/rt_api.o $(BUILD)/rt_comm.o $(BUILD)/rt_host.o $(BUILD)/rt_lbvh.o $(BUILD)/rt_trace.o $(BUILD)/rt_raster.o \
-        $(BUILD)/rt_denoise.o | $(LIBDIR)
+        $(BUILD)/rt_denoise.o $(BUILD)/rt_upscale.o | $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
 $(APP): $(SRC)/host/rt_app.cpp $(wildcard $(SRC)/host/*.hpp) $(LIB) | $(LIBDIR)
@@ -143,7 +143,7 @@ $(ASAN)/rt_host.o: $(SRC)/rt_host.cpp include/rt_api.h | $(ASAN)
 	g++ -O1 -g -std=c++17 -fPIC -ffp-contract=off -Wall $(SANFLAGS) -c $< -o $@
 
 $(ASAN)/librtamd.so: $(BUILD)/rt_api.o $(BUILD)/rt_comm.o $(ASAN)/rt_host.o $(BUILD)/rt_lbvh.o $(BUILD)/rt_trace.o $(BUILD)/rt_raster.o \
-                     $(BUILD)/rt_denoise.o
+                     $(BUILD)/rt_denoise.o $(BUILD)/rt_upscale.o
 	g++ -shared $(SANFLAGS) -o $@ $^ -L$(ROCM)/lib -lamdhip64 -ldl -Wl,-rpath,$(ROCM)/lib
 
 $(ASAN)/liboracle.so: oracle/rt_oracle.c oracle/rt_raster_oracle.c oracle/rt_oracle.h | $(ASAN)
@@ -166,7 +166,7 @@ $(ASAN)/ao_rays_asan.o: tools/ao_rays_asan.cpp include/rt_api.h | $(ASAN)
 	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
 
 ASAN_API_OBJS := $(ASAN)/rt_api.o $(BUILD)/rt_comm.o $(BUILD)/rt_host.o $(BUILD)/rt_lbvh.o $(BUILD)/rt_trace.o $(BUILD)/rt_raster.o \
-                 $(BUILD)/rt_denoise.o
+                 $(BUILD)/rt_denoise.o $(BUILD)/rt_upscale.o
 $(ASAN)/ao_rays_check: $(ASAN)/ao_rays_asan.o $(ASAN_API_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
@@ -181,10 +181,20 @@ $(ASAN)/denoise_asan.o: tools/denoise_asan.cpp include/rt_api.h | $(ASAN)
 $(ASAN)/denoise_check: $(ASAN)/denoise_asan.o $(ASAN_API_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
+# the same for the upscaler's host twin and the jitter helpers (rt_host_upscale, rt_camera_jitter, rt_jitter_halton):
+#   make asan-upscale && build/asan/upscale_check
+asan-upscale: $(ASAN)/upscale_check
+
+$(ASAN)/upscale_asan.o: tools/upscale_asan.cpp include/rt_api.h | $(ASAN)
+	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
+
+$(ASAN)/upscale_check: $(ASAN)/upscale_asan.o $(ASAN_API_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
+
 $(ASAN):
 	mkdir -p $@
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VDIR)
 
-.PHONY: all clean ref asan asan-ao asan-denoise
+.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale

@@ -32,7 +32,8 @@ extern "C" {
  * rt_set_motion_history, rt_dispatch_gbuffer_motion, rt_host_motion_project / _vectors and rt_gbuffer_motion, and
  * rt_dispatch_ao, rt_host_ao_rays and rt_ao_params, and rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous, their host
  * twins rt_host_denoise_guide, rt_host_ao_accumulate, rt_host_ao_atrous, rt_ao_temporal_params and
- * rt_ao_atrous_params, and rt_tile_plan_probe with rt_tile_plan_args. */
+ * rt_ao_atrous_params, and rt_tile_plan_probe with rt_tile_plan_args, and rt_upscale, rt_host_upscale,
+ * rt_upscale_params, rt_camera_jitter and rt_jitter_halton. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -538,6 +539,70 @@ typedef struct { uint32_t iterations; float depth_tol; float normal_cos; } rt_ao
 rt_status rt_ao_atrous(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
                        const float* guide, float* ao_out, float* tmp, void* hip_stream);
 
+/* ---- Temporal upscaler of the colour frame --------------------------------------------------------
+ * rt_upscale reconstructs a W x H display frame from a jittered w x h render (rt_dispatch_rays' rgba32f_dev under a
+ * camera from rt_camera_jitter), that render's motion plane (rt_gbuffer_motion.motion under the same camera) and its
+ * own previous outputs. One kernel, asynchronous on hip_stream (NULL: the context's stream); it needs a context only
+ * (no scene, camera or TLAS), allocates nothing and never waits. Whole row-major planes only, for the AO filter's
+ * reason; a tiled multi-GPU caller upscales after assembly. The AO filter's arithmetic rules hold (float32, no
+ * contraction, IEEE quotients, only + - * /, floorf, fabsf and comparisons, minf / maxf as defined there, sums in the
+ * order written), so the device equals rt_host_upscale bit for bit.
+ *
+ * jitter_cur / jitter_prev: the (jx, jy) given to rt_camera_jitter for this frame's and the previous frame's camera,
+ * in RENDER pixels, finite, |j| < 0.5; max_history 1..1024; depth_tol finite and > 0, relative. The Python binding's
+ * defaults: zero jitter, 16, 0.02. */
+typedef struct { float jitter_cur[2]; float jitter_prev[2]; uint32_t max_history; float depth_tol; } rt_upscale_params;
+
+/* Sizes: w <= W <= 4 w, h <= H <= 4 h. color_cur, motion_cur, motion_prev: w*h x 4 floats (of motion_prev, the
+ * previous frame's motion plane, only .w is read: that frame's view depth); color_prev: W*H x 4 floats and hist_prev:
+ * W*H floats, the previous call's color_out and hist_out; the three prev planes are all given or all NULL (the first
+ * frame: no history is sought). hist_prev's entries must be >= 1, as a hist_out's are: 1 / n below is not guarded.
+ * color_out: W*H x 4 floats; hist_out: W*H floats; rgba8_out: NULL, or W*H x 4 bytes, unorm8 (rt_dispatch_rays'
+ * quantiser) of color_out's four channels, r in the lowest byte. 4-float planes are 16-byte aligned, the others
+ * 4-byte aligned.
+ * For output pixel (X, Y), with (jcx, jcy) = jitter_cur, (jpx, jpy) = jitter_prev:
+ *   sx = (float)w / (float)W;  ux = minf(maxf(((float)X + 0.5f) * sx - jcx, 0.5f), (float)w - 0.5f);  sy, uy likewise:
+ *   the pixel's centre on the jittered sample grid. ic = (int)floorf(ux) clamped to [0, w-1], jc likewise.
+ *   The taps (ic + di, jc + dj), dj outer, di inner, both -1 .. 1 ascending; a tap outside the render frame is skipped.
+ *   c = color_cur[tap], q = motion_cur[tap]:
+ *     dx = ((float)(ic+di) + 0.5f) - ux;  dy likewise;  k = maxf(0, 1 - (dx dx + dy dy));  kw = k k
+ *     sw += kw;  per channel sc += kw * c;  mn = minf(mn, c);  mx = maxf(mx, c)   (mn, mx start at +inf, -inf and take
+ *     every in-frame tap, whatever its kw)
+ *   Dilation: m = motion_cur[the in-frame tap with the smallest q.w among those whose q.w is finite and > 0, the first
+ *   in scan order on a tie; none: the centre tap].
+ *   cur = minf(maxf(sc / sw, mn), mx) per channel;  conf = the centre tap's kw. (The centre has |dx|, |dy| <= 0.5, so
+ *   conf >= 0.25 and sw > 0. The clamp closes a hole: the quotient of two rounded sums can leave the taps' range by a
+ *   rounding, and a constant plane would then not stay constant.)
+ *   History is sought when the prev planes are given, m.x and m.y are finite and m.z > 0:
+ *     tmx = m.x + (jpx - jcx);  fX = (float)X + tmx / sx;  tmy, fY likewise (both frames' projections sit at their
+ *     own -jitter);  required: -1 < fX < W and -1 < fY < H.
+ *     x0 = floorf(fX), tx = fX - x0, likewise y; the taps (x0 + dx, y0 + dy) in rt_ao_accumulate's order and weights.
+ *     A tap is skipped (not read) when its weight is 0, it lies outside the display frame, or the depth test fails:
+ *     pi = (int)floorf(((float)tapx + 0.5f) * sx - jpx) clamped to [0, w-1], pj likewise, z = motion_prev[pj w + pi].w,
+ *     accepted only if fabsf(z - m.z) <= depth_tol * m.z (a NaN or infinite z fails). An accepted tap adds
+ *     sw2 += wt;  per channel sa += wt * color_prev[tap];  sh += wt * hist_prev[tap].
+ *   sw2 >= 0.01f: n = minf(sh / sw2 + 1.0f, (float)max_history);  per channel a = sa / sw2,
+ *     ac = minf(maxf(a, lo), hi),  out = ac + (conf * (1.0f / n)) * (cur - ac);  n == 1: out = cur;  hist_out = n.
+ *     lo = mn, hi = mx, except at an edge pixel, one whose ux or uy the position clamp above changed (the unclamped
+ *     value != the clamped one): there e = mx - mn, lo = mn - e, hi = mx + e per channel. (A third hole closed. An edge
+ *     pixel's centre lies outside the hull of the sample centres, by less than one sample, so its value is an
+ *     extrapolation that [mn, mx] does not bound: on a gradient the clamp pulled the history to the nearest sample
+ *     in every frame, the accumulated value could never be kept, and the frame's outer ring followed the last jitter.
+ *     The widened range holds every linear extrapolation of the taps by less than one sample.)
+ *   Otherwise out = cur, hist_out = 1.
+ * At W = w, H = h and zero jitter only the centre tap has weight (the others' k is 0), so the first frame's color_out is
+ * color_cur bit for bit (for colours that are not -0, NaN or infinite) and rgba8_out the frame rt_dispatch_rays wrote.
+ * RT_E_INVALID, nothing written, rt_last_error naming the argument: a null or misaligned plane; only some of the prev
+ * planes; an output equal to any input or to another output (pointer EQUALITY, as for the AO filter); a size of 0 or
+ * outside the ratio limits; null or out-of-range params, a jitter that is not finite or has |j| >= 0.5.
+ * RT_E_UNSUPPORTED, nothing written: W x H >= 2^31, or W or H above 2^20 (a second hole closed: float32 resolves a
+ * sample position near 2^20 to 1/16 pixel, beyond which the kernel weights and the staged footprint's bound mean
+ * nothing). */
+rt_status rt_upscale(rt_ctx_t ctx, uint32_t w, uint32_t h, uint32_t W, uint32_t H, const rt_upscale_params* params,
+                     const float* color_cur, const float* motion_cur, const float* motion_prev,
+                     const float* color_prev, const float* hist_prev, float* color_out, float* hist_out,
+                     void* rgba8_out, void* hip_stream);
+
 /* Stream lifetime: the context notes (host-side, no event per launch) which streams launched with the current
  * TLAS version, and records one event on each of them when the next rt_tlas_build swaps that version out; the tile
  * balance likewise notes the streams that read a work list, and queries the stream of a shape's previous launch
@@ -805,6 +870,34 @@ rt_status rt_host_ao_accumulate(uint32_t W, uint32_t H, const rt_ao_temporal_par
                                 const float* hist_prev, const float* guide_prev, float* ao_out, float* hist_out);
 rt_status rt_host_ao_atrous(uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
                             const float* guide, float* ao_out, float* tmp);
+
+/* rt_upscale on host arrays, likewise: the same arguments less the context and the stream, the same checks less the
+ * 16-byte alignment (4 bytes will do, rgba8_out included), the same per-pixel function, so the same bits. */
+rt_status rt_host_upscale(uint32_t w, uint32_t h, uint32_t W, uint32_t H, const rt_upscale_params* params,
+                          const float* color_cur, const float* motion_cur, const float* motion_prev,
+                          const float* color_prev, const float* hist_prev, float* color_out, float* hist_out,
+                          void* rgba8_out);
+
+/* Sub-pixel jitter through the camera buffer alone (no kernel knows about it). out = cb (rt_set_camera's layout) with
+ * the projection and its inverse replaced so that, for a W x H frame and (jx, jy) in pixels, finite, |j| < 0.5:
+ *   the ray every frame and G-buffer kernel (and the oracle) sends through pixel offset (px + 0.5, py + 0.5) is the
+ *   ray cb sends through (px + 0.5 + jx, py + 0.5 + jy), and
+ *   rt_gbuffer_motion's forward projection places every point at (x - jx, y - jy).
+ * With ax = (2 jx) / W, ay = (2 jy) / H, T the matrix that adds (ax, -ay) clip.w to (clip.x, clip.y):
+ *   proj' = T^-1 proj:   element (row 0, column j) -= ax * element (3, j);  (1, j) += ay * (3, j)
+ *   projInv' = projInv T: element (i, column 3) = (element (i, 3) + ax * (i, 0)) - ay * (i, 1)
+ * where element (row i, column j) of either matrix is float 4 j + i of its 16 (the order hlsl_mul4 reads XMMATRIX
+ * memory in). View and viewInv are copied. float32, in the order written; jx = jy = 0 returns cb itself, bit for bit
+ * (the formulas would turn a -0 entry into +0). out may be cb. The two properties hold up
+ * to float32 rounding (measured: DESIGN §3.11). Null arguments, W or H of 0, a bad jitter: RT_E_INVALID, out untouched. */
+rt_status rt_camera_jitter(const float cb[64], uint32_t W, uint32_t H, float jx, float jy, float out[64]);
+
+/* A jitter sequence: out = (h2(i) - 0.5f, h3(i) - 0.5f) with i = index % 14348906 + 1 and h_b the radical inverse in
+ * base b: num = 0, den = 1; while (i != 0) { num = num * b + i % b; den = den * b; i = i / b; }  h = (float)num /
+ * (float)den, ONE float32 quotient of integers that float32 holds exactly (i < 3^15 < 2^24). The Halton sequence's
+ * element 0 is (0, 0), whose -0.5 rt_upscale refuses, so the sequence starts at element 1 and repeats after 3^15 - 1
+ * indices; every value lies in [-0.5 + 2^-24, 0.5). out NULL: RT_E_INVALID. */
+rt_status rt_jitter_halton(uint32_t index, float out[2]);
 
 /* ---- Camera manipulator ------------------------------------------------------------------------
  * nv_helpers_dx12::Manipulator (include/manipulator.h:33-148, src/manipulator.cpp) as plain data the

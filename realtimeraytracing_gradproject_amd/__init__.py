@@ -101,6 +101,12 @@ class rt_ao_atrous_params(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
 
 
+class rt_upscale_params(ctypes.Structure):
+    """include/rt_api.h rt_upscale_params: the two frames' jitters (render pixels), max_history (1..1024), depth_tol."""
+    _fields_ = [("jitter_cur", ctypes.c_float * 2), ("jitter_prev", ctypes.c_float * 2),
+                ("max_history", ctypes.c_uint32), ("depth_tol", ctypes.c_float)]
+
+
 class rt_tile_plan_args(ctypes.Structure):
     """include/rt_api.h rt_tile_plan_args: the plan kernel's knobs for rt_tile_plan_probe."""
     _fields_ = [(k, ctypes.c_uint32) for k in ("ntiles", "extra_cap", "slots", "kmax_code", "force", "split", "front",
@@ -160,6 +166,8 @@ SIGNATURES = [
     ("rt_ao_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P,
                               _P]),
     ("rt_ao_atrous", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P, _P]),
+    ("rt_upscale", _I, [_P, _U32, _U32, _U32, _U32, ctypes.POINTER(rt_upscale_params), _P, _P, _P, _P, _P, _P, _P, _P,
+                        _P]),
     ("rt_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _P]),
     ("rt_raster_draw", _I, [_P, _UP, _U32, _FP, _U32, _U32, _P, _P, _P]),
     ("rt_assemble_strips", _I, [_P, _U32, _U32, _U32, _U32, _P, _P, _P]),
@@ -207,6 +215,10 @@ SIGNATURES = [
     ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
     ("rt_host_ao_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rt_host_ao_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P]),
+    ("rt_host_upscale", _I, [_U32, _U32, _U32, _U32, ctypes.POINTER(rt_upscale_params), _P, _P, _P, _P, _P, _P, _P,
+                             _P]),
+    ("rt_camera_jitter", _I, [_FP, _U32, _U32, ctypes.c_float, ctypes.c_float, _FP]),
+    ("rt_jitter_halton", _I, [_U32, _FP]),
     ("rt_manip_init", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_update", None, [ctypes.POINTER(rt_manipulator)]),
     ("rt_manip_set_lookat", None, [ctypes.POINTER(rt_manipulator), _FP, _FP, _FP]),
@@ -517,6 +529,55 @@ def host_ao_atrous(width: int, height: int, ao_in, guide, iterations: int = 3, d
     if st != RT_OK:
         raise RtError(st, "rt_host_ao_atrous")
     return out
+
+
+def _upscale_params(jitter_cur, jitter_prev, max_history, depth_tol) -> rt_upscale_params:
+    jc, jp = _f32(jitter_cur, 2), _f32(jitter_prev, 2)
+    return rt_upscale_params((ctypes.c_float * 2)(*jc.tolist()), (ctypes.c_float * 2)(*jp.tolist()), max_history,
+                             depth_tol)
+
+
+def host_upscale(render_width: int, render_height: int, width: int, height: int, color_cur, motion_cur,
+                 motion_prev=None, color_prev=None, hist_prev=None, jitter_cur=(0.0, 0.0), jitter_prev=(0.0, 0.0),
+                 max_history: int = 16, depth_tol: float = 0.02, want_rgba8: bool = False):
+    """rt_host_upscale: the temporal upscaler on the host (no GPU). color_cur, motion_cur: (render_width *
+    render_height, 4); motion_prev likewise, color_prev (width * height, 4) and hist_prev (width * height): the previous
+    frame's motion plane and outputs, or all None (the first frame). Returns (color_out (width * height, 4), hist_out
+    (width * height)) and, with want_rgba8, the (width * height, 4) uint8 frame as a third."""
+    n, N = render_width * render_height, width * height
+    cc, mc = _f32(color_cur, 4 * n), _f32(motion_cur, 4 * n)
+    mp = None if motion_prev is None else _f32(motion_prev, 4 * n)
+    cp = None if color_prev is None else _f32(color_prev, 4 * N)
+    hp = None if hist_prev is None else _f32(hist_prev, N)
+    p = _upscale_params(jitter_cur, jitter_prev, max_history, depth_tol)
+    out, hist = np.zeros((N, 4), np.float32), np.zeros(N, np.float32)
+    out8 = np.zeros((N, 4), np.uint8) if want_rgba8 else None
+    st = lib.rt_host_upscale(render_width, render_height, width, height, ctypes.byref(p), _vp(cc), _vp(mc), _vp(mp),
+                             _vp(cp), _vp(hp), _vp(out), _vp(hist), _vp(out8))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_upscale")
+    return (out, hist, out8) if want_rgba8 else (out, hist)
+
+
+def camera_jitter(camera, width: int, height: int, jx: float, jy: float) -> np.ndarray:
+    """rt_camera_jitter: the 64-float camera buffer whose pixel-centre rays are `camera`'s rays through (px + 0.5 + jx,
+    py + 0.5 + jy) of a width x height frame, and whose forward projection lands at (x - jx, y - jy). |j| < 0.5."""
+    cb = _f32(camera, 64)
+    out = np.zeros(64, np.float32)
+    st = lib.rt_camera_jitter(_fptr(cb), width, height, jx, jy, _fptr(out))
+    if st != RT_OK:
+        raise RtError(st, "rt_camera_jitter")
+    return out
+
+
+def jitter_halton(index: int):
+    """rt_jitter_halton: element 1 + index % (3^15 - 1) of the Halton sequence in bases (2, 3), minus 0.5: a jitter
+    (jx, jy) for camera_jitter, as two Python floats holding float32 values."""
+    out = np.zeros(2, np.float32)
+    st = lib.rt_jitter_halton(index, _fptr(out))
+    if st != RT_OK:
+        raise RtError(st, "rt_jitter_halton")
+    return float(out[0]), float(out[1])
 
 
 class Manipulator:
@@ -1136,6 +1197,25 @@ class Context:
         self._check(self._lib.rt_ao_atrous(self._h, width, height, ctypes.byref(p), self._plane(m, "ao_in", ao_in, n),
                                            self._plane(m, "guide", guide, 4 * n), self._plane(m, "ao_out", ao_out, n),
                                            self._plane(m, "tmp", tmp, n), stream), "rt_ao_atrous")
+
+    def upscale(self, render_width: int, render_height: int, width: int, height: int, color_cur, motion_cur, color_out,
+                hist_out, motion_prev=None, color_prev=None, hist_prev=None, rgba8_out=None, jitter_cur=(0.0, 0.0),
+                jitter_prev=(0.0, 0.0), max_history: int = 16, depth_tol: float = 0.02,
+                stream: Optional[int] = None):
+        """rt_upscale: a width x height frame reconstructed from the jittered render_width x render_height colour frame
+        (dispatch's rgba32f under camera_jitter's camera), its motion plane and the previous call's color_out /
+        hist_out, fetched through the motion. motion_prev, color_prev, hist_prev all None: the first frame. rgba8_out:
+        optional width * height x 4 bytes."""
+        n, N, m = render_width * render_height, width * height, "upscale"
+        p = _upscale_params(jitter_cur, jitter_prev, max_history, depth_tol)
+        self._check(self._lib.rt_upscale(
+            self._h, render_width, render_height, width, height, ctypes.byref(p),
+            self._plane(m, "color_cur", color_cur, 4 * n), self._plane(m, "motion_cur", motion_cur, 4 * n),
+            self._plane(m, "motion_prev", motion_prev, 4 * n), self._plane(m, "color_prev", color_prev, 4 * N),
+            self._plane(m, "hist_prev", hist_prev, N), self._plane(m, "color_out", color_out, 4 * N),
+            self._plane(m, "hist_out", hist_out, N),
+            self._plane(m, "rgba8_out", rgba8_out.view(torch.int32) if isinstance(rgba8_out, torch.Tensor)
+                        and rgba8_out.dtype == torch.uint8 else rgba8_out, N), stream), "rt_upscale")
 
     def pick(self, width: int, height: int, x: int, y: int) -> Optional[dict]:
         """What the camera ray through the centre of pixel (x, y) of a width x height frame hits: None on a miss, else

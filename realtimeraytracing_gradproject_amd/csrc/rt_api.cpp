@@ -341,6 +341,8 @@ struct rt_ctx {
   // rt_ao_atrous: which form of the iteration kernel runs (RT_ATROUS_FORM = direct | lds at context creation, for the
   // A/B of tools/denoise_study.py and the tests; unset: the per-step choice of launch_ao_atrous)
   int atrous_form = rt::kAtrousAuto;
+  // rt_upscale likewise (RT_UPSCALE_FORM = direct | lds, tools/upscale_study.py; unset: launch_upscale's choice)
+  int upscale_form = rt::kUpscaleAuto;
   // rt_blas_refit: staging of the host variant's vertices (pinned, then device; grown on demand), the pinned
   // readback of the root box, the timing events of the refit's kernels
   void* refit_stage_host = nullptr;
@@ -674,6 +676,10 @@ rt_status rt_create(int hip_device, rt_ctx_t* out) {
     c->atrous_form = std::strcmp(ev, "direct") == 0 ? rt::kAtrousDirect
                      : std::strcmp(ev, "lds") == 0  ? rt::kAtrousLds
                                                     : rt::kAtrousAuto;
+  if (const char* ev = std::getenv("RT_UPSCALE_FORM"))
+    c->upscale_form = std::strcmp(ev, "direct") == 0 ? rt::kUpscaleDirect
+                      : std::strcmp(ev, "lds") == 0  ? rt::kUpscaleLds
+                                                     : rt::kUpscaleAuto;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&c->d_stats, RT_STAT_COUNT * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(c->d_stats, 0, RT_STAT_COUNT * sizeof(unsigned long long)) != hipSuccess) {
@@ -2304,6 +2310,87 @@ rt_status rt_ao_atrous(rt_ctx_t c, uint32_t W, uint32_t H, const rt_ao_atrous_pa
   return RT_OK;
 }
 
+// ---- Temporal upscaler: the argument check shared by rt_upscale and rt_host_upscale (align as above) --
+namespace {
+
+bool bad_jitter(float j) { return !std::isfinite(j) || !(std::fabs(j) < 0.5f); }
+
+const char* upscale_args_error(uint32_t w, uint32_t h, uint32_t W, uint32_t H, const rt_upscale_params* p,
+                               const float* color_cur, const float* motion_cur, const float* motion_prev,
+                               const float* color_prev, const float* hist_prev, const float* color_out,
+                               const float* hist_out, const void* rgba8_out, bool align, rt_status* st) {
+  *st = RT_E_INVALID;
+  if (w == 0 || h == 0 || W == 0 || H == 0) return "a size is 0";
+  if (W < w || (uint64_t)W > 4ull * w) return "W outside w .. 4 w";
+  if (H < h || (uint64_t)H > 4ull * h) return "H outside h .. 4 h";
+  *st = RT_E_UNSUPPORTED;
+  if ((uint64_t)W * H >= (1ull << 31)) return "display frame of 2^31 pixels or more";
+  if (W > (1u << 20) || H > (1u << 20)) return "W or H above 2^20";
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (bad_jitter(p->jitter_cur[0]) || bad_jitter(p->jitter_cur[1])) return "jitter_cur not finite or |j| >= 0.5";
+  if (bad_jitter(p->jitter_prev[0]) || bad_jitter(p->jitter_prev[1])) return "jitter_prev not finite or |j| >= 0.5";
+  if (p->max_history < 1 || p->max_history > 1024) return "max_history outside 1..1024";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!color_cur) return "null color_cur";
+  if (!motion_cur) return "null motion_cur";
+  if (!color_out) return "null color_out";
+  if (!hist_out) return "null hist_out";
+  const int nprev = (motion_prev != nullptr) + (color_prev != nullptr) + (hist_prev != nullptr);
+  if (nprev != 0 && nprev != 3) return "motion_prev, color_prev and hist_prev must be all given or all NULL";
+  const size_t a4 = align ? 16 : 4;
+  if (misaligned(color_cur, a4)) return "color_cur misaligned";
+  if (misaligned(motion_cur, a4)) return "motion_cur misaligned";
+  if (misaligned(motion_prev, a4)) return "motion_prev misaligned";
+  if (misaligned(color_prev, a4)) return "color_prev misaligned";
+  if (misaligned(color_out, a4)) return "color_out misaligned";
+  if (misaligned(hist_prev, 4) || misaligned(hist_out, 4)) return "a history plane is not aligned to 4 bytes";
+  if (misaligned(rgba8_out, 4)) return "rgba8_out not aligned to 4 bytes";
+  if ((const void*)color_out == (const void*)hist_out) return "color_out is hist_out";
+  if (rgba8_out && (rgba8_out == (const void*)color_out || rgba8_out == (const void*)hist_out))
+    return "rgba8_out is another output";
+  for (const void* o : {(const void*)color_out, (const void*)hist_out, rgba8_out}) {
+    if (!o) continue;
+    if (o == color_cur || o == motion_cur) return "an output is color_cur or motion_cur";
+    if (nprev && (o == motion_prev || o == color_prev || o == hist_prev)) return "an output is a previous-frame plane";
+  }
+  return nullptr;
+}
+
+rt::Upscale upscale_of(uint32_t w, uint32_t h, uint32_t W, uint32_t H, const rt_upscale_params* p,
+                       const float* color_cur, const float* motion_cur, const float* motion_prev,
+                       const float* color_prev, const float* hist_prev, float* color_out, float* hist_out,
+                       void* rgba8_out) {
+  rt::Upscale u = {};
+  u.w = w, u.h = h, u.W = W, u.H = H;
+  u.jcx = p->jitter_cur[0], u.jcy = p->jitter_cur[1], u.jpx = p->jitter_prev[0], u.jpy = p->jitter_prev[1];
+  u.max_history = (float)p->max_history;
+  u.depth_tol = p->depth_tol;
+  u.color_cur = color_cur, u.motion_cur = motion_cur;
+  u.motion_prev = motion_prev, u.color_prev = color_prev, u.hist_prev = hist_prev;
+  u.color_out = color_out, u.hist_out = hist_out, u.rgba8_out = (uint32_t*)rgba8_out;
+  return u;
+}
+
+}  // namespace
+
+rt_status rt_upscale(rt_ctx_t c, uint32_t w, uint32_t h, uint32_t W, uint32_t H, const rt_upscale_params* params,
+                     const float* color_cur, const float* motion_cur, const float* motion_prev,
+                     const float* color_prev, const float* hist_prev, float* color_out, float* hist_out,
+                     void* rgba8_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = upscale_args_error(w, h, W, H, params, color_cur, motion_cur, motion_prev, color_prev,
+                                           hist_prev, color_out, hist_out, rgba8_out, true, &st))
+    return fail(c, st, std::string("rt_upscale: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_upscale(upscale_of(w, h, W, H, params, color_cur, motion_cur, motion_prev,
+                                                     color_prev, hist_prev, color_out, hist_out, rgba8_out),
+                                          c->upscale_form, pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "upscale launch");
+  return RT_OK;
+}
+
 rt_status rt_set_motion_history(rt_ctx_t c, int enable) {
   if (!c) return RT_E_INVALID;
   const bool on = enable != 0;
@@ -2630,6 +2717,66 @@ rt_status rt_host_ao_atrous(uint32_t W, uint32_t H, const rt_ao_atrous_params* p
                                                  HostTap{guide, src, (int)x, (int)y, (int)s, (int)W, (int)H});
       }
   }
+  return RT_OK;
+}
+
+// Host services: rt_upscale on host arrays through upscale_pixel, the function the kernels of rt_upscale.hip call,
+// after the device entry point's argument checks (less the 16-byte alignment); and the jitter helpers. Here for
+// rt_host_shading_normals' reason. No context, no GPU call.
+namespace {
+struct HostColorTap {  // rt_upscale.hip's GlobalTap on host arrays
+  const float* color;
+  const float* motion;
+  uint32_t w;
+  void operator()(int i, int j, float c[4], float m[4]) const {
+    const size_t t = (size_t)j * w + (size_t)i;
+    rt::ld4(color + 4 * t, c);
+    rt::ld4(motion + 4 * t, m);
+  }
+};
+}  // namespace
+
+rt_status rt_host_upscale(uint32_t w, uint32_t h, uint32_t W, uint32_t H, const rt_upscale_params* params,
+                          const float* color_cur, const float* motion_cur, const float* motion_prev,
+                          const float* color_prev, const float* hist_prev, float* color_out, float* hist_out,
+                          void* rgba8_out) {
+  rt_status st = RT_OK;
+  if (upscale_args_error(w, h, W, H, params, color_cur, motion_cur, motion_prev, color_prev, hist_prev, color_out,
+                         hist_out, rgba8_out, false, &st))
+    return st;
+  const rt::Upscale u = upscale_of(w, h, W, H, params, color_cur, motion_cur, motion_prev, color_prev, hist_prev,
+                                   color_out, hist_out, rgba8_out);
+  for (uint32_t Y = 0; Y < H; ++Y)
+    for (uint32_t X = 0; X < W; ++X) rt::upscale_pixel(u, X, Y, HostColorTap{color_cur, motion_cur, w});
+  return RT_OK;
+}
+
+rt_status rt_camera_jitter(const float cb[64], uint32_t W, uint32_t H, float jx, float jy, float out[64]) {
+  if (!cb || !out || W == 0 || H == 0 || bad_jitter(jx) || bad_jitter(jy)) return RT_E_INVALID;
+  const float ax = (2.0f * jx) / (float)W, ay = (2.0f * jy) / (float)H;
+  float r[64];
+  std::memcpy(r, cb, sizeof(r));
+  const float* p = cb + 16;   // projection: element (row i, column j) at p[4 j + i] (hlsl_mul4)
+  const float* q = cb + 48;   // its inverse likewise
+  if (jx == 0.0f && jy == 0.0f) {  // cb itself, bit for bit (x + 0 * y would turn a -0 entry into +0)
+    std::memcpy(out, r, sizeof(r));
+    return RT_OK;
+  }
+  for (int j = 0; j < 4; ++j) {  // T^-1 . proj: row 0 -= ax row 3, row 1 += ay row 3
+    r[16 + 4 * j + 0] = p[4 * j + 0] - ax * p[4 * j + 3];
+    r[16 + 4 * j + 1] = p[4 * j + 1] + ay * p[4 * j + 3];
+  }
+  for (int i = 0; i < 4; ++i)  // projInv . T: column 3 += ax column 0 - ay column 1
+    r[48 + 12 + i] = (q[12 + i] + ax * q[i]) - ay * q[4 + i];
+  std::memcpy(out, r, sizeof(r));
+  return RT_OK;
+}
+
+rt_status rt_jitter_halton(uint32_t index, float out[2]) {
+  if (!out) return RT_E_INVALID;
+  const uint32_t i = index % 14348906u + 1u;  // 1 .. 3^15 - 1: never element 0, whose -0.5 rt_upscale refuses
+  out[0] = rt::halton_radical(i, 2u) - 0.5f;
+  out[1] = rt::halton_radical(i, 3u) - 0.5f;
   return RT_OK;
 }
 

@@ -1027,4 +1027,140 @@ RT_HD float atrous_pixel(const float g[4], uint32_t s, float depth_tol, float no
   return sa / sw;
 }
 
+// ------------------------------------------------------------------------------------------
+// Temporal upscaler (rt_upscale): the per-pixel arithmetic, called by the kernels of rt_upscale.hip per
+// lane and by rt_host_upscale per pixel. The AO filter's rule (above), less sqrtf; tests/upscale_reference.py restates
+// it in numpy.
+// ------------------------------------------------------------------------------------------
+
+struct Upscale {  // rt_upscale's launch: rt_upscale_params and the planes (prev planes all null or none)
+  uint32_t w, h, W, H;  // render size, display size
+  float jcx, jcy, jpx, jpy, max_history, depth_tol;
+  const float *color_cur, *motion_cur, *motion_prev, *color_prev, *hist_prev;
+  float *color_out, *hist_out;
+  uint32_t* rgba8_out;  // or null
+};
+
+// A position on the display grid -> the clamped position on the jittered sample grid of n samples, and its sample.
+RT_HD float upscale_raw(uint32_t X, float s, float j) { return ((float)X + 0.5f) * s - j; }
+RT_HD float upscale_pos(uint32_t X, float s, float j, uint32_t n) {
+  return minf(maxf(upscale_raw(X, s, j), 0.5f), (float)n - 0.5f);
+}
+RT_HD int upscale_cell(float u, uint32_t n) {
+  const int i = (int)floorf(u);
+  return i < 0 ? 0 : i > (int)n - 1 ? (int)n - 1 : i;
+}
+
+// Output pixel (X, Y) of rt_upscale. tap(i, j, c, m) gives the colour and the motion entry of the render-resolution
+// sample (i, j), which lies inside the frame (the kernel's two forms and the host twin differ in nothing but where it
+// reads). The previous planes are read from memory in every form.
+template <typename Tap>
+RT_HD void upscale_pixel(const Upscale& u, uint32_t X, uint32_t Y, Tap tap) {
+  const float big = 3.402823466e+38f;
+  const float sx = (float)u.w / (float)u.W, sy = (float)u.h / (float)u.H;
+  const float ux = upscale_pos(X, sx, u.jcx, u.w), uy = upscale_pos(Y, sy, u.jcy, u.h);
+  const int ic = upscale_cell(ux, u.w), jc = upscale_cell(uy, u.h);
+  // the pixel's centre lies outside the hull of the sample centres: its value is extrapolated, by less than one sample
+  const bool edge = upscale_raw(X, sx, u.jcx) != ux || upscale_raw(Y, sy, u.jcy) != uy;
+  float sw = 0.0f, conf = 0.0f, zbest = 0.0f;
+  float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  float mn[4] = {__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
+  float mx[4] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+  bool dilated = false;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int dj = -1; dj <= 1; ++dj) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int di = -1; di <= 1; ++di) {
+      const int i = ic + di, j = jc + dj;
+      if (i < 0 || j < 0 || i >= (int)u.w || j >= (int)u.h) continue;
+      float c[4], q[4];
+      tap(i, j, c, q);
+      const float dx = ((float)i + 0.5f) - ux, dy = ((float)j + 0.5f) - uy;
+      const float k = maxf(0.0f, 1.0f - (dx * dx + dy * dy));
+      const float kw = k * k;
+      sw += kw;
+      for (int ch = 0; ch < 4; ++ch) {
+        sc[ch] += kw * c[ch];
+        mn[ch] = minf(mn[ch], c[ch]);
+        mx[ch] = maxf(mx[ch], c[ch]);
+      }
+      const bool centre = di == 0 && dj == 0;
+      if (centre) conf = kw;
+      // the nearest surface's motion: the smallest finite positive w_cur (the first on a tie), else the centre's
+      const bool surf = q[3] <= big && q[3] > 0.0f;
+      if (surf ? (!dilated || q[3] < zbest) : (centre && !dilated)) {
+        m[0] = q[0], m[1] = q[1], m[2] = q[2], m[3] = q[3];
+        if (surf) dilated = true, zbest = q[3];
+      }
+    }
+  }
+  float cur[4];
+  for (int ch = 0; ch < 4; ++ch) cur[ch] = minf(maxf(sc[ch] / sw, mn[ch]), mx[ch]);  // a rounded quotient may leave the range
+  float sw2 = 0.0f, sh = 0.0f, sa[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (u.color_prev && fabsf(m[0]) <= big && fabsf(m[1]) <= big && m[2] > 0.0f) {
+    const float tmx = m[0] + (u.jpx - u.jcx), tmy = m[1] + (u.jpy - u.jcy);
+    const float fx = (float)X + tmx / sx, fy = (float)Y + tmy / sy;
+    if (fx > -1.0f && fx < (float)u.W && fy > -1.0f && fy < (float)u.H) {  // before any conversion to integer
+      const float xf = floorf(fx), yf = floorf(fy);
+      const float tx = fx - xf, ty = fy - yf;
+      const int x0 = (int)xf, y0 = (int)yf;
+      const float lim = u.depth_tol * m[2];
+      for (int t = 0; t < 4; ++t) {
+        const int ddx = t & 1, ddy = t >> 1;
+        const float wt = (ddx ? tx : 1.0f - tx) * (ddy ? ty : 1.0f - ty);
+        const int xx = x0 + ddx, yy = y0 + ddy;
+        if (wt == 0.0f || xx < 0 || yy < 0 || xx >= (int)u.W || yy >= (int)u.H) continue;
+        // the previous frame's sample under the tap's centre, and its depth
+        const int pi = upscale_cell(((float)xx + 0.5f) * sx - u.jpx, u.w);
+        const int pj = upscale_cell(((float)yy + 0.5f) * sy - u.jpy, u.h);
+        const float q = u.motion_prev[4 * ((size_t)pj * u.w + (size_t)pi) + 3];
+        if (!(fabsf(q - m[2]) <= lim)) continue;
+        const size_t e = (size_t)yy * u.W + (size_t)xx;
+        float pc[4];
+        ld4(u.color_prev + 4 * e, pc);
+        sw2 += wt;
+        for (int ch = 0; ch < 4; ++ch) sa[ch] += wt * pc[ch];
+        sh += wt * u.hist_prev[e];
+      }
+    }
+  }
+  const size_t o = (size_t)Y * u.W + (size_t)X;
+  float out[4], n = 1.0f;
+  if (sw2 >= 0.01f) n = minf(sh / sw2 + 1.0f, u.max_history);
+  if (sw2 >= 0.01f && n != 1.0f) {
+    const float alpha = conf * (1.0f / n);
+    for (int ch = 0; ch < 4; ++ch) {
+      // at an edge pixel the taps' range is widened by its own extent on either side: what a linear extrapolation by
+      // less than one sample can reach (without it the clamp would pull the history to the nearest sample every frame)
+      const float ext = mx[ch] - mn[ch];
+      const float lo = edge ? mn[ch] - ext : mn[ch], hi = edge ? mx[ch] + ext : mx[ch];
+      const float ac = minf(maxf(sa[ch] / sw2, lo), hi);
+      out[ch] = ac + alpha * (cur[ch] - ac);
+    }
+  } else {
+    // no history, or n == 1 (max_history 1): the current value itself, not ac + (cur - ac), which rounds
+    out[0] = cur[0], out[1] = cur[1], out[2] = cur[2], out[3] = cur[3];
+  }
+  st4(u.color_out + 4 * o, out);
+  u.hist_out[o] = n;
+  if (u.rgba8_out)
+    u.rgba8_out[o] = unorm8(out[0]) | (unorm8(out[1]) << 8) | (unorm8(out[2]) << 16) | (unorm8(out[3]) << 24);
+}
+
+// The radical inverse in integers: the digits of i in base b, reversed, over b^digits, as ONE float32 quotient of two
+// integers that float32 holds exactly (rt_jitter_halton keeps i below 3^15 < 2^24, so num < den <= 2^24).
+RT_HD float halton_radical(uint32_t i, uint32_t b) {
+  uint32_t num = 0, den = 1;
+  while (i != 0) {
+    num = num * b + i % b;
+    den = den * b;
+    i = i / b;
+  }
+  return (float)num / (float)den;
+}
+
 }  // namespace rt

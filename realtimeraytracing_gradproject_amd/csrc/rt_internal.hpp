@@ -210,6 +210,12 @@ enum { kAtrousAuto = 0, kAtrousDirect = 1, kAtrousLds = 2 };
 hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol, float normal_cos, const float* in,
                             const float* guide, float* out, int form, hipStream_t stream);
 
+// --- Temporal upscaler (rt_upscale.hip) ---------------------------------------
+// One launch; no scene, no scratch. form: kUpscaleDirect (each lane loads its 9 + 9 taps) or kUpscaleLds (a workgroup
+// stages its tile's render-resolution footprint in LDS); kUpscaleAuto picks.
+enum { kUpscaleAuto = 0, kUpscaleDirect = 1, kUpscaleLds = 2 };
+hipError_t launch_upscale(const Upscale& u, int form, hipStream_t stream);
+
 // rank_stride_rows: rows from one rank's block of `gathered` to the next (0: rows_per_rank, one frame per block;
 // a batched gather holds several frames per rank block and passes their total)
 // in_bpp: bytes per pixel of the gathered strips (4 RGBA8, 3 RGB8: the alpha byte restored as 255); out is RGBA8
