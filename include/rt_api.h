@@ -33,7 +33,7 @@ extern "C" {
  * rt_dispatch_ao, rt_host_ao_rays and rt_ao_params, and rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous, their host
  * twins rt_host_denoise_guide, rt_host_ao_accumulate, rt_host_ao_atrous, rt_ao_temporal_params and
  * rt_ao_atrous_params, and rt_tile_plan_probe with rt_tile_plan_args, and rt_upscale, rt_host_upscale,
- * rt_upscale_params, rt_camera_jitter and rt_jitter_halton. */
+ * rt_upscale_params, rt_camera_jitter and rt_jitter_halton, and rt_dispatch_rays_gbuffer. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -422,6 +422,39 @@ typedef struct {
  * aligned. Without a motion plane the call needs no history. */
 rt_status rt_dispatch_gbuffer_motion(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
                                      const rt_gbuffer_motion* out, const float prev_cb[64], void* hip_stream);
+
+/* The fused frame + G-buffer launch: rt_dispatch_rays and rt_dispatch_gbuffer_motion in ONE launch with one primary
+ * walk per pixel, for a frame loop whose later passes (rt_upscale, the AO filter, reprojection) read the planes of the
+ * frame it has just rendered. In DXR terms: the hit programs write their AOVs in the DispatchRays that shades.
+ * Frame outputs: rgba8_dev and rgba32f_dev (optional) come out byte for byte as rt_dispatch_rays(ctx, W, H, rows,
+ * nrows, rgba8_dev, rgba32f_dev, hip_stream) writes them for the same context state.
+ * Planes: out->hits, uv, normal, object and motion, each optional, at least one non-NULL, come out bit for bit as
+ * rt_dispatch_gbuffer_motion(ctx, W, H, rows, nrows, out, prev_cb, hip_stream) writes them; pixel order is the
+ * compact order both launches share. The planes are stored from the frame kernel's own primary hit, right after the
+ * primary walk (before any shadow or reflection ray): the kernel walks no second primary ray.
+ * spp: one sample per pixel only; after rt_set_shading(..., spp != 1) the call returns RT_E_INVALID (no offset of the
+ * 2 x 2, 3 x 3 or 4 x 4 stratified grids is the pixel centre the G-buffer's ray goes through, so there is nothing to
+ * fuse). The upscaler's jittered one-sample frame is the intended caller.
+ * Every shade mode, RT_SHADE_REF with reflectivity 0 and != 0. rt_set_schedule and rt_set_triangle_test are
+ * honoured, with the frame's fall-back to RT_SCHED_LANE when the scene's worst-case packet stack is 64 entries or
+ * more. The grid is always the plain grid of 8 x 8 pixel tiles: like a watertight frame the call ignores
+ * rt_set_tile_balance, and it ignores rt_set_tile_rows; it neither reads nor records a tile-balance cost map and runs
+ * no plan, so rt_dispatch_rays launches around it find the balance's state as they left it. The image never depends
+ * on either setting, so the equalities above hold whatever the context's settings are. One RGBA8 frame per launch (no
+ * counterpart of rt_dispatch_frames or of the RGB8 strips).
+ * rt_set_stats: every counter grows exactly as one rt_dispatch_rays with the same arguments makes it grow; the planes
+ * add nothing. Streams, the slot rings, the TLAS double buffer, rt_forget_stream and refit-before-rebuild: as
+ * rt_dispatch_rays; the launch is noted like a frame. Motion: rt_dispatch_gbuffer_motion's rules (a motion plane needs
+ * rt_set_motion_history(ctx, 1) and a TLAS built since; prev_cb NULL = the context's camera).
+ * Errors, with nothing written and rt_last_error naming the cause: every error of rt_dispatch_rays (RT_E_INVALID: no
+ * TLAS, a stale or refitted scene, no shading, no camera, W or H of 0, a NULL rgba8_dev, a bad row list;
+ * RT_E_UNSUPPORTED: a frame of 4 GB or more, trees deeper than the traversal stack), every error of
+ * rt_dispatch_gbuffer_motion (RT_E_INVALID: a NULL `out`, all five planes NULL, a misaligned plane, a motion plane
+ * without history), and the spp rule above.
+ * No reference counterpart beyond DispatchRays itself: the reference's hit programs write the colour only. */
+rt_status rt_dispatch_rays_gbuffer(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                   void* rgba8_dev, float* rgba32f_dev, const rt_gbuffer_motion* out,
+                                   const float prev_cb[64], void* hip_stream);
 
 /* Parameters of the ambient-occlusion pass. samples: rays per pixel, 1..64; seed: any value (the same seed gives the
  * same plane, bit for bit); radius: the rays' tmax, finite and > 0; tmin: their tmin, finite, >= 0 and < radius (the

@@ -161,6 +161,7 @@ SIGNATURES = [
     ("rt_dispatch_gbuffer", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer), _P]),
     ("rt_set_motion_history", _I, [_P, _I]),
     ("rt_dispatch_gbuffer_motion", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer_motion), _FP, _P]),
+    ("rt_dispatch_rays_gbuffer", _I, [_P, _U32, _U32, _P, _U32, _P, _P, ctypes.POINTER(rt_gbuffer_motion), _FP, _P]),
     ("rt_dispatch_ao", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
     ("rt_denoise_guide", _I, [_P, _U32, _P, _P, _U32, _P, _P]),
     ("rt_ao_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P,
@@ -1138,6 +1139,23 @@ class Context:
         self._check(self._lib.rt_dispatch_gbuffer_motion(self._h, width, height, rp, nr, ctypes.byref(g),
                                                          None if pcb is None else _fptr(pcb), stream),
                     "rt_dispatch_gbuffer_motion")
+
+    def dispatch_with_gbuffer(self, width: int, height: int, rgba8, rgba32f=None, hits=None, uv=None, normal=None,
+                              object=None, motion=None, prev_camera=None,  # noqa: A002
+                              rows: Optional[np.ndarray] = None, stream: Optional[int] = None):
+        """rt_dispatch_rays_gbuffer: dispatch() and dispatch_gbuffer_motion() in one launch with one primary walk per
+        pixel. rgba8 / rgba32f come out as dispatch() writes them, the planes as dispatch_gbuffer_motion() does, bit for
+        bit. One sample per pixel only (set_shading's spp must be 1); always the plain grid (set_tile_balance and
+        set_tile_rows do not apply); at least one plane must be given."""
+        rp, nr, _keep = self._rows_arg(rows, height)
+        g = rt_gbuffer_motion()
+        self._set_planes(g, "dispatch_with_gbuffer", nr * width,
+                         (("hits", hits, 4), ("uv", uv, 2), ("normal", normal, 4), ("object", object, 2),
+                          ("motion", motion, 4)))
+        pcb = None if prev_camera is None else _f32(prev_camera, 64)
+        self._check(self._lib.rt_dispatch_rays_gbuffer(self._h, width, height, rp, nr, _ptr(rgba8), _ptr(rgba32f),
+                                                       ctypes.byref(g), None if pcb is None else _fptr(pcb), stream),
+                    "rt_dispatch_rays_gbuffer")
 
     def dispatch_ao(self, width: int, height: int, ao, samples: int, radius: float, tmin: float = 0.01, seed: int = 0,
                     rows: Optional[np.ndarray] = None, stream: Optional[int] = None):

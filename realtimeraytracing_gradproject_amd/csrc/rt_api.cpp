@@ -1423,12 +1423,13 @@ hipError_t ctx_forget_stream(rt_ctx* c, hipStream_t s) {
 }
 void* ctx_stream(rt_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
-rt_status check_dispatch(rt_ctx* c, uint32_t W, uint32_t H, const void* rgba8, bool cameras_given) {
-  const rt_status st = check_scene_ready(c, "rt_dispatch_rays");
+rt_status check_dispatch(rt_ctx* c, uint32_t W, uint32_t H, const void* rgba8, bool cameras_given, const char* fn) {
+  const std::string f(fn);
+  const rt_status st = check_scene_ready(c, fn);
   if (st != RT_OK) return st;
-  if (!c->have_shading) return fail(c, RT_E_INVALID, "rt_dispatch_rays: shading not set");
-  if (!c->have_camera && !cameras_given) return fail(c, RT_E_INVALID, "rt_dispatch_rays: camera not set");
-  if (W == 0 || H == 0 || !rgba8) return fail(c, RT_E_INVALID, "rt_dispatch_rays: bad size or output");
+  if (!c->have_shading) return fail(c, RT_E_INVALID, f + ": shading not set");
+  if (!c->have_camera && !cameras_given) return fail(c, RT_E_INVALID, f + ": camera not set");
+  if (W == 0 || H == 0 || !rgba8) return fail(c, RT_E_INVALID, f + ": bad size or output");
   return RT_OK;
 }
 
@@ -1752,10 +1753,12 @@ static rt_status balance_frame(rt_ctx* c, const rt::SceneView& sv, const rt::Pac
 // null; the caller validated the arguments with check_dispatch and keeps d_rows alive until the launch completed).
 // nframes frames in one launch (the grid's z): frame z with camera buffer cams[64 z ..] (null: the context's
 // camera for every frame) into out + z * frame_stride bytes (0: nrows * W * out_bpp, compact); out_bpp 4 = RGBA8,
-// 3 = RGB8 (strips). Prologue, balance, launch, epilogue.
+// 3 = RGB8 (strips). Prologue, balance, launch, epilogue. gbuf (rt_dispatch_rays_gbuffer): the fused kernels, which also
+// store these planes; always the plain grid of 8 x 8 tiles, whatever rt_set_tile_balance and rt_set_tile_rows say (no
+// cost map is looked up, read or recorded and no plan runs: the balance's state is as the launch found it).
 static rt_status launch_frame(TraceLaunch& L, uint32_t W, uint32_t H, const uint32_t* d_rows, uint32_t nrows,
                               void* rgba8, float* rgba32f, uint32_t out_bpp, uint32_t nframes, const float* cams,
-                              uint64_t frame_stride, uint64_t rows_gen) {
+                              uint64_t frame_stride, uint64_t rows_gen, const rt::GbufMotionParams* gbuf = nullptr) {
   rt_ctx* c = L.c;
   if (nframes < 1 || nframes > (uint32_t)rt::kMaxLaunchFrames || (out_bpp != 3 && out_bpp != 4) ||
       (nframes > 1 && rgba32f))
@@ -1767,7 +1770,7 @@ static rt_status launch_frame(TraceLaunch& L, uint32_t W, uint32_t H, const uint
   c->fp.fwidth = (float)W;  // exact: W, H < 2^24
   c->fp.fheight = (float)H;
   c->fp.nrows = nrows;
-  c->fp.tile_rows = c->tile_rows;
+  c->fp.tile_rows = gbuf ? 8u : c->tile_rows;
   c->fp.out_bpp = out_bpp;
   c->fp.nframes = nframes;
   c->fp.frame_bytes = (uint32_t)frame_bytes;
@@ -1779,10 +1782,12 @@ static rt_status launch_frame(TraceLaunch& L, uint32_t W, uint32_t H, const uint
   c->fp.grid_x = g.grid_x;
   c->fp.waves_per_frame = g.waves_per_frame;
   uint32_t plan_items = 0;
-  if ((st = balance_frame(c, L.sv, g, W, nrows, d_rows, nframes, L.s, rows_gen, &plan_items, &L.plan)) != RT_OK)
+  if (gbuf)
+    c->fp.plan = c->fp.cost = nullptr;
+  else if ((st = balance_frame(c, L.sv, g, W, nrows, d_rows, nframes, L.s, rows_gen, &plan_items, &L.plan)) != RT_OK)
     return st;
   st = L.finish(rt::launch_trace_frame(L.sv, c->fp, d_rows, rgba8, rgba32f, c->d_stats, c->stats_on, c->schedule,
-                                       plan_items, L.s),
+                                       plan_items, L.s, gbuf),
                 "trace launch");
   if (st != RT_OK) return st;
   if (c->stats_on) {
@@ -2038,9 +2043,19 @@ static rt_status grid_pass_check(rt_ctx* c, const std::string& fn, uint32_t W, u
   return RT_OK;
 }
 
-// ... and what every such pass does once its checks are through: the pixel-count limit, the camera and the frame size
-// into gb (the launch's GbufParams: its planes are the caller's business), the row list's and the overflow stack's
-// slots, launch(scene view, device rows, stream) -> hipError_t, the launch record and the host-side counters.
+// The camera and the frame size of a launch on that grid into gb (the launch's GbufParams: its planes are the
+// caller's business).
+static void grid_pass_frame(rt_ctx* c, uint32_t W, uint32_t H, uint32_t nrows, rt::GbufParams& gb) {
+  rt::frame_cam(c->cam_cb, gb.cam);
+  gb.width = W;
+  gb.nrows = nrows;
+  gb.fwidth = (float)W;  // exact: W, H < 2^24
+  gb.fheight = (float)H;
+}
+
+// ... and what every such pass does once its checks are through: the pixel-count limit, grid_pass_frame, the row
+// list's and the overflow stack's slots, launch(scene view, device rows, stream) -> hipError_t, the launch record and
+// the host-side counters.
 using GridLaunch = std::function<hipError_t(const rt::SceneView&, const uint32_t*, hipStream_t)>;
 static rt_status grid_pass_launch(rt_ctx* c, const std::string& fn, uint32_t W, uint32_t H, const uint32_t* rows,
                                   uint32_t nrows, void* stream, rt::GbufParams& gb, const char* what,
@@ -2051,11 +2066,7 @@ static rt_status grid_pass_launch(rt_ctx* c, const std::string& fn, uint32_t W, 
   TraceLaunch L{c, fn.c_str(), pick_stream(c, stream)};
   rt_status st = L.open();
   if (st != RT_OK) return st;
-  rt::frame_cam(c->cam_cb, gb.cam);
-  gb.width = W;
-  gb.nrows = nrows;
-  gb.fwidth = (float)W;  // exact: W, H < 2^24
-  gb.fheight = (float)H;
+  grid_pass_frame(c, W, H, nrows, gb);
   const uint32_t* d_rows = nullptr;
   uint64_t rows_gen = 0;
   if ((st = L.take_rows(rows, nrows, &d_rows, &rows_gen)) != RT_OK) return st;
@@ -2070,23 +2081,22 @@ static rt_status grid_pass_launch(rt_ctx* c, const std::string& fn, uint32_t W, 
   return RT_OK;
 }
 
-// rt_dispatch_gbuffer (fn names it in the messages; out.motion null, the four-plane kernels) and
-// rt_dispatch_gbuffer_motion (the motion kernels: the same four planes and out.motion, which may be null too).
-static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion_kernels, uint32_t W, uint32_t H,
-                                  const uint32_t* rows, uint32_t nrows, const rt_gbuffer_motion& out,
-                                  const float* prev_cb, void* stream) {
+// The checks of a launch that writes G-buffer planes (fn names the entry point in the messages; *nrows becomes H
+// without a row list), and its planes, cameras and motion records into mp.
+static rt_status gbuffer_params(rt_ctx_t c, const std::string& fn, uint32_t W, uint32_t H, const uint32_t* rows,
+                                uint32_t* nrows, const rt_gbuffer_motion& out, const float* prev_cb,
+                                rt::GbufMotionParams& mp) {
   if (!out.hits && !out.uv && !out.normal && !out.object && !out.motion)
     return fail(c, RT_E_INVALID, fn + ": every output plane is null");
   if (((uintptr_t)out.hits | (uintptr_t)out.normal) % 16u || ((uintptr_t)out.uv | (uintptr_t)out.object) % 8u)
     return fail(c, RT_E_INVALID, fn + ": output plane not aligned (hits, normal: 16 bytes; uv, object: 8)");
   if ((uintptr_t)out.motion % 16u) return fail(c, RT_E_INVALID, fn + ": motion plane not aligned to 16 bytes");
-  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, nrows);
   if (st != RT_OK) return st;
   if (out.motion && !c->motion_on)
     return fail(c, RT_E_INVALID, fn + ": motion plane asked for, but motion history is off (rt_set_motion_history)");
   if (out.motion && !c->ver[c->cur].motion)
     return fail(c, RT_E_INVALID, fn + ": the current TLAS was built before motion history was switched on");
-  rt::GbufMotionParams mp;
   rt::GbufParams& gb = mp.gb;
   gb.hits = out.hits;
   gb.uv = out.uv;
@@ -2095,6 +2105,18 @@ static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion
   motion_cams(c->cam_cb, prev_cb, mp.cams);
   mp.motion = out.motion;
   mp.recs = c->ver[c->cur].motion;
+  return RT_OK;
+}
+
+// rt_dispatch_gbuffer (out.motion null, the four-plane kernels) and rt_dispatch_gbuffer_motion (the motion kernels: the
+// same four planes and out.motion, which may be null too).
+static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion_kernels, uint32_t W, uint32_t H,
+                                  const uint32_t* rows, uint32_t nrows, const rt_gbuffer_motion& out,
+                                  const float* prev_cb, void* stream) {
+  rt::GbufMotionParams mp;
+  rt::GbufParams& gb = mp.gb;
+  const rt_status st = gbuffer_params(c, fn, W, H, rows, &nrows, out, prev_cb, mp);
+  if (st != RT_OK) return st;
   return grid_pass_launch(c, fn, W, H, rows, nrows, stream, gb, "G-buffer launch",
                           [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
                             return motion_kernels
@@ -2116,6 +2138,30 @@ rt_status rt_dispatch_gbuffer_motion(rt_ctx_t c, uint32_t W, uint32_t H, const u
   if (!c) return RT_E_INVALID;
   if (!out) return fail(c, RT_E_INVALID, "rt_dispatch_gbuffer_motion: null output structure");
   return gbuffer_dispatch(c, "rt_dispatch_gbuffer_motion", true, W, H, rows, nrows, *out, prev_cb, stream);
+}
+
+// The fused frame + G-buffer launch: rt_dispatch_rays' checks and launch (check_dispatch, launch_frame) around
+// rt_dispatch_gbuffer_motion's (gbuffer_params), and the one rule of its own (one sample per pixel).
+rt_status rt_dispatch_rays_gbuffer(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                   void* rgba8, float* rgba32f, const rt_gbuffer_motion* out, const float prev_cb[64],
+                                   void* stream) {
+  static const char* fn = "rt_dispatch_rays_gbuffer";
+  if (!c) return RT_E_INVALID;
+  if (!out) return fail(c, RT_E_INVALID, std::string(fn) + ": null output structure");
+  rt_status st = check_rows(c, fn, H, rows, &nrows);
+  if (st != RT_OK || (st = rt::check_dispatch(c, W, H, rgba8, false, fn)) != RT_OK) return st;
+  if (c->fp.spp_side != 1)
+    return fail(c, RT_E_INVALID, std::string(fn) + ": one sample per pixel only (rt_set_shading's spp is not 1: no "
+                                                   "sample of a stratified grid is the G-buffer's pixel centre)");
+  rt::GbufMotionParams mp;
+  if ((st = gbuffer_params(c, fn, W, H, rows, &nrows, *out, prev_cb, mp)) != RT_OK) return st;
+  grid_pass_frame(c, W, H, nrows, mp.gb);
+  (void)hipSetDevice(c->device);
+  TraceLaunch L{c, fn, pick_stream(c, stream)};
+  const uint32_t* d_rows = nullptr;
+  uint64_t rows_gen = 0;
+  if ((st = L.take_rows(rows, nrows, &d_rows, &rows_gen)) != RT_OK) return st;
+  return rt::launch_frame(L, W, H, d_rows, nrows, rgba8, rgba32f, 4, 1, nullptr, 0, rows_gen, &mp);
 }
 
 // What is wrong with an rt_ao_params, or null (rt_dispatch_ao and rt_host_ao_rays check alike).

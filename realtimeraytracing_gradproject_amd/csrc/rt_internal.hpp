@@ -16,7 +16,9 @@ uint64_t ctx_next_rows_gen(rt_ctx* c);
 void* ctx_stream(rt_ctx* c);
 // rt_dispatch_rays' argument / scene checks and its launch with a device row list (rt_render_strips keeps its
 // rank's rows on the device and skips the host list's upload ring)
-rt_status check_dispatch(rt_ctx* c, uint32_t W, uint32_t H, const void* rgba8, bool cameras_given = false);
+// (fn: the entry point's name in the messages)
+rt_status check_dispatch(rt_ctx* c, uint32_t W, uint32_t H, const void* rgba8, bool cameras_given = false,
+                         const char* fn = "rt_dispatch_rays");
 // nframes (1 .. kMaxLaunchFrames) frames in one launch, frame z with camera buffer cams[64 z ..] (null: the
 // context's camera) into rgba8 + z * frame_stride bytes (0: nrows * W * out_bpp); out_bpp 4 = RGBA8, 3 = RGB8
 // (the strips of rt_comm)
@@ -108,9 +110,12 @@ hipError_t tlas_prepare(const InstanceRec* d_inst, const float* d_blas_bounds, u
 // --- Trace (rt_trace.hip) -------------------------------------------------------------------
 
 // plan_items: with fp.plan set, the waves of the launch's 1-D grid (the work list's budget: tiles + parts)
+// gbuf: the fused frame + G-buffer launch (rt_dispatch_rays_gbuffer): the fused kernels, which also store these
+// planes from the frame's primary hit; one frame of one sample per pixel, fp.plan and fp.cost null
 hipError_t launch_trace_frame(const SceneView& scene, const FrameParams& fp, const uint32_t* d_rows,
                               void* rgba8, float* rgba32f, unsigned long long* d_stats, bool stats,
-                              int schedule, uint32_t plan_items, hipStream_t stream);
+                              int schedule, uint32_t plan_items, hipStream_t stream,
+                              const GbufMotionParams* gbuf = nullptr);
 
 // The packet kernel's plain grid for a launch (schedule, tile layout), or packet = false (the per-lane kernel).
 struct PacketGeometry {
@@ -134,9 +139,10 @@ struct FrameKernel {
   bool bal = false;     // the tile balance's kernel (work list, wave times); never under the watertight test
   bool mf = true;       // the general kernel: several frames per launch or RGB8 strips; false: one RGBA8 frame
   int tt = 0;           // triangle test (1: watertight)
+  bool gb = false;      // the fused frame + G-buffer kernel (rt_dispatch_rays_gbuffer): never with the tile balance
 };
 FrameKernel select_frame_kernel(const SceneView& sc, const FrameParams& fp, const PacketGeometry& g, bool stats,
-                                bool balance);
+                                bool balance, bool fused = false);
 // The GPU's wave slots for the packet kernel a tile-balance launch of this shape runs (select_frame_kernel with the
 // balance on and the counters off: what launch_trace_frame launches): hipOccupancyMaxActiveBlocksPerMultiprocessor of
 // that kernel x waves per workgroup x the device's CUs, cached per (kernel, device); 0 if the runtime cannot tell.

@@ -1261,10 +1261,27 @@ __device__ V3 shade_ref(const SceneView& sc, const FrameParams& fp, uint32_t py,
   }
 }
 
+// The fused frame + G-buffer launch (rt_dispatch_rays_gbuffer). The frame kernels' fused variants store
+// the G-buffer pass's planes from their own primary hit, through that pass's two store functions (defined with it,
+// below: the same calls on the same hit record, so the same bits), right after the primary walk: no plane input is
+// live across the shadow and reflection walks, and the reflection walks may overwrite the hit record. G is what the
+// sample stores besides its colour: FusedPlanes in a fused kernel (the launch's plane parameters, an extra kernel
+// argument of those kernels only, and the rays' plane entries: o[r] for ray r, ~0 where the lane stores nothing),
+// NoGbuf (the default, an empty structure: no argument at all) in every other one, which compiles the stores out.
+struct NoGbuf {};
+struct FusedPlanes {
+  const GbufMotionParams& p;
+  const uint32_t* o;
+};
+__device__ __forceinline__ void gbuffer_store(const SceneView& sc, const GbufParams& gb, uint32_t o, bool f,
+                                              const HitRec& hit);
+__device__ __forceinline__ void gbuffer_motion_store(const SceneView& sc, const GbufMotionParams& mp, uint32_t o, bool f,
+                                                     const HitRec& hit, V3 O, V3 D);
+
 // One camera sample -> color (RayGen.hlsl:28-43 and the hit/miss programs).
-template <int MODE, bool STATS, int TT = 0>
+template <int MODE, bool STATS, int TT = 0, typename G = NoGbuf>
 __device__ V3 shade_sample(const SceneView& sc, const FrameParams& fp, const FrameCam& cam, uint32_t px, uint32_t py,
-                           float ox, float oy, const LaneStack& stk, Counters& cnt) {
+                           float ox, float oy, const LaneStack& stk, Counters& cnt, G fused = G{}) {
   const float dx = (((float)px + ox) / fp.fwidth) * 2.0f - 1.0f;
   const float dy = (((float)py + oy) / fp.fheight) * 2.0f - 1.0f;
   float dc[4], dw[4];
@@ -1277,6 +1294,10 @@ __device__ V3 shade_sample(const SceneView& sc, const FrameParams& fp, const Fra
   HitRec hit;
   if (STATS) ++cnt.primary;
   const bool f = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
+  if constexpr (!std::is_same_v<G, NoGbuf>) {
+    gbuffer_store(sc, fused.p.gb, fused.o[0], f, hit);
+    gbuffer_motion_store(sc, fused.p, fused.o[0], f, hit, O, D);
+  }
   if (MODE == 0 || MODE == 3) return shade_ref<STATS, TT>(sc, fp, py, O, D, f, hit, stk, cnt);
   if (!f) return miss_color(fp, py);
   const HitInstance ir = load_hit_instance(sc, hit.inst);
@@ -1368,10 +1389,11 @@ __device__ bool shadow_compact(const SceneView& sc, V3 P, V3 d, bool need, uint3
 #ifndef RT_WAVE_TIMES
 #define RT_WAVE_TIMES 0  // 1: every wave stores its start / end clock (diagnostics; tools/wave_times.py)
 #endif
-template <int MODE, bool STATS, int R, int TT = 0>
+// fused: the fused launch's planes and the rays' plane entries (see NoGbuf above).
+template <int MODE, bool STATS, int R, int TT = 0, typename G = NoGbuf>
 __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, const FrameCam& cam, const uint32_t* px,
                                     const uint32_t* py, float ox, float oy, const bool* inimg, V3* color,
-                                    Counters& cnt) {
+                                    Counters& cnt, G fused = G{}) {
   V3 O[R], D[R], P[R], sd[R];
   HitRec hit[R], sh[R];
   bool found[R], occl[R], need[R];
@@ -1389,6 +1411,14 @@ __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, 
     if (STATS && inimg[r]) ++cnt.primary;
   }
   trace_packet<false, STATS, R, false, TT>(sc, O, D, 0.0f, 100000.0f, inimg, found, hit, cnt);
+  if constexpr (!std::is_same_v<G, NoGbuf>) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (fused.o[r] != 0xffffffffu) {
+        gbuffer_store(sc, fused.p.gb, fused.o[r], found[r], hit[r]);
+        gbuffer_motion_store(sc, fused.p, fused.o[r], found[r], hit[r], O[r], D[r]);
+      }
+  }
 #pragma unroll
   for (int r = 0; r < R; ++r) P[r] = add(O[r], muls(D[r], hit[r].t));  // GetWorldHitPoint, Common.hlsl:24-27
   if (MODE == 0 || MODE == 3) {  // MODE 3: RT_SHADE_REF with reflectivity 0 (no reflection rays)
@@ -1585,6 +1615,33 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void k_trace_frame(SceneView 
   if (STATS) flush_stats<false>(cnt, stats);
 }
 
+// k_trace_frame for the fused frame + G-buffer launch (one frame, one sample per pixel: the sample loop's single
+// pass at offsets (0 + 0.5) / 1, its sum 0 + colour kept): shade_sample stores the planes from its primary hit.
+template <int MODE, bool STATS, int TT = 0>
+__global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void k_trace_frame_gbuffer(SceneView sc, FrameParams fp,
+                                                                const uint32_t* __restrict__ rows,
+                                                                uint32_t* __restrict__ rgba8,
+                                                                float4* __restrict__ rgba32f,
+                                                                unsigned long long* __restrict__ stats,
+                                                                GbufMotionParams gbuf) {
+  extern __shared__ int s_stack[];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  Counters cnt;
+  if (px < fp.width && orow < fp.nrows) {
+    const uint32_t py = rows ? rows[orow] : orow;
+    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+    const uint32_t o = orow * fp.width + px;  // < 2^32 pixels (rt_api.cpp)
+    const V3 acc = add(v3(0.0f, 0.0f, 0.0f),
+                       shade_sample<MODE, STATS, TT>(sc, fp, fp.cam[0], px, py, 0.5f, 0.5f, stk, cnt,
+                                                     FusedPlanes{gbuf, &o}));
+    store_pixel(fp, rgba8, o, acc, 0u);
+    if (rgba32f) rgba32f[o] = make_float4(acc.x, acc.y, acc.z, 1.0f);
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
 // Wave-packet frame kernel. KS = 1: a wave covers an 8 x 8R pixel tile (ray r of lane l: column
 // l % 8, row entry 8r + l / 8 of the tile), one camera sample per pixel. KS = 2 / 4 (spp 4 / 16,
 // R = 1): the KS x KS samples of a pixel sit in consecutive lanes and a wave covers an
@@ -1692,6 +1749,30 @@ static_assert(packet_block(0) <= kPopCullThreads && packet_block(1) <= kPopCullT
 #include "rt_trace_packet.inc"
 #undef RT_PK_NAME
 #undef RT_PK_SGPR_ATTR
+// ... and a third time for the fused frame + G-buffer launch (rt_dispatch_rays_gbuffer):
+// k_trace_frame_gbuffer_packet, the same body with the planes' parameters as a seventh kernel argument
+// (RT_PK_GBUF), handed to shade_sample_packet. Its SGPR budget is the compiler's own (LAMBERT_SHADOW: 65 VGPRs, 94
+// SGPRs, 6 SGPR spills, no scratch, 7 waves per SIMD). RT_FUSED_PLAIN_SGPRS=1 builds it under the plain kernels' 80-SGPR
+// cap: the 128 camera floats of MotionCams crowd the walk (30 SGPR spills) and the 65 VGPRs still hold it at 7 waves;
+// with RT_FUSED_LS_WAVES=8 as well it reaches 8 waves at 20 B of scratch per lane. Both measured slower on C2 at 1080p
+// (DESIGN §3.12 has the kres rows and the A/B of the three builds).
+#ifndef RT_FUSED_PLAIN_SGPRS
+#define RT_FUSED_PLAIN_SGPRS 0
+#endif
+#ifndef RT_FUSED_LS_WAVES
+#define RT_FUSED_LS_WAVES RT_LS_WAVES  // the fused LAMBERT_SHADOW kernel's occupancy target (RT_LS_WAVES: 7)
+#endif
+#define RT_PK_NAME k_trace_frame_gbuffer_packet
+#if RT_FUSED_PLAIN_SGPRS
+#define RT_PK_SGPR_ATTR RT_PLAIN_SGPR_ATTR
+#else
+#define RT_PK_SGPR_ATTR RT_PACKET_SGPR_ATTR
+#endif
+#define RT_PK_GBUF 1
+#include "rt_trace_packet.inc"
+#undef RT_PK_NAME
+#undef RT_PK_SGPR_ATTR
+#undef RT_PK_GBUF
 
 
 template <bool ANY_HIT, bool STATS, bool CULL, int TT = 0>
@@ -2132,6 +2213,13 @@ constexpr FrameKernel canonical(FrameKernel k) {
   }
   if (k.stats) k.mf = true;            // counter passes always take the general (MF) kernel: fewer instantiations
   if (RT_PACKET_RAYS != 1) k.ks = 0;   // sample lanes need one ray per lane
+  // The fused frame + G-buffer launch (rt_dispatch_rays_gbuffer): one frame, one sample per pixel, the plain grid. Its
+  // kernels follow the rules above (counters and the watertight test take the general kernel) and exist for the
+  // one-sample layout only: the tile layout, or the sample loop's single pass where a lane holds several rays.
+  if (k.gb) {
+    k.bal = false;
+    k.ks = RT_PACKET_RAYS == 1 ? 1 : 0;
+  }
   if (!k.packet) {                     // the per-lane kernel has none of the three
     k.ks = 0;
     k.bal = false;
@@ -2141,14 +2229,17 @@ constexpr FrameKernel canonical(FrameKernel k) {
 }
 constexpr bool same(const FrameKernel& a, const FrameKernel& b) {
   return a.packet == b.packet && a.mode == b.mode && a.stats == b.stats && a.ks == b.ks && a.bal == b.bal &&
-         a.mf == b.mf && a.tt == b.tt;
+         a.mf == b.mf && a.tt == b.tt && a.gb == b.gb;
 }
 
 // A selection's kernel: what to launch, and what to ask the runtime about (trace_wave_slots). fn null: no such kernel
 // (a shade mode out of range).
 using FrameKernelFn = void (*)(SceneView, FrameParams, const uint32_t*, uint32_t*, float4*, unsigned long long*);
+using FusedKernelFn = void (*)(SceneView, FrameParams, const uint32_t*, uint32_t*, float4*, unsigned long long*,
+                               GbufMotionParams);
 struct FrameLaunch {
   FrameKernelFn fn = nullptr;
+  FusedKernelFn fused = nullptr;  // a fused selection's kernel (FrameKernel::gb), fn then null
   int block = 0;
   size_t lds = 0;  // dynamic LDS: the per-lane kernel's stacks
 };
@@ -2157,11 +2248,14 @@ FrameLaunch frame_launch(const FrameKernel& sel, const SceneView& sc) {
   l.block = sel.packet ? packet_block(sel.ks) : kBlock;
   l.lds = sel.packet ? 0 : (size_t)sc.lds_cap * kBlock * sizeof(int);
   lift(
-      [&](auto P, auto M, auto S, auto KS, auto B, auto MF, auto T) {
-        constexpr FrameKernel k{P.value, M.value, S.value, KS.value, B.value, MF.value, T.value};
+      [&](auto P, auto M, auto S, auto KS, auto B, auto MF, auto T, auto GB) {
+        constexpr FrameKernel k{P.value, M.value, S.value, KS.value, B.value, MF.value, T.value, GB.value};
         constexpr int R = RT_PACKET_RAYS;
         if constexpr (same(canonical(k), k)) {
-          if constexpr (!k.packet) l.fn = &k_trace_frame<k.mode, k.stats, k.tt>;
+          if constexpr (k.gb && !k.packet) l.fused = &k_trace_frame_gbuffer<k.mode, k.stats, k.tt>;
+          else if constexpr (k.gb)
+            l.fused = &k_trace_frame_gbuffer_packet<k.mode, k.stats, R, k.ks, k.bal, k.mf, k.tt>;
+          else if constexpr (!k.packet) l.fn = &k_trace_frame<k.mode, k.stats, k.tt>;
           // k_trace_frame_packet8: see its definition (the launches that can use the eighth wave)
           else if constexpr (!k.bal && !k.stats && k.mode != 0 && k.ks >= 1 && !k.tt)
             l.fn = &k_trace_frame_packet8<k.mode, k.stats, R, k.ks, k.bal, k.mf>;
@@ -2169,7 +2263,7 @@ FrameLaunch frame_launch(const FrameKernel& sel, const SceneView& sc) {
         }
       },
       Flag{sel.packet}, OneOf<0, 1, 2, 3>{sel.mode}, Flag{sel.stats}, OneOf<0, 1, 2, 4>{sel.ks}, Flag{sel.bal},
-      Flag{sel.mf}, OneOf<0, 1>{sel.tt});
+      Flag{sel.mf}, OneOf<0, 1>{sel.tt}, Flag{sel.gb});
   return l;
 }
 
@@ -2202,7 +2296,7 @@ PacketGeometry packet_geometry(const SceneView& sc, const FrameParams& fp, int s
 }
 
 FrameKernel select_frame_kernel(const SceneView& sc, const FrameParams& fp, const PacketGeometry& g, bool stats,
-                                bool balance) {
+                                bool balance, bool fused) {
   FrameKernel k;
   k.packet = g.packet;
   // the reference scene's parity config pins reflectivity to 0: a kernel without
@@ -2213,22 +2307,27 @@ FrameKernel select_frame_kernel(const SceneView& sc, const FrameParams& fp, cons
   k.bal = balance;
   k.mf = fp.nframes > 1u || fp.out_bpp != 4u;  // several frames, or RGB8 strips
   k.tt = sc.tri_test ? 1 : 0;
+  k.gb = fused;
   return canonical(k);
 }
 
 hipError_t launch_trace_frame(const SceneView& sc, const FrameParams& fp, const uint32_t* d_rows,
                               void* rgba8, float* rgba32f, unsigned long long* d_stats, bool stats,
-                              int schedule, uint32_t plan_items, hipStream_t s) {
+                              int schedule, uint32_t plan_items, hipStream_t s, const GbufMotionParams* gbuf) {
   const PacketGeometry g = packet_geometry(sc, fp, schedule);
-  const FrameKernel k = select_frame_kernel(sc, fp, g, stats, fp.plan || fp.cost);
+  const FrameKernel k = select_frame_kernel(sc, fp, g, stats, fp.plan || fp.cost, gbuf != nullptr);
   const FrameLaunch l = frame_launch(k, sc);
-  if (!l.fn) return hipErrorInvalidValue;
+  if (gbuf ? !l.fused : !l.fn) return hipErrorInvalidValue;
   // per lane 16 x 16 pixel workgroups; the packet kernel's plain grid, or (tile balance) one wave per work-list
   // item, as many as the list's budget
   const dim3 grid = !k.packet             ? dim3((fp.width + 15) / 16, (fp.nrows + 15) / 16, fp.nframes)
                     : (k.bal && fp.plan) ? dim3((plan_items + g.wl - 1) / g.wl)
                                          : dim3(g.grid_x, g.grid_y, fp.nframes);
-  hipLaunchKernelGGL(l.fn, grid, dim3(l.block), l.lds, s, sc, fp, d_rows, (uint32_t*)rgba8, (float4*)rgba32f, d_stats);
+  if (gbuf)  // the fused kernels: the planes' parameters as one more argument
+    hipLaunchKernelGGL(l.fused, grid, dim3(l.block), l.lds, s, sc, fp, d_rows, (uint32_t*)rgba8, (float4*)rgba32f,
+                       d_stats, *gbuf);
+  else
+    hipLaunchKernelGGL(l.fn, grid, dim3(l.block), l.lds, s, sc, fp, d_rows, (uint32_t*)rgba8, (float4*)rgba32f, d_stats);
   return hipGetLastError();
 }
 

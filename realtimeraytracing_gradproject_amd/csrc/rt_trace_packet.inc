@@ -1,15 +1,29 @@
 // rt_trace_packet.inc — the packet frame kernel's definition, included twice by rt_trace.hip (inside namespace
-// rt::{anonymous}) under two names and register budgets: RT_PK_NAME / RT_PK_SGPR_ATTR (see there). Not a header.
+// rt::{anonymous}) under its names and register budgets: RT_PK_NAME / RT_PK_SGPR_ATTR (see there). Not a header.
+// RT_PK_GBUF defined: the fused frame + G-buffer kernel, with the planes' parameters as one more kernel argument that
+// shade_sample_packet stores from after the primary walk; otherwise the argument block and the body are the frame's.
+#ifdef RT_PK_GBUF
+#define RT_PK_GBUF_PARAM , GbufMotionParams gbuf
+#define RT_PK_GBUF_ARGS , FusedPlanes{gbuf, out}
+#define RT_PK_LS_WAVES RT_FUSED_LS_WAVES
+#else
+#define RT_PK_GBUF_PARAM
+#define RT_PK_GBUF_ARGS
+#define RT_PK_LS_WAVES RT_LS_WAVES
+#endif
 template <int MODE, bool STATS, int R, int KS, bool BAL, bool MF, int TT = 0>
 __global__ __launch_bounds__(packet_block(KS)) __attribute__((amdgpu_waves_per_eu(
     TT ? 1  // the watertight kernels (TT 1) keep the allocator's choice: the occupancy targets below were tuned for
             // Moller-Trumbore's registers
-    : (MODE == 1 && !STATS) ? (KS == 0 ? RT_SPP_WAVES : (KS == 1 ? RT_LS_WAVES : RT_KS_WAVES))
+    : (MODE == 1 && !STATS) ? (KS == 0 ? RT_SPP_WAVES : (KS == 1 ? RT_PK_LS_WAVES : RT_KS_WAVES))
     : (MODE == 3 && !STATS) ? (KS == 0 ? RT_SPP_WAVES : (KS == 1 ? RT_REF0_WAVES : RT_KS_WAVES))
                             : ((MODE == 0 && !STATS && KS == 1) ? RT_REF_WAVES : 1)))) RT_PK_SGPR_ATTR
 void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows, uint32_t* __restrict__ rgba8,
-                float4* __restrict__ rgba32f, unsigned long long* __restrict__ stats) {
+                float4* __restrict__ rgba32f, unsigned long long* __restrict__ stats RT_PK_GBUF_PARAM) {
   static_assert(KS <= 1 || R == 1, "sample lanes need one ray per lane");
+#ifdef RT_PK_GBUF
+  static_assert(KS <= 1 && !BAL, "the fused launch: one sample per pixel on the plain grid");
+#endif
   stage_top_nodes<packet_block(KS)>(sc);  // RT_LDS_TOP only
 #if RT_WAVE_TIMES
   const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
@@ -70,7 +84,7 @@ void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows,
   const uint32_t k = KS == 1 ? 1u : (KS > 1 ? (uint32_t)KS : fp.spp_side);
   const FrameCam& cam = fp.cam[MF ? bz : 0u];
   if (KS == 1) {
-    shade_sample_packet<MODE, STATS, R, TT>(sc, fp, cam, px, py, 0.5f, 0.5f, inimg, acc, cnt);  // (0 + 0.5) / 1
+    shade_sample_packet<MODE, STATS, R, TT>(sc, fp, cam, px, py, 0.5f, 0.5f, inimg, acc, cnt RT_PK_GBUF_ARGS);  // (0 + 0.5) / 1
   } else if (KS > 1) {
     // this lane's sample (sx, sy) of the k x k grid, the sample loop's offsets
     const float ox = ((float)(sample % KS) + 0.5f) / (float)KS;
@@ -99,7 +113,7 @@ void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows,
       for (uint32_t sx = 0; sx < k; ++sx) {
         const float ox = ((float)sx + 0.5f) / (float)k;
         const float oy = ((float)sy + 0.5f) / (float)k;
-        shade_sample_packet<MODE, STATS, R, TT>(sc, fp, cam, px, py, ox, oy, inimg, col, cnt);
+        shade_sample_packet<MODE, STATS, R, TT>(sc, fp, cam, px, py, ox, oy, inimg, col, cnt RT_PK_GBUF_ARGS);
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = add(acc[r], col[r]);
       }
@@ -145,3 +159,6 @@ void RT_PK_NAME(SceneView sc, FrameParams fp, const uint32_t* __restrict__ rows,
   }
 #endif
 }
+#undef RT_PK_GBUF_PARAM
+#undef RT_PK_GBUF_ARGS
+#undef RT_PK_LS_WAVES
