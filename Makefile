@@ -191,10 +191,21 @@ $(ASAN)/upscale_asan.o: tools/upscale_asan.cpp include/rt_api.h | $(ASAN)
 $(ASAN)/upscale_check: $(ASAN)/upscale_asan.o $(ASAN_API_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
+# the same for the soft-shadow host twins (rt_host_shadow_rays, rt_host_shade_resolve: per-light, per-sample and
+# strided-plane indexing on exact-size heap blocks):
+#   make asan-shadow && build/asan/shadow_check
+asan-shadow: $(ASAN)/shadow_check
+
+$(ASAN)/shadow_asan.o: tools/shadow_asan.cpp include/rt_api.h | $(ASAN)
+	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
+
+$(ASAN)/shadow_check: $(ASAN)/shadow_asan.o $(ASAN_API_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
+
 $(ASAN):
 	mkdir -p $@
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VDIR)
 
-.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale
+.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow

@@ -33,7 +33,9 @@ extern "C" {
  * rt_dispatch_ao, rt_host_ao_rays and rt_ao_params, and rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous, their host
  * twins rt_host_denoise_guide, rt_host_ao_accumulate, rt_host_ao_atrous, rt_ao_temporal_params and
  * rt_ao_atrous_params, and rt_tile_plan_probe with rt_tile_plan_args, and rt_upscale, rt_host_upscale,
- * rt_upscale_params, rt_camera_jitter and rt_jitter_halton, and rt_dispatch_rays_gbuffer. */
+ * rt_upscale_params, rt_camera_jitter and rt_jitter_halton, and rt_dispatch_rays_gbuffer, and rt_dispatch_shadow,
+ * rt_shade_resolve, their host twins rt_host_shadow_rays and rt_host_shade_resolve, rt_shadow_params and
+ * rt_resolve_inputs. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -497,6 +499,54 @@ typedef struct { uint32_t samples; uint32_t seed; float radius; float tmin; } rt
 rt_status rt_dispatch_ao(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
                          const rt_ao_params* params, float* ao_dev, void* hip_stream);
 
+/* Parameters of the visibility pass. samples: rays per pixel and light, 1..64; seed: any value (the same seed gives
+ * the same planes, bit for bit); light_radius: the radius of every light's sphere, finite and >= 0 (0: a point light,
+ * the frame kernels' hard shadow); tmin: the rays' tmin, finite and >= 0 (the frame kernels' shadow rays use 0.01, and
+ * so does the Python binding's default). */
+typedef struct { uint32_t samples; uint32_t seed; float light_radius; float tmin; } rt_shadow_params;
+
+/* The visibility pass: per pixel of the frame rt_dispatch_gbuffer describes and per light of
+ * rt_set_shading, the share of `samples` any-hit rays from the primary hit point towards a spherical light that arrive,
+ * in one launch that writes 4 bytes per pixel and light.
+ * Everything rt_dispatch_ao documents about W, H, rows, nrows, the camera ray, the schedule rule and its per-lane
+ * fall-back, rt_set_triangle_test (the primary ray and the shadow rays both follow it), streams, slot rings, the TLAS
+ * double buffer, rt_forget_stream and refit-before-rebuild holds here: the passes run the same host functions.
+ * Beyond a camera and a current TLAS it needs the context's lights: rt_set_shading must have been called (its shade
+ * mode, spp and material are not read). It changes no other launch's results.
+ * Output: plane l (0 <= l < nlights) starts at vis_dev + l * plane_stride floats and holds nrows * W floats in
+ * rt_dispatch_rays' compact order; plane_stride >= nrows * W, 0 meaning nrows * W (the planes back to back). vis_dev is
+ * device memory, 4-byte aligned. Each plane is a float plane in [0, 1] that rt_ao_accumulate / rt_ao_atrous take as
+ * they take an AO plane.
+ * The value, for pixel (px, py) (py the GLOBAL row rows[r]) with camera ray (O, D), primary hit (over [0, 1e5]) at
+ * distance t in an instance of hit group g, and G-buffer normal N (rt_gbuffer.normal's xyz, bit for bit):
+ *   P = O + D t;  n_s = g == RT_HITGROUP_PLANE ? N : -N  (the normal the Lambert kernels shade with)
+ *   per light l at position lp:  L = normalize(lp - P), nl = dot(n_s, L), lit = nl > 0  (false for a NaN normal)
+ *   not lit: exactly 0.0f, no ray traced.  A primary miss: exactly 1.0f in every plane, no ray traced.
+ *   lit: sample k = 0 .. samples - 1 has target = lp when light_radius == 0 (no sample is generated), else
+ *     target = lp + light_radius * sph(base_l, k), componentwise, with rt_dispatch_ao's hash, base and sphere point:
+ *     base_l = hash(px + hash(py + hash(seed ^ hash(l + 1)))), sph(base, k) from hash(base + 2k), hash(base + 2k + 1);
+ *   ray k = (origin P, tmin, direction normalize(normalize(target - P)), tmax 100000): normalised twice, as both frame
+ *     kernels normalise the already normalised L again, so the radius-0 ray is theirs to the bit;
+ *   value = (float)unoccluded / (float)samples, unoccluded = the rays for which an any-hit search (rt_trace_rays with
+ *   RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH) finds nothing. Sample k does not depend on `samples`.
+ * float32, no contraction, IEEE quotients, rt_dispatch_ao's arithmetic: the device and rt_host_shadow_rays give the
+ * same rays to the bit. With light_radius 0 and samples > 1 a light's rays are identical and all are traced. tmax is
+ * the frame's 1e5, not the distance to the light: an occluder behind the light still shadows, as in the frame kernels.
+ * With light_radius 0, samples 1 and tmin 0.01 the planes hold 1 - occl of the RT_SHADE_LAMBERT_SHADOW frame's shadow
+ * rays, and rt_shade_resolve turns them into that frame bit for bit.
+ * rt_set_stats: RT_STAT_PRIMARY_RAYS and RT_STAT_PIXELS grow by nrows * W, RT_STAT_DISPATCHES by 1,
+ * RT_STAT_SHADOW_RAYS by (lit pixel-light pairs) * samples, RT_STAT_REFLECTION_RAYS by 0: with radius 0 and one sample
+ * exactly what one RT_SHADE_LAMBERT_SHADOW frame adds to these five. The traversal counters grow as the walks make them
+ * grow (not part of the contract).
+ * Errors: RT_E_INVALID with nothing written (rt_last_error says which) for NULL params or vis_dev, vis_dev not 4-byte
+ * aligned, samples outside 1..64, light_radius not finite or < 0, tmin not finite or < 0, a non-zero plane_stride
+ * below nrows * W, rt_set_shading never called ("shading not set"), and every RT_E_INVALID case of
+ * rt_dispatch_gbuffer (sizes, rows, no TLAS, no camera, a refit without its rt_tlas_build); RT_E_UNSUPPORTED as
+ * rt_dispatch_gbuffer.
+ * No reference counterpart: the reference's shadow ray is PlaneClosestHit's single ray to light 0 (Hit.hlsl:207-241). */
+rt_status rt_dispatch_shadow(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                             const rt_shadow_params* params, float* vis_dev, uint64_t plane_stride, void* hip_stream);
+
 /* ---- AO filter: what turns a few AO rays per pixel into a usable plane ----------------------------
  * Three passes over planes the caller owns (device memory): a guide plane from the G-buffer, a temporal accumulation
  * through rt_gbuffer_motion.motion, and an edge-aware a-trous blur. All three are asynchronous on hip_stream (NULL =
@@ -635,6 +685,42 @@ rt_status rt_upscale(rt_ctx_t ctx, uint32_t w, uint32_t h, uint32_t W, uint32_t 
                      const float* color_cur, const float* motion_cur, const float* motion_prev,
                      const float* color_prev, const float* hist_prev, float* color_out, float* hist_out,
                      void* rgba8_out, void* hip_stream);
+
+/* Inputs of rt_shade_resolve: whole row-major W x H planes (entry y W + x), device pointers. */
+typedef struct {
+  const uint32_t* hits;   /* W*H x 4, rt_gbuffer.hits */
+  const float*    normal; /* W*H x 4, rt_gbuffer.normal */
+  const uint32_t* object; /* W*H x 2, rt_gbuffer.object */
+  const float*    vis;    /* nlights planes of W*H floats, or NULL: every light fully visible */
+  uint64_t        vis_stride; /* floats between planes; 0 = W*H */
+  const float*    ao;     /* W*H floats, or NULL: 1 */
+} rt_resolve_inputs;
+
+/* The deferred resolve: G-buffer planes, rt_dispatch_shadow's visibility planes (filtered or not) and
+ * optionally an AO plane -> the colour frame, in the format rt_upscale and the display take. One pointwise launch,
+ * asynchronous on hip_stream (NULL = the context's stream); it allocates nothing and needs the context's camera
+ * (rt_set_camera) and lights (rt_set_shading; mode, spp and material are not read) but no TLAS. Whole frames only, as
+ * for the AO filter. color_out: W*H x 4 floats, 16-byte aligned, alpha 1.0f; rgba8_out: optional, W*H x 4 bytes,
+ * R8G8B8A8_UNORM as rt_dispatch_rays packs it, alpha 255.
+ * Pixel i = y W + x:
+ *   hits[4i+3] == 0 (a miss): colour = (0, 0.2f, 0.7f - 0.3f * ((float)y / (float)H)), the frame's miss colour.
+ *   a hit: (O, D) = the pixel's camera ray, t = hits[4i] as float, P = O + D t,
+ *     n_s = object[2i+1] == RT_HITGROUP_PLANE ? normal[4i..4i+2] : -normal[4i..4i+2];  c = 0;
+ *     for l = 0 .. nlights - 1: L = normalize(lp_l - P), nl = dot(n_s, L);
+ *       if nl > 0: c = c + nl * ((0.3f * a) + (0.7f * v_l)),  a = ao ? ao[i] : 1,  v_l = vis ? vis[l * stride + i] : 1;
+ *     c = c / (float)nlights;  colour = (c, c, c).
+ * float32, no contraction, in the order written (the AO filter's arithmetic rules); rt_host_shade_resolve agrees to the
+ * bit. In float32 0.3f * 1 + 0.7f * 1 == 1.0f and 0.3f * 1 + 0.7f * 0 == 0.3f exactly, the frame kernels' occl ? 0.3f
+ * : 1.0f. Hence the anchor: with the planes of rt_dispatch_gbuffer, vis from rt_dispatch_shadow at light_radius 0,
+ * samples 1 and tmin 0.01, and ao NULL, color_out and rgba8_out equal rt_dispatch_rays' float and RGBA8 frames in
+ * RT_SHADE_LAMBERT_SHADOW at one sample per pixel, bit for bit; with vis NULL as well, its RT_SHADE_PRIMARY frames.
+ * Errors, nothing written, rt_last_error naming the cause: RT_E_INVALID for a NULL `in`, a NULL hits, normal or object
+ * plane, a NULL color_out, a misaligned plane (hits, normal, color_out: 16 bytes; object: 8; vis, ao, rgba8_out: 4),
+ * an output equal to an input or to the other output (pointer EQUALITY, the filters' rule), W or H of 0, a non-zero
+ * vis_stride below W * H, no camera, no shading; RT_E_UNSUPPORTED for W * H >= 2^31.
+ * No reference counterpart: the reference shades inside its hit programs. */
+rt_status rt_shade_resolve(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_resolve_inputs* in, float* color_out,
+                           void* rgba8_out, void* hip_stream);
 
 /* Stream lifetime: the context notes (host-side, no event per launch) which streams launched with the current
  * TLAS version, and records one event on each of them when the next rt_tlas_build swaps that version out; the tile
@@ -910,6 +996,23 @@ rt_status rt_host_upscale(uint32_t w, uint32_t h, uint32_t W, uint32_t H, const 
                           const float* color_cur, const float* motion_cur, const float* motion_prev,
                           const float* color_prev, const float* hist_prev, float* color_out, float* hist_out,
                           void* rgba8_out);
+
+/* The rays rt_dispatch_shadow traces for n pixels, on the host: the check of its planes (it calls the functions the
+ * shadow kernels call; trace the rays with rt_trace_rays' any-hit search and count). cam_rays, t, normal, px, py as
+ * rt_host_ao_rays; hit_group: n words, the hit's group (rt_gbuffer.object's second word); lights, nlights (1..16) as
+ * rt_set_shading; params as rt_dispatch_shadow. rays_out: n x nlights x samples x 8 floats, pixel i, light l, sample k
+ * at entry (i * nlights + l) * samples + k, (P, tmin, d, 100000); lit_out: n x nlights bytes or NULL, 1 where the
+ * pixel faces the light (nl > 0). A pair that is not lit gets zero-filled rays. The caller leaves a primary miss out
+ * (its planes hold 1). All host memory. Null arrays with n > 0, bad params or a bad light count: RT_E_INVALID. */
+rt_status rt_host_shadow_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* hit_group,
+                              const uint32_t* px, const uint32_t* py, uint32_t n, const rt_light* lights,
+                              uint32_t nlights, const rt_shadow_params* params, float* rays_out, uint8_t* lit_out);
+
+/* rt_shade_resolve on host arrays: cb and lights, nlights in place of the context's camera (rt_set_camera's layout;
+ * the origin and the inverses are derived from it as rt_set_camera's are) and lights, no stream; the same checks less
+ * the 16-byte alignment (4 bytes will do), the same per-pixel function, so the same bits. */
+rt_status rt_host_shade_resolve(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights, uint32_t nlights,
+                                const rt_resolve_inputs* in, float* color_out, void* rgba8_out);
 
 /* Sub-pixel jitter through the camera buffer alone (no kernel knows about it). out = cb (rt_set_camera's layout) with
  * the projection and its inverse replaced so that, for a W x H frame and (jx, jy) in pixels, finite, |j| < 0.5:

@@ -91,6 +91,18 @@ class rt_ao_params(ctypes.Structure):
                 ("tmin", ctypes.c_float)]
 
 
+class rt_shadow_params(ctypes.Structure):
+    """include/rt_api.h rt_shadow_params: samples (1..64), seed, light_radius, tmin of rt_dispatch_shadow."""
+    _fields_ = [("samples", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("light_radius", ctypes.c_float),
+                ("tmin", ctypes.c_float)]
+
+
+class rt_resolve_inputs(ctypes.Structure):
+    """include/rt_api.h rt_resolve_inputs: the planes rt_shade_resolve reads (vis and ao may be None)."""
+    _fields_ = [("hits", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("object", ctypes.c_void_p),
+                ("vis", ctypes.c_void_p), ("vis_stride", ctypes.c_uint64), ("ao", ctypes.c_void_p)]
+
+
 class rt_ao_temporal_params(ctypes.Structure):
     """include/rt_api.h rt_ao_temporal_params: max_history (1..1024), depth_tol, normal_cos of rt_ao_accumulate."""
     _fields_ = [("max_history", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
@@ -163,6 +175,8 @@ SIGNATURES = [
     ("rt_dispatch_gbuffer_motion", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_gbuffer_motion), _FP, _P]),
     ("rt_dispatch_rays_gbuffer", _I, [_P, _U32, _U32, _P, _U32, _P, _P, ctypes.POINTER(rt_gbuffer_motion), _FP, _P]),
     ("rt_dispatch_ao", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
+    ("rt_dispatch_shadow", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_shadow_params), _P, ctypes.c_uint64, _P]),
+    ("rt_shade_resolve", _I, [_P, _U32, _U32, ctypes.POINTER(rt_resolve_inputs), _P, _P, _P]),
     ("rt_denoise_guide", _I, [_P, _U32, _P, _P, _U32, _P, _P]),
     ("rt_ao_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P,
                               _P]),
@@ -213,6 +227,10 @@ SIGNATURES = [
     ("rt_host_motion_project", _I, [_P, _P, _U32, _P, _P, _U32, _U32, _P]),
     ("rt_host_motion_vectors", _I, [_P, _P, _U32, _U32, _P, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
     ("rt_host_ao_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
+    ("rt_host_shadow_rays", _I, [_P, _P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_light), _U32,
+                                 ctypes.POINTER(rt_shadow_params), _P, _P]),
+    ("rt_host_shade_resolve", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_light), _U32, ctypes.POINTER(rt_resolve_inputs),
+                                   _P, _P]),
     ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
     ("rt_host_ao_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rt_host_ao_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P]),
@@ -479,6 +497,75 @@ def host_ao_rays(cam_rays, t, normal, px, py, samples: int, radius: float, tmin:
     if st != RT_OK:
         raise RtError(st, "rt_host_ao_rays")
     return rays, valid
+
+
+def _lights_array(lights):
+    """An rt_light array from (colour, position, intensity) triples, Context.set_shading's form."""
+    lights = list(lights)
+    arr = (rt_light * len(lights))()
+    for k, (col, pos, inten) in enumerate(lights):
+        arr[k].color[:] = [float(v) for v in col]
+        arr[k].position[:] = [float(v) for v in pos]
+        arr[k].intensity = float(inten)
+    return arr
+
+
+def host_shadow_rays(cam_rays, t, normal, hit_group, px, py, lights, samples: int = 1, light_radius: float = 0.0,
+                     tmin: float = 0.01, seed: int = 0):
+    """rt_host_shadow_rays: the rays rt_dispatch_shadow traces, on the host (no GPU). cam_rays: (n, 8) camera rays in
+    trace_rays' layout; t: n hit distances; normal: (n, 4) G-buffer normals; hit_group: n hit groups (the object
+    plane's second word); px, py: the pixels' global coordinates; lights: set_shading's (colour, position, intensity)
+    triples. Returns (rays, lit): (n, nlights, samples, 8) float32 (P, tmin, d, 100000) and (n, nlights) uint8; a pair
+    that is not lit has zero rays and lit 0. Primary misses are the caller's to leave out."""
+    cr = np.ascontiguousarray(cam_rays, dtype=np.float32).reshape(-1, 8)
+    n = cr.shape[0]
+    tt = _f32(t, n)
+    nr = _f32(normal, 4 * n)
+    g = np.ascontiguousarray(hit_group, dtype=np.uint32).ravel()
+    x = np.ascontiguousarray(px, dtype=np.uint32).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if x.size != n or y.size != n or g.size != n:
+        raise ValueError(f"expected {n} pixel coordinates and hit groups, got {x.size}, {y.size} and {g.size}")
+    arr = _lights_array(lights)
+    nl = len(arr)
+    if not 1 <= int(samples) <= 64:  # rt_host_shadow_rays' own limits, checked before the output is sized by them
+        raise RtError(RT_E_INVALID, f"rt_host_shadow_rays: samples {samples} outside 1..64")
+    if not 1 <= nl <= 16:
+        raise RtError(RT_E_INVALID, f"rt_host_shadow_rays: {nl} lights, outside 1..16")
+    p = rt_shadow_params(samples, seed, light_radius, tmin)
+    rays = np.zeros((n, nl, int(samples), 8), np.float32)
+    lit = np.zeros((n, nl), np.uint8)
+    st = lib.rt_host_shadow_rays(_vp(cr), _vp(tt), _vp(nr), _vp(g), _vp(x), _vp(y), n, arr, nl, ctypes.byref(p),
+                                 _vp(rays), _vp(lit))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_shadow_rays")
+    return rays, lit
+
+
+def host_shade_resolve(width: int, height: int, camera, lights, hits, normal, object, vis=None, ao=None,  # noqa: A002
+                       want_rgba8: bool = False):
+    """rt_host_shade_resolve: the deferred resolve on the host (no GPU). camera: the 64-float camera buffer; lights:
+    set_shading's triples; hits (n, 4) uint32, normal (n, 4) float32, object (n, 2) uint32 with n = width * height;
+    vis: (nlights, n) float32 or None (every light fully visible); ao: n float32 or None (1). Returns color (n, 4)
+    float32 and, with want_rgba8, the (n, 4) uint8 frame as a second."""
+    n = width * height
+    cb = _f32(camera, 64)
+    arr = _lights_array(lights)
+    nl = len(arr)
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    oo = np.ascontiguousarray(object).view(np.uint32).reshape(-1)
+    if hh.size != 4 * n or oo.size != 2 * n:
+        raise ValueError(f"expected {4 * n} hit words and {2 * n} object words, got {hh.size} and {oo.size}")
+    nn = _f32(normal, 4 * n)
+    vv = None if vis is None else _f32(vis, nl * n)
+    aa = None if ao is None else _f32(ao, n)
+    inp = rt_resolve_inputs(_vp(hh), _vp(nn), _vp(oo), _vp(vv), 0, _vp(aa))
+    out = np.zeros((n, 4), np.float32)
+    out8 = np.zeros((n, 4), np.uint8) if want_rgba8 else None
+    st = lib.rt_host_shade_resolve(width, height, _fptr(cb), arr, nl, ctypes.byref(inp), _vp(out), _vp(out8))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_shade_resolve")
+    return (out, out8) if want_rgba8 else out
 
 
 def host_denoise_guide(normal, depth):
@@ -1008,6 +1095,7 @@ class Context:
         m.albedo[:] = [float(v) for v in material[0:3]]
         m.roughness, m.metallic, m.reflectivity = (float(v) for v in material[3:6])
         self._check(self._lib.rt_set_shading(self._h, arr, len(lights), ctypes.byref(m), mode, spp), "rt_set_shading")
+        self._nlights = len(lights)  # the visibility planes' count (dispatch_shadow, shade_resolve size their tensors)
 
     def set_schedule(self, schedule: int):
         self._check(self._lib.rt_set_schedule(self._h, schedule), "rt_set_schedule")
@@ -1171,6 +1259,58 @@ class Context:
         p = rt_ao_params(samples, seed, radius, tmin)
         self._check(self._lib.rt_dispatch_ao(self._h, width, height, rp, nr, ctypes.byref(p), _ptr(ao), stream),
                     "rt_dispatch_ao")
+
+    def _vis_planes(self, method: str, vis, entries: int, stride: int, nlights: Optional[int]):
+        """Checks a tensor of visibility planes: `nlights` planes (None: the count Context.set_shading was last given)
+        of `entries` floats, `stride` floats apart (0: back to back), must fit in it. The library cannot check a
+        tensor's size, so a context whose lights were set some other way (the raw library) must say how many there
+        are. A stride below `entries` is left to the library to refuse; a raw address is not checked."""
+        if vis is None or isinstance(vis, int):
+            return
+        nl = getattr(self, "_nlights", None) if nlights is None else int(nlights)
+        if nl is None:
+            raise ValueError(f"{method}: the light count is not known to this Context (set_shading was not called "
+                             f"through it): pass nlights, so that the planes' tensor can be checked")
+        need = (nl - 1) * max(stride or entries, entries) + entries
+        if vis.element_size() != 4 or not vis.is_contiguous() or vis.numel() < need:
+            raise ValueError(f"{method}: vis must be a contiguous tensor of at least {need} 32-bit elements ({nl} "
+                             f"planes of {entries}), got {vis.numel()} of {vis.element_size()} bytes")
+
+    def dispatch_shadow(self, width: int, height: int, vis, samples: int = 1, light_radius: float = 0.0,
+                        tmin: float = 0.01, seed: int = 0, rows: Optional[np.ndarray] = None, plane_stride: int = 0,
+                        stream: Optional[int] = None, nlights: Optional[int] = None):
+        """rt_dispatch_shadow: per light of set_shading a visibility plane of the frame dispatch_gbuffer describes, one
+        float per pixel (nrows * width entries in dispatch()'s compact row order): the share of `samples` (1..64)
+        any-hit rays from the primary hit towards the light's sphere (radius light_radius; 0: its centre, the frame's
+        hard shadow) that arrive; 0.0 where the pixel does not face the light, 1.0 on a miss. vis: a device tensor (or
+        a raw address) holding the planes plane_stride floats apart (0: nrows * width, back to back). Each plane feeds
+        ao_accumulate / ao_atrous as an AO plane does; host_shadow_rays gives the rays. nlights: the number of planes
+        the tensor is checked to hold (None: the count set_shading was given through this Context)."""
+        rp, nr, _keep = self._rows_arg(rows, height)
+        self._vis_planes("dispatch_shadow", vis, nr * width, plane_stride, nlights)
+        p = rt_shadow_params(samples, seed, light_radius, tmin)
+        self._check(self._lib.rt_dispatch_shadow(self._h, width, height, rp, nr, ctypes.byref(p), _ptr(vis),
+                                                 plane_stride, stream), "rt_dispatch_shadow")
+
+    def shade_resolve(self, width: int, height: int, hits, normal, object, color_out, vis=None, ao=None,  # noqa: A002
+                      rgba8_out=None, vis_stride: int = 0, stream: Optional[int] = None,
+                      nlights: Optional[int] = None):
+        """rt_shade_resolve: the colour frame from dispatch_gbuffer's hits, normal and object planes (whole frames),
+        dispatch_shadow's visibility planes (vis, vis_stride floats apart, 0: width * height; None: every light fully
+        visible) and an AO plane (ao; None: 1), under the context's camera and lights. color_out: width * height x 4
+        floats (alpha 1), the format upscale takes; rgba8_out: optional width * height x 4 bytes. With vis from
+        dispatch_shadow(samples=1, light_radius=0) and ao None the frame is dispatch()'s RT_SHADE_LAMBERT_SHADOW frame
+        bit for bit; with vis None, its RT_SHADE_PRIMARY frame. nlights: as for dispatch_shadow."""
+        n, m = width * height, "shade_resolve"
+        self._vis_planes(m, vis, n, vis_stride, nlights)
+        inp = rt_resolve_inputs(self._plane(m, "hits", hits, 4 * n), self._plane(m, "normal", normal, 4 * n),
+                                self._plane(m, "object", object, 2 * n), _ptr(vis), vis_stride,
+                                self._plane(m, "ao", ao, n))
+        out8 = rgba8_out.view(torch.int32) if isinstance(rgba8_out, torch.Tensor) and rgba8_out.dtype == torch.uint8 \
+            else rgba8_out
+        self._check(self._lib.rt_shade_resolve(self._h, width, height, ctypes.byref(inp),
+                                               self._plane(m, "color_out", color_out, 4 * n),
+                                               self._plane(m, "rgba8_out", out8, n), stream), "rt_shade_resolve")
 
     @staticmethod
     def _plane(method: str, name: str, t, words: int):

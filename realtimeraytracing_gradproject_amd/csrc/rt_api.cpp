@@ -2196,6 +2196,43 @@ rt_status rt_dispatch_ao(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* row
                           });
 }
 
+// What is wrong with an rt_shadow_params, or null (rt_dispatch_shadow and rt_host_shadow_rays check alike).
+static const char* shadow_params_error(const rt_shadow_params* p) {
+  if (!p) return "null params";
+  if (p->samples < 1 || p->samples > 64) return "samples outside 1..64";
+  if (!std::isfinite(p->light_radius) || !(p->light_radius >= 0.0f)) return "light_radius not finite and >= 0";
+  if (!std::isfinite(p->tmin) || !(p->tmin >= 0.0f)) return "tmin not finite and >= 0";
+  return nullptr;
+}
+
+// The G-buffer passes' shared checks and launch sequence (grid_pass_check, grid_pass_launch) around the shadow kernels.
+rt_status rt_dispatch_shadow(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                             const rt_shadow_params* params, float* vis_dev, uint64_t plane_stride, void* stream) {
+  if (!c) return RT_E_INVALID;
+  const std::string fn = "rt_dispatch_shadow";
+  if (const char* why = shadow_params_error(params)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (!vis_dev) return fail(c, RT_E_INVALID, fn + ": null output planes");
+  if ((uintptr_t)vis_dev % 4u) return fail(c, RT_E_INVALID, fn + ": output planes not aligned to 4 bytes");
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  if (st != RT_OK) return st;
+  if (!c->have_shading) return fail(c, RT_E_INVALID, fn + ": shading not set");
+  if (plane_stride != 0 && plane_stride < (uint64_t)nrows * W)
+    return fail(c, RT_E_INVALID, fn + ": plane_stride below nrows * W");
+  rt::ShadowParams sp = {};
+  std::memcpy(sp.lights, c->fp.lights, sizeof(sp.lights));
+  sp.nlights = c->fp.nlights;
+  sp.samples = params->samples;
+  sp.seed = params->seed;
+  sp.light_radius = params->light_radius;
+  sp.tmin = params->tmin;
+  sp.vis = vis_dev;
+  sp.plane_stride = plane_stride ? plane_stride : (uint64_t)nrows * W;
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, sp.gb, "shadow launch",
+                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
+                            return rt::launch_trace_shadow(sv, sp, d_rows, c->d_stats, c->stats_on, c->schedule, s);
+                          });
+}
+
 // ---- AO filter: the argument checks, shared by the device entry points and their host twins (align:
 // the device forms' 16-byte rule for 4-float planes; the host twins pass false) ---------------------------------
 namespace {
@@ -2434,6 +2471,72 @@ rt_status rt_upscale(rt_ctx_t c, uint32_t w, uint32_t h, uint32_t W, uint32_t H,
                                                      color_prev, hist_prev, color_out, hist_out, rgba8_out),
                                           c->upscale_form, pick_stream(c, stream));
   if (e != hipSuccess) return hip_fail(c, e, "upscale launch");
+  return RT_OK;
+}
+
+// ---- Deferred resolve: the argument check shared by rt_shade_resolve and rt_host_shade_resolve (align
+// as above) ------------------------------------------------------------------------------------------------------
+namespace {
+
+const char* resolve_args_error(uint32_t W, uint32_t H, const rt_resolve_inputs* in, const float* color_out,
+                               const void* rgba8_out, bool align, rt_status* st) {
+  *st = RT_E_INVALID;
+  if (W == 0 || H == 0) return "W or H is 0";
+  if ((uint64_t)W * H >= (1ull << 31)) {
+    *st = RT_E_UNSUPPORTED;
+    return "frame of 2^31 pixels or more";
+  }
+  if (!in) return "null inputs";
+  if (!in->hits) return "null hits plane";
+  if (!in->normal) return "null normal plane";
+  if (!in->object) return "null object plane";
+  if (!color_out) return "null color_out";
+  const size_t a4 = align ? 16 : 4;
+  if (misaligned(in->hits, a4)) return "hits plane misaligned";
+  if (misaligned(in->normal, a4)) return "normal plane misaligned";
+  if (misaligned(in->object, align ? 8 : 4)) return "object plane misaligned";
+  if (misaligned(color_out, a4)) return "color_out misaligned";
+  if (misaligned(in->vis, 4) || misaligned(in->ao, 4)) return "a float plane is not aligned to 4 bytes";
+  if (misaligned(rgba8_out, 4)) return "rgba8_out not aligned to 4 bytes";
+  if (in->vis_stride != 0 && in->vis_stride < (uint64_t)W * H) return "vis_stride below W * H";
+  if (rgba8_out && rgba8_out == (const void*)color_out) return "rgba8_out is color_out";
+  for (const void* o : {(const void*)color_out, rgba8_out}) {
+    if (!o) continue;
+    if (o == in->hits || o == in->normal || o == in->object || o == in->vis || o == in->ao)
+      return "an output is an input plane";
+  }
+  return nullptr;
+}
+
+rt::Resolve resolve_of(uint32_t W, uint32_t H, const float cb[64], const rt::LightRec* lights, uint32_t nlights,
+                       const rt_resolve_inputs* in, float* color_out, void* rgba8_out) {
+  rt::Resolve r = {};
+  rt::frame_cam(cb, r.cam);
+  std::memcpy(r.lights, lights, sizeof(rt::LightRec) * nlights);
+  r.nlights = nlights;
+  r.W = W, r.H = H;
+  r.fwidth = (float)W, r.fheight = (float)H;  // exact up to 2^24; rounded beyond, as the trace passes' own are
+  r.hits = in->hits, r.normal = in->normal, r.object = in->object;
+  r.vis = in->vis, r.vis_stride = in->vis_stride ? in->vis_stride : (uint64_t)W * H;
+  r.ao = in->ao;
+  r.color_out = color_out, r.rgba8_out = (uint32_t*)rgba8_out;
+  return r;
+}
+
+}  // namespace
+
+rt_status rt_shade_resolve(rt_ctx_t c, uint32_t W, uint32_t H, const rt_resolve_inputs* in, float* color_out,
+                           void* rgba8_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = resolve_args_error(W, H, in, color_out, rgba8_out, true, &st))
+    return fail(c, st, std::string("rt_shade_resolve: ") + why);
+  if (!c->have_camera) return fail(c, RT_E_INVALID, "rt_shade_resolve: camera not set");
+  if (!c->have_shading) return fail(c, RT_E_INVALID, "rt_shade_resolve: shading not set");
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_shade_resolve(
+      resolve_of(W, H, c->cam_cb, c->fp.lights, c->fp.nlights, in, color_out, rgba8_out), pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "resolve launch");
   return RT_OK;
 }
 
@@ -2698,6 +2801,45 @@ rt_status rt_host_ao_rays(const float* cam_rays, const float* t, const float* no
   return RT_OK;
 }
 
+// Host service: the rays rt_dispatch_shadow traces for n pixels, from the functions of rt_device.hpp the shadow kernels
+// call (shading_normal, shadow_lit, shadow_base, shadow_direction), in the kernels' order of operations. Here for
+// rt_host_shading_normals' reason. No context, no GPU call.
+rt_status rt_host_shadow_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* hit_group,
+                              const uint32_t* px, const uint32_t* py, uint32_t n, const rt_light* lights,
+                              uint32_t nlights, const rt_shadow_params* params, float* rays_out, uint8_t* lit_out) {
+  if (shadow_params_error(params) || !lights || nlights < 1 || nlights > (uint32_t)rt::kMaxLights ||
+      (n && (!cam_rays || !t || !normal || !hit_group || !px || !py || !rays_out)))
+    return RT_E_INVALID;
+  const uint32_t S = params->samples;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* cr = cam_rays + 8 * (size_t)i;
+    const float* nr = normal + 4 * (size_t)i;
+    const rt::V3 O = rt::v3(cr[0], cr[1], cr[2]), D = rt::v3(cr[4], cr[5], cr[6]);
+    const rt::V3 ns = rt::shading_normal(rt::v3(nr[0], nr[1], nr[2]), hit_group[i]);
+    const rt::V3 P = rt::add(O, rt::muls(D, t[i]));
+    for (uint32_t l = 0; l < nlights; ++l) {
+      float* out = rays_out + 8 * ((size_t)i * nlights + l) * S;
+      const rt::V3 lp = rt::v3(lights[l].position[0], lights[l].position[1], lights[l].position[2]);
+      rt::V3 L;
+      float nl;
+      const bool lit = rt::shadow_lit(ns, lp, P, L, nl);
+      if (lit_out) lit_out[(size_t)i * nlights + l] = lit ? 1 : 0;
+      if (!lit) {
+        std::memset(out, 0, sizeof(float) * 8 * (size_t)S);
+        continue;
+      }
+      const uint32_t base = rt::shadow_base(px[i], py[i], params->seed, l);
+      for (uint32_t k = 0; k < S; ++k) {
+        const rt::V3 d = rt::shadow_direction(lp, params->light_radius, base, k, P);
+        float* r = out + 8 * (size_t)k;
+        r[0] = P.x, r[1] = P.y, r[2] = P.z, r[3] = params->tmin;
+        r[4] = d.x, r[5] = d.y, r[6] = d.z, r[7] = 100000.0f;
+      }
+    }
+  }
+  return RT_OK;
+}
+
 // Host services: the AO filter's three passes on host arrays, pixel by pixel through the functions of rt_device.hpp
 // the kernels of rt_denoise.hip call, after the device entry points' argument checks (less the 16-byte alignment).
 // Here for rt_host_shading_normals' reason. No context, no GPU call.
@@ -2794,6 +2936,22 @@ rt_status rt_host_upscale(uint32_t w, uint32_t h, uint32_t W, uint32_t H, const 
                                    color_out, hist_out, rgba8_out);
   for (uint32_t Y = 0; Y < H; ++Y)
     for (uint32_t X = 0; X < W; ++X) rt::upscale_pixel(u, X, Y, HostColorTap{color_cur, motion_cur, w});
+  return RT_OK;
+}
+
+// Host service: rt_shade_resolve on host arrays through resolve_pixel, the function k_shade_resolve calls, after the
+// device entry point's argument checks (less the 16-byte alignment); the camera's origin and inverses come from cb as
+// rt_set_camera's do (frame_cam). Here for rt_host_shading_normals' reason. No context, no GPU call.
+rt_status rt_host_shade_resolve(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights, uint32_t nlights,
+                                const rt_resolve_inputs* in, float* color_out, void* rgba8_out) {
+  rt_status st = RT_OK;
+  if (resolve_args_error(W, H, in, color_out, rgba8_out, false, &st)) return st;
+  if (!cb || !lights || nlights < 1 || nlights > (uint32_t)rt::kMaxLights) return RT_E_INVALID;
+  static_assert(sizeof(rt_light) == sizeof(rt::LightRec), "rt_light is LightRec's layout (rt_set_shading copies it)");
+  const rt::Resolve r =
+      resolve_of(W, H, cb, reinterpret_cast<const rt::LightRec*>(lights), nlights, in, color_out, rgba8_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::resolve_pixel(r, x, y);
   return RT_OK;
 }
 

@@ -14,9 +14,13 @@
 //                       and the values a [12][36] array of floats: a half-wave reads 32 consecutive entries of one row
 //                       (512 contiguous bytes by ds_read_b128, every 16-lane group of which covers the 64 banks once;
 //                       128 contiguous bytes by ds_read_b32), whatever the tap offset, so no read conflicts.
+//   k_shade_resolve     the deferred resolve (rt_shade_resolve), one pixel per lane: G-buffer planes,
+//                       the per-light visibility planes and the AO plane -> the colour frame (one 16-byte store, and
+//                       4 bytes of RGBA8 when asked for). The lights and the camera ride in the kernel argument.
 //
-// The arithmetic of all four is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel), which the
-// host twins in rt_api.cpp call too: the kernels differ from them in where a value is read, never in how it is used.
+// The arithmetic of all five is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
+// resolve_pixel), which the host twins in rt_api.cpp call too: the kernels differ from them in where a value is read,
+// never in how it is used.
 // Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
 #include "rt_internal.hpp"
 
@@ -130,6 +134,13 @@ __global__ __launch_bounds__(256) void k_ao_atrous_lds(uint32_t W, uint32_t H, u
   out[i] = atrous_pixel(g, s, depth_tol, normal_cos, LdsTap{sg, sv, at});
 }
 
+// One-dimensional over the pixels (W * H < 2^31, rt_api.cpp): a wave's 64 pixels are consecutive in every plane.
+__global__ __launch_bounds__(256) void k_shade_resolve(Resolve r) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= r.W * r.H) return;
+  resolve_pixel(r, i % r.W, i / r.W);
+}
+
 uint32_t tiles(uint32_t n, uint32_t t) { return (n + t - 1u) / t; }
 
 }  // namespace
@@ -145,6 +156,11 @@ hipError_t launch_denoise_guide(uint32_t n, const float* normal, const float* de
 hipError_t launch_ao_accumulate(const AoTemporal& a, hipStream_t stream) {
   const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
   hipLaunchKernelGGL(k_ao_accumulate, dim3(tx * ty), dim3(256), 0, stream, a, tx);
+  return hipGetLastError();
+}
+
+hipError_t launch_shade_resolve(const Resolve& r, hipStream_t stream) {
+  hipLaunchKernelGGL(k_shade_resolve, dim3(tiles(r.W * r.H, 256u)), dim3(256), 0, stream, r);
   return hipGetLastError();
 }
 

@@ -900,6 +900,66 @@ RT_HD V3 ao_direction(V3 nf, V3 sph) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Soft shadows (rt_dispatch_shadow, rt_shade_resolve): the rays of the visibility pass, called by the
+// shadow kernels per lane and by rt_host_shadow_rays per pixel, and the resolve's per-pixel function, called by
+// k_shade_resolve per lane and by rt_host_shade_resolve per pixel. The AO section's arithmetic rule holds, so the
+// device and the host agree to the bit; tests/shadow_reference.py restates both in numpy.
+// ------------------------------------------------------------------------------------------
+
+// rt_dispatch_shadow: the G-buffer launch's camera and frame size (gb's planes stay null), the context's lights (as in
+// FrameParams), rt_shadow_params' four values as checked by the entry point, and the output planes: plane l starts
+// l * plane_stride floats into vis, entry orow * width + x of a plane as for a G-buffer plane.
+struct ShadowParams {
+  GbufParams gb;
+  LightRec lights[kMaxLights];
+  uint32_t nlights;
+  uint32_t samples, seed;
+  float light_radius, tmin;
+  float* vis;
+  uint64_t plane_stride;
+};
+
+// RayGen's camera ray of pixel (px, py) through its centre: rt_trace.hip's gbuffer_ray (shade_sample_packet's
+// expressions, in its order) for the callers outside that file, the host among them.
+RT_HD void pixel_ray(const FrameCam& cam, float fwidth, float fheight, uint32_t px, uint32_t py, V3& O, V3& D) {
+  const float dx = (((float)px + 0.5f) / fwidth) * 2.0f - 1.0f;
+  const float dy = (((float)py + 0.5f) / fheight) * 2.0f - 1.0f;
+  float dc[4], dw[4];
+  const float ndc[4] = {dx, -dy, 1.0f, 1.0f};
+  hlsl_mul4(cam.proj_inv, ndc, dc);
+  const float dcam[4] = {dc[0], dc[1], dc[2], 0.0f};
+  hlsl_mul4(cam.view_inv, dcam, dw);
+  O = v3(cam.origin[0], cam.origin[1], cam.origin[2]);
+  D = normalize(v3(dw[0], dw[1], dw[2]));
+}
+
+// The normal the Lambert kernels shade with, from the G-buffer's normal plane: the plane group's as stored, the model
+// group's negated (the plane holds CalculateInterpolatedWorldNormal un-negated; a negation is exact).
+RT_HD V3 shading_normal(V3 n, uint32_t hit_group) { return hit_group == 2u ? n : neg(n); }
+
+// The frame kernels' light test at the hit point P with shading normal ns: L = normalize(lp - P), nl = dot(ns, L), lit
+// where nl > 0 (false for a NaN normal). Their expressions, in their order.
+RT_HD bool shadow_lit(V3 ns, V3 lp, V3 P, V3& L, float& nl) {
+  L = normalize(sub(lp, P));
+  nl = dot(ns, L);
+  return nl > 0.0f;
+}
+
+// The hash base of light l's samples at a pixel: the AO pass's base under a seed of the light's own.
+RT_HD uint32_t shadow_base(uint32_t px, uint32_t py, uint32_t seed, uint32_t l) {
+  return ao_base(px, py, seed ^ ao_hash(l + 1u));
+}
+
+// Direction of shadow ray k from P towards the spherical light (centre lp, radius `radius`): the sample's target is lp
+// itself at radius 0 (no sample is generated), else lp + radius * ao_sphere(base, k). Normalised twice, as both frame
+// kernels normalise the already normalised L again (shadow_ray, sd[r] = normalize(L)): the radius-0 ray is theirs.
+RT_HD V3 shadow_direction(V3 lp, float radius, uint32_t base, uint32_t k, V3 P) {
+  V3 target = lp;
+  if (radius != 0.0f) target = add(lp, muls(ao_sphere(base, k), radius));
+  return normalize(normalize(sub(target, P)));
+}
+
+// ------------------------------------------------------------------------------------------
 // AO filter (rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous): the per-pixel arithmetic, called by
 // the kernels of rt_denoise.hip per lane and by the rt_host_* twins per pixel. The AO section's rule: float32, no
 // contraction, IEEE quotients, only + - * / sqrtf, floorf, fabsf and comparisons, sums in the written order, so the
@@ -1025,6 +1085,61 @@ RT_HD float atrous_pixel(const float g[4], uint32_t s, float depth_tol, float no
     }
   }
   return sa / sw;
+}
+
+// The resolve of the soft-shadow section above (rt_shade_resolve); here for ld4 / st4.
+// rt_shade_resolve's launch: the camera, the lights, the frame's size and the planes (vis, ao, rgba8_out may be null).
+struct Resolve {
+  FrameCam cam;
+  LightRec lights[kMaxLights];
+  uint32_t nlights;
+  uint32_t W, H;
+  float fwidth, fheight;
+  const uint32_t* hits;
+  const float* normal;
+  const uint32_t* object;
+  const float* vis;
+  uint64_t vis_stride;
+  const float* ao;
+  float* color_out;
+  uint32_t* rgba8_out;
+};
+
+// Pixel (x, y) of rt_shade_resolve: the miss colour, or the Lambert sum over the lights with each light's term scaled
+// by 0.3 a + 0.7 v (a: the AO plane's value, v: the light's visibility; 1 where the plane is null). With a = 1 the
+// factor is exactly 1.0f at v = 1 and exactly 0.3f at v = 0: the frame kernels' `occl ? 0.3f : 1.0f`.
+RT_HD void resolve_pixel(const Resolve& r, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * r.W + x;
+  float h[4];
+  ld4(reinterpret_cast<const float*>(r.hits) + 4 * i, h);  // bits only: (t, instance id, primitive, hit flag)
+  V3 col;
+  if (__builtin_bit_cast(uint32_t, h[3]) == 0u) {
+    const float ramp = (float)y / r.fheight;  // miss_color, Miss.hlsl:8
+    col = v3(0.0f, 0.2f, 0.7f - 0.3f * ramp);
+  } else {
+    V3 O, D;
+    pixel_ray(r.cam, r.fwidth, r.fheight, x, y, O, D);
+    const V3 P = add(O, muls(D, h[0]));
+    float nv[4];
+    ld4(r.normal + 4 * i, nv);
+    const V3 ns = shading_normal(v3(nv[0], nv[1], nv[2]), r.object[2 * i + 1]);
+    const float a = r.ao ? r.ao[i] : 1.0f;
+    float c = 0.0f;
+    for (uint32_t l = 0; l < r.nlights; ++l) {
+      const LightRec& Lr = r.lights[l];
+      V3 L;
+      float nl;
+      if (shadow_lit(ns, v3(Lr.position[0], Lr.position[1], Lr.position[2]), P, L, nl)) {
+        const float v = r.vis ? r.vis[(size_t)l * r.vis_stride + i] : 1.0f;
+        c = c + nl * ((0.3f * a) + (0.7f * v));
+      }
+    }
+    c = c / (float)r.nlights;
+    col = v3(c, c, c);
+  }
+  const float out[4] = {col.x, col.y, col.z, 1.0f};
+  st4(r.color_out + 4 * i, out);
+  if (r.rgba8_out) r.rgba8_out[i] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | (255u << 24);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -205,6 +205,16 @@ hipError_t launch_trace_gbuffer(const SceneView& scene, const P& params, const u
 hipError_t launch_trace_ao(const SceneView& scene, const AoParams& params, const uint32_t* d_rows,
                            unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
 
+// The visibility pass (rt_dispatch_shadow): launch_trace_ao's schedule rule and grids on the shadow kernels;
+// params.vis's planes are written, params.gb's planes are not read.
+hipError_t launch_trace_shadow(const SceneView& scene, const ShadowParams& params, const uint32_t* d_rows,
+                               unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
+
+// --- Deferred resolve (rt_denoise.hip) ----------------------------------------
+// One launch, one pixel per lane; no scene, no scratch. Its per-pixel arithmetic is rt_device.hpp's resolve_pixel,
+// shared with rt_host_shade_resolve.
+hipError_t launch_shade_resolve(const Resolve& r, hipStream_t stream);
+
 // --- AO filter (rt_denoise.hip) -----------------------------------------------
 // One launch each; no scene, no scratch. Their per-pixel arithmetic is rt_device.hpp's, shared with the host twins.
 hipError_t launch_denoise_guide(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,

@@ -2084,6 +2084,142 @@ __global__ __launch_bounds__(kBlock) void k_trace_ao(SceneView sc, AoParams ap, 
   if (STATS) flush_stats<false>(cnt, stats);
 }
 
+// ------------------------------------------------------------------------------------------
+// Visibility pass (rt_dispatch_shadow): the AO kernels' launch shapes, camera ray and primary walk, then
+// per light of the context S any-hit rays from the frame's hit point towards a spherical light (rt_device.hpp's
+// shadow_direction, shared with rt_host_shadow_rays) over [tmin, 1e5], the frame kernels' tmax, and one float per
+// pixel and light: the share of them that arrive. A light the pixel does not face (the frame kernels' nl > 0 test) is
+// 0 with no ray traced, a primary miss 1 in every plane. With radius 0 and S = 1 the rays are the
+// RT_SHADE_LAMBERT_SHADOW frame's shadow rays to the bit. No reference counterpart (PlaneClosestHit's single ray to
+// light 0, Hit.hlsl:207-241).
+// ------------------------------------------------------------------------------------------
+
+// The normal the Lambert kernels shade the hit with: shade_sample's expression.
+__device__ __forceinline__ V3 shadow_normal(const SceneView& sc, const HitRec& hit) {
+  const HitInstance ir = load_hit_instance(sc, hit.inst);
+  return ir.hit_group == 2u ? face_world_normal(ir, hit.prim) : neg(interpolated_world_normal(ir, hit.prim, hit.u, hit.v));
+}
+
+// The packet kernel's SGPR budget: the plain kernels' cap (8 waves per SIMD; the walks' and the light loop's uniform
+// state then spills 20 - 47 SGPRs to VGPR lanes, none to scratch), or with RT_SHADOW_PLAIN_SGPRS=0 the compiler's own
+// (102 SGPRs, no spills, 7 waves), measured 1.05 - 1.06 x slower on C2 at 1080p and 1.01 - 1.03 x on REF at 720p;
+// DESIGN §3.13 has the resource rows and the A/B of the two builds.
+#ifndef RT_SHADOW_PLAIN_SGPRS
+#define RT_SHADOW_PLAIN_SGPRS 1
+#endif
+#if RT_SHADOW_PLAIN_SGPRS
+#define RT_SHADOW_SGPR_ATTR RT_PLAIN_SGPR_ATTR
+#else
+#define RT_SHADOW_SGPR_ATTR
+#endif
+
+// Packet schedule: k_trace_ao_packet's layout and closest-hit walk, then a wave-uniform loop over the lights and inside
+// it a wave-uniform loop over the samples: every lit lane generates its ray k and the wave walks the 64 of them as one
+// any-hit packet; lanes that missed or do not face the light join every packet dead, and a light no lane of the wave
+// faces skips its sample loop. One 4-B store per lane per light: an 8-pixel tile row is 32 contiguous bytes.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_SHADOW_SGPR_ATTR
+void k_trace_shadow_packet(SceneView sc, ShadowParams sp, const uint32_t* __restrict__ rows,
+                           unsigned long long* __restrict__ stats) {
+  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
+  const GbufParams& gb = sp.gb;
+  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
+  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
+  const bool inimg = x < gb.width && orow < gb.nrows;
+  uint32_t py = 0;
+  if (inimg) py = rows ? rows[orow] : orow;
+  V3 O, D;
+  gbuffer_ray(gb, x, py, O, D);
+  Counters cnt;
+  if (STATS && inimg) ++cnt.primary;
+  HitRec hit;
+  bool found;
+  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  const bool live = inimg && found;
+  V3 ns = v3(0.0f, 0.0f, 0.0f), P = O;  // a dead lane faces no light
+  if (live) {
+    ns = shadow_normal(sc, hit);
+    P = add(O, muls(D, hit.t));  // GetWorldHitPoint, the frame's expression
+  }
+  float* out = sp.vis + (orow * gb.width + x);  // < 2^32 pixels (rt_api.cpp); dereferenced by in-image lanes only
+  for (uint32_t l = 0; l < sp.nlights; ++l) {
+    const LightRec& Lr = sp.lights[l];
+    const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+    V3 L;
+    float nl;
+    const bool need = shadow_lit(ns, lp, P, L, nl) && live;
+    uint32_t clear = 0;
+    if (wave_ballot(need)) {  // uniform
+      const uint32_t base = shadow_base(x, py, sp.seed, l);
+      for (uint32_t k = 0; k < sp.samples; ++k) {
+        V3 d = v3(0.0f, 0.0f, 1.0f);  // a dead lane's ray: finite, never traced
+        if (need) d = shadow_direction(lp, sp.light_radius, base, k, P);
+        if (STATS && need) ++cnt.shadow;
+        HitRec h;
+        bool occ;
+        trace_packet<true, STATS, 1, false, TT>(sc, &P, &d, sp.tmin, 100000.0f, &need, &occ, &h, cnt);
+        clear += need && !occ ? 1u : 0u;
+      }
+    }
+    if (inimg) out[(size_t)l * sp.plane_stride] = !found ? 1.0f : need ? (float)clear / (float)sp.samples : 0.0f;
+  }
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_ao's indexing, LDS stack and
+// per-launch HBM overflow; each lane loops over its own lights and samples.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_shadow(SceneView sc, ShadowParams sp, const uint32_t* __restrict__ rows,
+                                                         unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const GbufParams& gb = sp.gb;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  Counters cnt;
+  if (px < gb.width && orow < gb.nrows) {
+    const uint32_t py = rows ? rows[orow] : orow;
+    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+    V3 O, D;
+    gbuffer_ray(gb, px, py, O, D);
+    HitRec hit;
+    if (STATS) ++cnt.primary;
+    const bool found = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
+    V3 ns = v3(0.0f, 0.0f, 0.0f), P = O;
+    if (found) {
+      ns = shadow_normal(sc, hit);
+      P = add(O, muls(D, hit.t));
+    }
+    float* out = sp.vis + (orow * gb.width + px);
+    for (uint32_t l = 0; l < sp.nlights; ++l) {
+      const LightRec& Lr = sp.lights[l];
+      const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+      float vis = 1.0f;
+      if (found) {
+        V3 L;
+        float nl;
+        vis = 0.0f;
+        if (shadow_lit(ns, lp, P, L, nl)) {
+          const uint32_t base = shadow_base(px, py, sp.seed, l);
+          uint32_t clear = 0;
+          for (uint32_t k = 0; k < sp.samples; ++k) {
+            const V3 d = shadow_direction(lp, sp.light_radius, base, k, P);
+            if (STATS) ++cnt.shadow;
+            HitRec h;
+            clear += trace<true, STATS, false, TT>(sc, P, d, sp.tmin, 100000.0f, h, stk, cnt) ? 0u : 1u;
+          }
+          vis = (float)clear / (float)sp.samples;
+        }
+      }
+      out[(size_t)l * sp.plane_stride] = vis;
+    }
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
 // Un-interleaves the gathered strips (rank-major blocks; rank k holds strips s % nranks == k) into the RGBA8 frame.
 // in_bpp 3: the strips are RGB8 and the constant alpha 255 is restored here (RayGen.hlsl:42 writes float4(c, 1)).
 __global__ void k_assemble(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
@@ -2779,6 +2915,25 @@ hipError_t launch_trace_ao(const SceneView& sc, const AoParams& ap, const uint32
         else
           hipLaunchKernelGGL((k_trace_ao_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, ap, d_rows,
                              d_stats);
+      },
+      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
+  return hipGetLastError();
+}
+
+// The visibility pass: launch_trace_ao's schedule rule, grids and compile-time choices, on the shadow kernels.
+hipError_t launch_trace_shadow(const SceneView& sc, const ShadowParams& sp, const uint32_t* d_rows,
+                               unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
+  const bool packet = gbuffer_packet(sc, schedule);
+  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
+  const dim3 grid((sp.gb.width + tw - 1) / tw, (sp.gb.nrows + th - 1) / th);
+  lift(
+      [&](auto S, auto T) {
+        if (!packet)
+          hipLaunchKernelGGL((k_trace_shadow<S.value, T.value>), grid, dim3(kBlock),
+                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, sp, d_rows, d_stats);
+        else
+          hipLaunchKernelGGL((k_trace_shadow_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, sp,
+                             d_rows, d_stats);
       },
       Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
   return hipGetLastError();
