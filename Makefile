@@ -202,10 +202,21 @@ $(ASAN)/shadow_asan.o: tools/shadow_asan.cpp include/rt_api.h | $(ASAN)
 $(ASAN)/shadow_check: $(ASAN)/shadow_asan.o $(ASAN_API_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
+# the same for the reflection host twins (rt_host_reflection_rays, rt_host_reflection_radiance,
+# rt_host_reflection_composite: per-sample and per-light indexing on exact-size heap blocks):
+#   make asan-reflection && build/asan/reflection_check
+asan-reflection: $(ASAN)/reflection_check
+
+$(ASAN)/reflection_asan.o: tools/reflection_asan.cpp include/rt_api.h | $(ASAN)
+	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
+
+$(ASAN)/reflection_check: $(ASAN)/reflection_asan.o $(ASAN_API_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
+
 $(ASAN):
 	mkdir -p $@
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VDIR)
 
-.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow
+.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow asan-reflection

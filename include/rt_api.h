@@ -35,7 +35,9 @@ extern "C" {
  * rt_ao_atrous_params, and rt_tile_plan_probe with rt_tile_plan_args, and rt_upscale, rt_host_upscale,
  * rt_upscale_params, rt_camera_jitter and rt_jitter_halton, and rt_dispatch_rays_gbuffer, and rt_dispatch_shadow,
  * rt_shade_resolve, their host twins rt_host_shadow_rays and rt_host_shade_resolve, rt_shadow_params and
- * rt_resolve_inputs. */
+ * rt_resolve_inputs, and rt_dispatch_reflection, rt_reflection_composite, their host twins rt_host_reflection_rays,
+ * rt_host_reflection_radiance and rt_host_reflection_composite, rt_reflection_params, rt_reflection_planes and
+ * rt_reflection_composite_params. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -547,6 +549,63 @@ typedef struct { uint32_t samples; uint32_t seed; float light_radius; float tmin
 rt_status rt_dispatch_shadow(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
                              const rt_shadow_params* params, float* vis_dev, uint64_t plane_stride, void* hip_stream);
 
+/* Parameters of the reflection pass. samples: rays per pixel, 1..64; seed: any value (the same seed gives the same
+ * planes, bit for bit); roughness: finite, in [0, 1] (0: the mirror ray); tmax: the reflection rays' tmax, finite and
+ * > 0.001 (the frame kernels' CastReflectionRay uses 1000, and so does the Python binding's default); shadow_tmin: the
+ * tmin of the shadow rays at the reflected hits, finite and >= 0 (the frame kernels use 0.01). */
+typedef struct { uint32_t samples; uint32_t seed; float roughness; float tmax; float shadow_tmin; } rt_reflection_params;
+
+/* Outputs of the reflection pass (device memory, each nrows * W entries of 4 words in rt_dispatch_rays' compact order,
+ * 16-byte aligned). radiance: required; hits: optional (NULL: not written). */
+typedef struct { float* radiance; uint32_t* hits; } rt_reflection_planes;
+
+/* The reflection pass: per pixel of the frame rt_dispatch_gbuffer describes, `samples` reflection rays
+ * about the mirror direction of the G-buffer's normal, each shaded as an RT_SHADE_LAMBERT_SHADOW sample is, reduced to
+ * one 16-byte entry: the mean colour and the mean reflection distance. One launch: the primary walk, ray generation,
+ * per sample one closest-hit walk and the shadow walks of that hit, and the reduction.
+ * Everything rt_dispatch_shadow documents about W, H, rows, nrows, the camera ray, the schedule rule and its per-lane
+ * fall-back, rt_set_triangle_test (every ray of the pass follows it), streams, slot rings, the TLAS double buffer,
+ * rt_forget_stream and refit-before-rebuild holds here: the passes run the same host functions. It needs a camera, a
+ * current TLAS and the context's lights (rt_set_shading; its shade mode, spp and material are not read). It changes no
+ * other launch's results.
+ * The value, for pixel (px, py) (py the GLOBAL row rows[r]) with camera ray (O, D), primary hit (over [0, 1e5]) at
+ * distance t, and G-buffer normal N (rt_gbuffer.normal's xyz, bit for bit):
+ *   a primary miss, or N not valid (a non-finite component, dot(N, N) not finite or not > 0: rt_dispatch_ao's rule):
+ *     radiance = four zeros, hits = four zero words, no ray traced.
+ *   otherwise nn = normalize(N), P = O + D t, m = normalize(normalize(reflect(normalize(D), nn))) (the frame kernels'
+ *     reflection ray, HLSL's reflect(i, n) = i - (2 n) dot(i, n)), and per sample k = 0 .. samples - 1 the direction
+ *     roughness == 0: d_k = m (no sample is generated; the `samples` identical rays are all traced);
+ *     roughness > 0:  nf = rt_dispatch_ao's facing normal of nn (n' = normalize(nn); -n' where dot(n', D) > 0),
+ *                     base = hash(px + hash(py + hash(seed ^ hash(0x100)))), rt_dispatch_ao's hash and sphere point,
+ *                     v = m + roughness * sph(base, k) componentwise, d = dot(v, v) < 1e-4f ? m : normalize(v),
+ *                     d_k = dot(d, nf) > 0 ? d : m  (a sample below the horizon falls back to the mirror ray);
+ *   ray k = (origin P + d_k * 0.001f, tmin 0.001f, direction d_k, tmax), a closest-hit search with
+ *     RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES: the frame's CastReflectionRay. Sample k does not depend on `samples`.
+ *   its colour L_k and distance t_k:
+ *     a miss: L_k = (0, 0.2f, 0.7f - 0.3f * ((float)py / (float)H)), the frame's miss colour at the row; t_k = tmax;
+ *     a hit at t2 in an instance of hit group g2 with G-buffer-form normal N2: P2 = origin + d_k * t2,
+ *       n_s = g2 == RT_HITGROUP_PLANE ? N2 : -N2, c = 0; for l = 0 .. nlights - 1: L = normalize(lp_l - P2),
+ *       nl = dot(n_s, L); if nl > 0: c = c + nl * (occluded ? 0.3f : 1.0f), occluded = an any-hit search of the ray
+ *       (P2, shadow_tmin, normalize(normalize(lp_l - P2)), 100000) finds something (rt_dispatch_shadow's radius-0 ray);
+ *       c = c / (float)nlights; L_k = (c, c, c), t_k = t2  (RT_SHADE_LAMBERT_SHADOW's expression on the reflected ray);
+ *   radiance = ((sum of L_k) / (float)samples, (sum of t_k) / (float)samples), the sums from 0 with k ascending; .w,
+ *     the mean reflection distance, is what a reflection denoiser takes;
+ *   hits = ray 0's record exactly as rt_trace_rays writes it: (t, instance, primitive, 1), a miss (tmax, ~0, ~0, 0).
+ * float32, no contraction, IEEE quotients (rt_dispatch_ao's arithmetic): the device, rt_host_reflection_rays and
+ * rt_host_reflection_radiance agree to the bit.
+ * rt_set_stats: RT_STAT_PRIMARY_RAYS and RT_STAT_PIXELS grow by nrows * W, RT_STAT_DISPATCHES by 1,
+ * RT_STAT_REFLECTION_RAYS by (valid pixels) * samples, RT_STAT_SHADOW_RAYS by the lit (reflected hit, light) pairs; the
+ * traversal counters grow as the walks make them grow (not part of the contract).
+ * Errors: RT_E_INVALID with nothing written (rt_last_error says which) for NULL params or out, a NULL radiance, a plane
+ * not 16-byte aligned, samples outside 1..64, roughness not finite or outside [0, 1], tmax not finite or <= 0.001,
+ * shadow_tmin not finite or < 0, rt_set_shading never called ("shading not set"), and every RT_E_INVALID case of
+ * rt_dispatch_gbuffer; RT_E_UNSUPPORTED as rt_dispatch_gbuffer.
+ * Reference: ReflectRay / CastReflectionRay (Hit.hlsl:176-203, Common.hlsl:58-69), there a mirror chain inside the hit
+ * programs for InstanceID 0 and 1 only. */
+rt_status rt_dispatch_reflection(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                 const rt_reflection_params* params, const rt_reflection_planes* out,
+                                 void* hip_stream);
+
 /* ---- AO filter: what turns a few AO rays per pixel into a usable plane ----------------------------
  * Three passes over planes the caller owns (device memory): a guide plane from the G-buffer, a temporal accumulation
  * through rt_gbuffer_motion.motion, and an edge-aware a-trous blur. All three are asynchronous on hip_stream (NULL =
@@ -721,6 +780,34 @@ typedef struct {
  * No reference counterpart: the reference shades inside its hit programs. */
 rt_status rt_shade_resolve(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_resolve_inputs* in, float* color_out,
                            void* rgba8_out, void* hip_stream);
+
+/* The weights of rt_reflection_composite: both finite, in [0, 1]. strength: the share of the reflection at F = 1;
+ * f0: the Fresnel reflectance at normal incidence. */
+typedef struct { float strength; float f0; } rt_reflection_composite_params;
+
+/* The Fresnel composite: puts rt_dispatch_reflection's radiance plane onto a colour frame. One pointwise
+ * launch, asynchronous on hip_stream (NULL = the context's stream); it allocates nothing and needs the context's
+ * camera only. Whole row-major W x H frames (entry y W + x), device pointers: color_in, radiance, normal and color_out
+ * W*H x 4 floats, hits (the PRIMARY rt_gbuffer.hits) W*H x 4 words, all 16-byte aligned; rgba8_out: optional, W*H x 4
+ * bytes, 4-byte aligned, R8G8B8A8_UNORM as rt_dispatch_rays packs it, alpha 255.
+ * Pixel i = y W + x:
+ *   hits[4i+3] == 0 (a miss), or a normal that is not valid (rt_dispatch_reflection's rule): color_out = color_in, all
+ *     four floats.
+ *   otherwise (O, D) = the pixel's camera ray, nf = the facing normal of normalize(N) (rt_dispatch_reflection's),
+ *     x = clamp01(1 - max(dot(nf, -D), 0)), x5 = ((x x)(x x)) x, F = f0 + (1 - f0) * x5 (Schlick), k = strength * F;
+ *     per colour channel out = base + k * (refl - base), HLSL's lerp as the frame uses it (Hit.hlsl:202); alpha 1.0f.
+ * float32, no contraction, in the order written; rt_host_reflection_composite agrees to the bit. Two identities follow
+ * from the formulas: with strength == 0 and finite planes, k is 0 and color_out equals color_in bit for bit (for a
+ * frame whose alpha is 1.0f and that holds no negative zero, as rt_shade_resolve's and rt_upscale's do); with f0 == 1,
+ * F is 1 + 0 * x5 == 1 and k == strength exactly.
+ * color_out == color_in is allowed (a pixel reads its own entry only). Errors, nothing written, rt_last_error naming
+ * the cause: RT_E_INVALID for NULL params, a strength or f0 that is not finite or outside [0, 1], a NULL color_in,
+ * radiance, hits, normal or color_out, a misaligned plane, an output equal to any other plane but color_out ==
+ * color_in (pointer EQUALITY, rt_shade_resolve's rule), W or H of 0, no camera; RT_E_UNSUPPORTED for W * H >= 2^31.
+ * Reference: the lerp of ClosestHit (Hit.hlsl:194-203), there with the material's constant reflectivity. */
+rt_status rt_reflection_composite(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_reflection_composite_params* params,
+                                  const float* color_in, const float* radiance, const uint32_t* hits,
+                                  const float* normal, float* color_out, void* rgba8_out, void* hip_stream);
 
 /* Stream lifetime: the context notes (host-side, no event per launch) which streams launched with the current
  * TLAS version, and records one event on each of them when the next rt_tlas_build swaps that version out; the tile
@@ -1013,6 +1100,40 @@ rt_status rt_host_shadow_rays(const float* cam_rays, const float* t, const float
  * the 16-byte alignment (4 bytes will do), the same per-pixel function, so the same bits. */
 rt_status rt_host_shade_resolve(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights, uint32_t nlights,
                                 const rt_resolve_inputs* in, float* color_out, void* rgba8_out);
+
+/* The rays rt_dispatch_reflection traces for n pixels, on the host: the first half of the check of its planes (it
+ * calls the functions the reflection kernels call; trace the rays with rt_trace_rays' closest-hit search under
+ * RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES). cam_rays, t, normal, px, py as rt_host_ao_rays; params as
+ * rt_dispatch_reflection. rays_out: n x samples x 8 floats, pixel i's sample k at entry i * samples + k,
+ * (P + d * 0.001f, 0.001f, d, tmax); valid_out: n bytes or NULL, 1 where the normal is valid. An invalid pixel gets
+ * zero-filled rays. The caller leaves a primary miss out (its entries are zeros). All host memory. Null arrays with
+ * n > 0 or bad params: RT_E_INVALID, nothing written. */
+rt_status rt_host_reflection_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
+                                  const uint32_t* py, uint32_t n, const rt_reflection_params* params, float* rays_out,
+                                  uint8_t* valid_out);
+
+/* The radiance plane rt_dispatch_reflection writes for n pixels, on the host, from what the traced rays found: the
+ * second half of the check. rays: rt_host_reflection_rays' n x S x 8 floats (S = params->samples); hits: their
+ * n x S x 4-word records as rt_trace_rays writes them; hit_normal: n x S x 4 floats, the G-buffer-form normal of each
+ * hit (rt_host_shading_normals; not read for a miss); hit_group: n x S words, the hit instance's group (not read for a
+ * miss); occluded: n x S x nlights bytes, non-zero where the shadow ray of (reflected hit, light) found an occluder,
+ * read only where the hit faces the light; valid: n bytes (rt_host_reflection_rays' valid_out; 0: four zeros); py: n
+ * global rows; H: the frame's height; lights, nlights (1..16) as rt_set_shading. radiance_out: n x 4 floats; lit_out:
+ * n x S x nlights bytes or NULL, 1 where a shadow ray is traced (a reflected hit that faces the light). All host
+ * memory. Null arrays with n > 0, bad params, H of 0 or a bad light count: RT_E_INVALID, nothing written. */
+rt_status rt_host_reflection_radiance(const float* rays, const uint32_t* hits, const float* hit_normal,
+                                      const uint32_t* hit_group, const uint8_t* occluded, const uint8_t* valid,
+                                      const uint32_t* py, uint32_t n, uint32_t H, const rt_light* lights,
+                                      uint32_t nlights, const rt_reflection_params* params, float* radiance_out,
+                                      uint8_t* lit_out);
+
+/* rt_reflection_composite on host arrays: cb in place of the context's camera (rt_set_camera's layout; the origin and
+ * the inverses are derived from it as rt_set_camera's are), no stream; the same checks less the 16-byte alignment
+ * (4 bytes will do), the same per-pixel function, so the same bits. */
+rt_status rt_host_reflection_composite(uint32_t W, uint32_t H, const float cb[64],
+                                       const rt_reflection_composite_params* params, const float* color_in,
+                                       const float* radiance, const uint32_t* hits, const float* normal,
+                                       float* color_out, void* rgba8_out);
 
 /* Sub-pixel jitter through the camera buffer alone (no kernel knows about it). out = cb (rt_set_camera's layout) with
  * the projection and its inverse replaced so that, for a W x H frame and (jx, jy) in pixels, finite, |j| < 0.5:

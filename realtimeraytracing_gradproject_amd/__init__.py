@@ -103,6 +103,23 @@ class rt_resolve_inputs(ctypes.Structure):
                 ("vis", ctypes.c_void_p), ("vis_stride", ctypes.c_uint64), ("ao", ctypes.c_void_p)]
 
 
+class rt_reflection_params(ctypes.Structure):
+    """include/rt_api.h rt_reflection_params: samples (1..64), seed, roughness, tmax, shadow_tmin of
+    rt_dispatch_reflection."""
+    _fields_ = [("samples", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("roughness", ctypes.c_float),
+                ("tmax", ctypes.c_float), ("shadow_tmin", ctypes.c_float)]
+
+
+class rt_reflection_planes(ctypes.Structure):
+    """include/rt_api.h rt_reflection_planes: the planes rt_dispatch_reflection writes (hits may be None)."""
+    _fields_ = [("radiance", ctypes.c_void_p), ("hits", ctypes.c_void_p)]
+
+
+class rt_reflection_composite_params(ctypes.Structure):
+    """include/rt_api.h rt_reflection_composite_params: strength and f0 of rt_reflection_composite, both in [0, 1]."""
+    _fields_ = [("strength", ctypes.c_float), ("f0", ctypes.c_float)]
+
+
 class rt_ao_temporal_params(ctypes.Structure):
     """include/rt_api.h rt_ao_temporal_params: max_history (1..1024), depth_tol, normal_cos of rt_ao_accumulate."""
     _fields_ = [("max_history", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
@@ -177,6 +194,10 @@ SIGNATURES = [
     ("rt_dispatch_ao", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
     ("rt_dispatch_shadow", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_shadow_params), _P, ctypes.c_uint64, _P]),
     ("rt_shade_resolve", _I, [_P, _U32, _U32, ctypes.POINTER(rt_resolve_inputs), _P, _P, _P]),
+    ("rt_dispatch_reflection", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_reflection_params),
+                                    ctypes.POINTER(rt_reflection_planes), _P]),
+    ("rt_reflection_composite", _I, [_P, _U32, _U32, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P, _P,
+                                     _P, _P, _P]),
     ("rt_denoise_guide", _I, [_P, _U32, _P, _P, _U32, _P, _P]),
     ("rt_ao_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P,
                               _P]),
@@ -231,6 +252,11 @@ SIGNATURES = [
                                  ctypes.POINTER(rt_shadow_params), _P, _P]),
     ("rt_host_shade_resolve", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_light), _U32, ctypes.POINTER(rt_resolve_inputs),
                                    _P, _P]),
+    ("rt_host_reflection_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_reflection_params), _P, _P]),
+    ("rt_host_reflection_radiance", _I, [_P, _P, _P, _P, _P, _P, _P, _U32, _U32, ctypes.POINTER(rt_light), _U32,
+                                         ctypes.POINTER(rt_reflection_params), _P, _P]),
+    ("rt_host_reflection_composite", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P,
+                                          _P, _P, _P]),
     ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
     ("rt_host_ao_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rt_host_ao_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P]),
@@ -565,6 +591,92 @@ def host_shade_resolve(width: int, height: int, camera, lights, hits, normal, ob
     st = lib.rt_host_shade_resolve(width, height, _fptr(cb), arr, nl, ctypes.byref(inp), _vp(out), _vp(out8))
     if st != RT_OK:
         raise RtError(st, "rt_host_shade_resolve")
+    return (out, out8) if want_rgba8 else out
+
+
+def host_reflection_rays(cam_rays, t, normal, px, py, samples: int = 1, roughness: float = 0.0, tmax: float = 1000.0,
+                         shadow_tmin: float = 0.01, seed: int = 0):
+    """rt_host_reflection_rays: the rays rt_dispatch_reflection traces, on the host (no GPU). cam_rays: (n, 8) camera
+    rays in trace_rays' layout; t: n hit distances; normal: (n, 4) G-buffer normals; px, py: the pixels' global
+    coordinates. Returns (rays, valid): (n, samples, 8) float32 (P + 0.001 d, 0.001, d, tmax), to be traced closest-hit
+    with cull_back, and n uint8; an invalid normal has zero rays and valid 0. Primary misses are the caller's to leave
+    out."""
+    cr = np.ascontiguousarray(cam_rays, dtype=np.float32).reshape(-1, 8)
+    n = cr.shape[0]
+    tt = _f32(t, n)
+    nr = _f32(normal, 4 * n)
+    x = np.ascontiguousarray(px, dtype=np.uint32).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if x.size != n or y.size != n:
+        raise ValueError(f"expected {n} pixel coordinates, got {x.size} and {y.size}")
+    if not 1 <= int(samples) <= 64:  # rt_host_reflection_rays' own limit, checked before the output is sized by it
+        raise RtError(RT_E_INVALID, f"rt_host_reflection_rays: samples {samples} outside 1..64")
+    p = rt_reflection_params(samples, seed, roughness, tmax, shadow_tmin)
+    rays = np.zeros((n, int(samples), 8), np.float32)
+    valid = np.zeros(n, np.uint8)
+    st = lib.rt_host_reflection_rays(_vp(cr), _vp(tt), _vp(nr), _vp(x), _vp(y), n, ctypes.byref(p), _vp(rays),
+                                     _vp(valid))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_reflection_rays")
+    return rays, valid
+
+
+def host_reflection_radiance(rays, hits, hit_normal, hit_group, occluded, valid, py, height: int, lights,
+                             roughness: float = 0.0, tmax: float = 1000.0, shadow_tmin: float = 0.01, seed: int = 0,
+                             want_lit: bool = False):
+    """rt_host_reflection_radiance: rt_dispatch_reflection's radiance plane from what its rays found, on the host (no
+    GPU). rays: (n, S, 8) from host_reflection_rays; hits: (n, S, 4) uint32 records of their closest-hit trace;
+    hit_normal: (n, S, 4) G-buffer-form normals of those hits; hit_group: (n, S) hit groups; occluded: (n, S, nlights)
+    bytes, non-zero where the shadow ray of (hit, light) is occluded (read only where the hit faces the light); valid: n
+    bytes; py: n global rows; height: the frame's; lights: set_shading's triples. Returns (n, 4) float32 (mean colour,
+    mean distance) and, with want_lit, the (n, S, nlights) uint8 mask of the shadow rays traced."""
+    ry = np.ascontiguousarray(rays, dtype=np.float32)
+    if ry.ndim != 3 or ry.shape[2] != 8:
+        raise ValueError(f"rays must be (n, samples, 8), got {ry.shape}")
+    n, S = ry.shape[0], ry.shape[1]
+    arr = _lights_array(lights)
+    nl = len(arr)
+    if not 1 <= S <= 64:
+        raise RtError(RT_E_INVALID, f"rt_host_reflection_radiance: samples {S} outside 1..64")
+    if not 1 <= nl <= 16:
+        raise RtError(RT_E_INVALID, f"rt_host_reflection_radiance: {nl} lights, outside 1..16")
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    hn = _f32(hit_normal, 4 * n * S)
+    hg = np.ascontiguousarray(hit_group, dtype=np.uint32).ravel()
+    oc = np.ascontiguousarray(occluded, dtype=np.uint8).ravel()
+    va = np.ascontiguousarray(valid, dtype=np.uint8).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if hh.size != 4 * n * S or hg.size != n * S or oc.size != n * S * nl or va.size != n or y.size != n:
+        raise ValueError(f"expected {n} x {S} records and hit groups, {n * S * nl} occlusion bytes and {n} valid bytes "
+                         f"and rows, got {hh.size // 4}, {hg.size}, {oc.size}, {va.size} and {y.size}")
+    p = rt_reflection_params(S, seed, roughness, tmax, shadow_tmin)
+    out = np.zeros((n, 4), np.float32)
+    lit = np.zeros((n, S, nl), np.uint8) if want_lit else None
+    st = lib.rt_host_reflection_radiance(_vp(ry), _vp(hh), _vp(hn), _vp(hg), _vp(oc), _vp(va), _vp(y), n, height, arr,
+                                         nl, ctypes.byref(p), _vp(out), _vp(lit))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_reflection_radiance")
+    return (out, lit) if want_lit else out
+
+
+def host_reflection_composite(width: int, height: int, camera, color_in, radiance, hits, normal,
+                              strength: float = 1.0, f0: float = 0.04, want_rgba8: bool = False):
+    """rt_host_reflection_composite: the Fresnel composite on the host (no GPU). camera: the 64-float camera buffer;
+    color_in, radiance, normal: (n, 4) float32 and hits (n, 4) uint32 (the primary G-buffer's) with n = width * height.
+    Returns color (n, 4) float32 and, with want_rgba8, the (n, 4) uint8 frame as a second."""
+    n = width * height
+    cb = _f32(camera, 64)
+    ci, rd, nn = _f32(color_in, 4 * n), _f32(radiance, 4 * n), _f32(normal, 4 * n)
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    if hh.size != 4 * n:
+        raise ValueError(f"expected {4 * n} hit words, got {hh.size}")
+    p = rt_reflection_composite_params(strength, f0)
+    out = np.zeros((n, 4), np.float32)
+    out8 = np.zeros((n, 4), np.uint8) if want_rgba8 else None
+    st = lib.rt_host_reflection_composite(width, height, _fptr(cb), ctypes.byref(p), _vp(ci), _vp(rd), _vp(hh), _vp(nn),
+                                          _vp(out), _vp(out8))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_reflection_composite")
     return (out, out8) if want_rgba8 else out
 
 
@@ -1311,6 +1423,39 @@ class Context:
         self._check(self._lib.rt_shade_resolve(self._h, width, height, ctypes.byref(inp),
                                                self._plane(m, "color_out", color_out, 4 * n),
                                                self._plane(m, "rgba8_out", out8, n), stream), "rt_shade_resolve")
+
+    def dispatch_reflection(self, width: int, height: int, radiance, samples: int = 1, roughness: float = 0.0,
+                            tmax: float = 1000.0, shadow_tmin: float = 0.01, seed: int = 0, hits=None,
+                            rows: Optional[np.ndarray] = None, stream: Optional[int] = None):
+        """rt_dispatch_reflection: the reflections of the frame dispatch_gbuffer describes, 4 floats per pixel (nrows *
+        width entries in dispatch()'s compact row order): the mean colour of `samples` (1..64) reflection rays about
+        the mirror direction of the G-buffer's normal (roughness in [0, 1]; 0: the mirror ray itself), each shaded as a
+        Lambert-shadow sample under set_shading's lights or with the miss colour, and in .w their mean distance; four
+        zeros on a primary miss. hits: optional, ray 0's record per pixel as trace_rays writes it (4 words). Device
+        tensors (or raw addresses). host_reflection_rays and host_reflection_radiance give the rays and the plane."""
+        rp, nr, _keep = self._rows_arg(rows, height)
+        g = rt_reflection_planes()
+        self._set_planes(g, "dispatch_reflection", nr * width, (("radiance", radiance, 4), ("hits", hits, 4)))
+        p = rt_reflection_params(samples, seed, roughness, tmax, shadow_tmin)
+        self._check(self._lib.rt_dispatch_reflection(self._h, width, height, rp, nr, ctypes.byref(p), ctypes.byref(g),
+                                                     stream), "rt_dispatch_reflection")
+
+    def reflection_composite(self, width: int, height: int, color_in, radiance, hits, normal, color_out,
+                             strength: float = 1.0, f0: float = 0.04, rgba8_out=None, stream: Optional[int] = None):
+        """rt_reflection_composite: color_out = lerp(color_in, radiance, strength * F) per pixel, F Schlick's Fresnel
+        term (f0 at normal incidence) at the G-buffer's normal under the context's camera; color_in where the primary
+        ray missed. Whole frames: color_in, radiance, normal, color_out width * height x 4 floats, hits the primary
+        dispatch_gbuffer hits plane; color_out may be color_in; rgba8_out: optional width * height x 4 bytes. strength
+        0 returns color_in bit for bit; f0 1 weights every pixel by strength exactly."""
+        n, m = width * height, "reflection_composite"
+        out8 = rgba8_out.view(torch.int32) if isinstance(rgba8_out, torch.Tensor) and rgba8_out.dtype == torch.uint8 \
+            else rgba8_out
+        p = rt_reflection_composite_params(strength, f0)
+        self._check(self._lib.rt_reflection_composite(
+            self._h, width, height, ctypes.byref(p), self._plane(m, "color_in", color_in, 4 * n),
+            self._plane(m, "radiance", radiance, 4 * n), self._plane(m, "hits", hits, 4 * n),
+            self._plane(m, "normal", normal, 4 * n), self._plane(m, "color_out", color_out, 4 * n),
+            self._plane(m, "rgba8_out", out8, n), stream), "rt_reflection_composite")
 
     @staticmethod
     def _plane(method: str, name: str, t, words: int):

@@ -2233,6 +2233,47 @@ rt_status rt_dispatch_shadow(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t*
                           });
 }
 
+// What is wrong with an rt_reflection_params, or null (rt_dispatch_reflection and its host twins check alike).
+static const char* reflection_params_error(const rt_reflection_params* p) {
+  if (!p) return "null params";
+  if (p->samples < 1 || p->samples > 64) return "samples outside 1..64";
+  if (!std::isfinite(p->roughness) || !(p->roughness >= 0.0f && p->roughness <= 1.0f))
+    return "roughness not finite and in [0, 1]";
+  if (!std::isfinite(p->tmax) || !(p->tmax > 0.001f)) return "tmax not finite and > 0.001";
+  if (!std::isfinite(p->shadow_tmin) || !(p->shadow_tmin >= 0.0f)) return "shadow_tmin not finite and >= 0";
+  return nullptr;
+}
+
+// The G-buffer passes' shared checks and launch sequence (grid_pass_check, grid_pass_launch) around the reflection
+// kernels.
+rt_status rt_dispatch_reflection(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                 const rt_reflection_params* params, const rt_reflection_planes* out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  const std::string fn = "rt_dispatch_reflection";
+  if (const char* why = reflection_params_error(params)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (!out) return fail(c, RT_E_INVALID, fn + ": null output planes");
+  if (!out->radiance) return fail(c, RT_E_INVALID, fn + ": null radiance plane");
+  if ((uintptr_t)out->radiance % 16u) return fail(c, RT_E_INVALID, fn + ": radiance plane not aligned to 16 bytes");
+  if ((uintptr_t)out->hits % 16u) return fail(c, RT_E_INVALID, fn + ": hits plane not aligned to 16 bytes");
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  if (st != RT_OK) return st;
+  if (!c->have_shading) return fail(c, RT_E_INVALID, fn + ": shading not set");
+  rt::ReflectionParams rp = {};
+  std::memcpy(rp.lights, c->fp.lights, sizeof(rp.lights));
+  rp.nlights = c->fp.nlights;
+  rp.samples = params->samples;
+  rp.seed = params->seed;
+  rp.roughness = params->roughness;
+  rp.tmax = params->tmax;
+  rp.shadow_tmin = params->shadow_tmin;
+  rp.radiance = out->radiance;
+  rp.hits = out->hits;
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, rp.gb, "reflection launch",
+                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
+                            return rt::launch_trace_reflection(sv, rp, d_rows, c->d_stats, c->stats_on, c->schedule, s);
+                          });
+}
+
 // ---- AO filter: the argument checks, shared by the device entry points and their host twins (align:
 // the device forms' 16-byte rule for 4-float planes; the host twins pass false) ---------------------------------
 namespace {
@@ -2537,6 +2578,75 @@ rt_status rt_shade_resolve(rt_ctx_t c, uint32_t W, uint32_t H, const rt_resolve_
   const hipError_t e = rt::launch_shade_resolve(
       resolve_of(W, H, c->cam_cb, c->fp.lights, c->fp.nlights, in, color_out, rgba8_out), pick_stream(c, stream));
   if (e != hipSuccess) return hip_fail(c, e, "resolve launch");
+  return RT_OK;
+}
+
+// ---- Fresnel composite: the argument check shared by rt_reflection_composite and
+// rt_host_reflection_composite (align as above) -------------------------------------------------------------------
+namespace {
+
+const char* composite_args_error(uint32_t W, uint32_t H, const rt_reflection_composite_params* p, const float* color_in,
+                                 const float* radiance, const uint32_t* hits, const float* normal,
+                                 const float* color_out, const void* rgba8_out, bool align, rt_status* st) {
+  *st = RT_E_INVALID;
+  if (W == 0 || H == 0) return "W or H is 0";
+  if ((uint64_t)W * H >= (1ull << 31)) {
+    *st = RT_E_UNSUPPORTED;
+    return "frame of 2^31 pixels or more";
+  }
+  if (!p) return "null params";
+  if (!std::isfinite(p->strength) || !(p->strength >= 0.0f && p->strength <= 1.0f))
+    return "strength not finite and in [0, 1]";
+  if (!std::isfinite(p->f0) || !(p->f0 >= 0.0f && p->f0 <= 1.0f)) return "f0 not finite and in [0, 1]";
+  if (!color_in) return "null color_in";
+  if (!radiance) return "null radiance plane";
+  if (!hits) return "null hits plane";
+  if (!normal) return "null normal plane";
+  if (!color_out) return "null color_out";
+  const size_t a4 = align ? 16 : 4;
+  if (misaligned(color_in, a4)) return "color_in misaligned";
+  if (misaligned(radiance, a4)) return "radiance plane misaligned";
+  if (misaligned(hits, a4)) return "hits plane misaligned";
+  if (misaligned(normal, a4)) return "normal plane misaligned";
+  if (misaligned(color_out, a4)) return "color_out misaligned";
+  if (misaligned(rgba8_out, 4)) return "rgba8_out not aligned to 4 bytes";
+  if (rgba8_out && rgba8_out == (const void*)color_out) return "rgba8_out is color_out";
+  if (color_out == radiance || (const void*)color_out == hits || color_out == normal)
+    return "an output is an input plane";
+  if (rgba8_out && (rgba8_out == color_in || rgba8_out == radiance || rgba8_out == hits || rgba8_out == normal))
+    return "an output is an input plane";
+  return nullptr;
+}
+
+rt::ReflComposite composite_of(uint32_t W, uint32_t H, const float cb[64], const rt_reflection_composite_params* p,
+                               const float* color_in, const float* radiance, const uint32_t* hits,
+                               const float* normal, float* color_out, void* rgba8_out) {
+  rt::ReflComposite r = {};
+  rt::frame_cam(cb, r.cam);
+  r.W = W, r.H = H;
+  r.fwidth = (float)W, r.fheight = (float)H;  // as resolve_of's
+  r.strength = p->strength, r.f0 = p->f0;
+  r.color_in = color_in, r.radiance = radiance, r.hits = hits, r.normal = normal;
+  r.color_out = color_out, r.rgba8_out = (uint32_t*)rgba8_out;
+  return r;
+}
+
+}  // namespace
+
+rt_status rt_reflection_composite(rt_ctx_t c, uint32_t W, uint32_t H, const rt_reflection_composite_params* params,
+                                  const float* color_in, const float* radiance, const uint32_t* hits,
+                                  const float* normal, float* color_out, void* rgba8_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why =
+          composite_args_error(W, H, params, color_in, radiance, hits, normal, color_out, rgba8_out, true, &st))
+    return fail(c, st, std::string("rt_reflection_composite: ") + why);
+  if (!c->have_camera) return fail(c, RT_E_INVALID, "rt_reflection_composite: camera not set");
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_reflection_composite(
+      composite_of(W, H, c->cam_cb, params, color_in, radiance, hits, normal, color_out, rgba8_out),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "reflection composite launch");
   return RT_OK;
 }
 
@@ -2952,6 +3062,113 @@ rt_status rt_host_shade_resolve(uint32_t W, uint32_t H, const float cb[64], cons
       resolve_of(W, H, cb, reinterpret_cast<const rt::LightRec*>(lights), nlights, in, color_out, rgba8_out);
   for (uint32_t y = 0; y < H; ++y)
     for (uint32_t x = 0; x < W; ++x) rt::resolve_pixel(r, x, y);
+  return RT_OK;
+}
+
+// Host service: the rays rt_dispatch_reflection traces for n pixels, from the functions of rt_device.hpp the reflection
+// kernels call (ao_normal_valid, reflection_mirror, ao_facing_normal, reflection_base, reflection_direction,
+// reflection_origin), in the kernels' order of operations. Here for rt_host_shading_normals' reason. No context, no
+// GPU call.
+rt_status rt_host_reflection_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
+                                  const uint32_t* py, uint32_t n, const rt_reflection_params* params, float* rays_out,
+                                  uint8_t* valid_out) {
+  if (reflection_params_error(params) || (n && (!cam_rays || !t || !normal || !px || !py || !rays_out)))
+    return RT_E_INVALID;
+  const uint32_t S = params->samples;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* cr = cam_rays + 8 * (size_t)i;
+    const float* nr = normal + 4 * (size_t)i;
+    float* out = rays_out + 8 * (size_t)i * S;
+    const rt::V3 O = rt::v3(cr[0], cr[1], cr[2]), D = rt::v3(cr[4], cr[5], cr[6]), nv = rt::v3(nr[0], nr[1], nr[2]);
+    const bool valid = rt::ao_normal_valid(nv);
+    if (valid_out) valid_out[i] = valid ? 1 : 0;
+    if (!valid) {
+      std::memset(out, 0, sizeof(float) * 8 * (size_t)S);
+      continue;
+    }
+    const rt::V3 nn = rt::normalize(nv);
+    const rt::V3 m = rt::reflection_mirror(D, nn);
+    const rt::V3 nf = rt::ao_facing_normal(nn, D);
+    const rt::V3 P = rt::add(O, rt::muls(D, t[i]));
+    const uint32_t base = rt::reflection_base(px[i], py[i], params->seed);
+    for (uint32_t k = 0; k < S; ++k) {
+      const rt::V3 d = rt::reflection_direction(m, nf, params->roughness, base, k);
+      const rt::V3 ro = rt::reflection_origin(P, d);
+      float* r = out + 8 * (size_t)k;
+      r[0] = ro.x, r[1] = ro.y, r[2] = ro.z, r[3] = 0.001f;
+      r[4] = d.x, r[5] = d.y, r[6] = d.z, r[7] = params->tmax;
+    }
+  }
+  return RT_OK;
+}
+
+// Host service: rt_dispatch_reflection's radiance plane for n pixels from the records, normals, hit groups and
+// occlusion of the traced rays, through the functions the reflection kernels call (reflection_miss_color,
+// shading_normal, shadow_lit, reflection_light_add, reflection_hit_color, reflection_sum_add, reflection_reduce), in the
+// kernels' order of operations. No context, no GPU call.
+rt_status rt_host_reflection_radiance(const float* rays, const uint32_t* hits, const float* hit_normal,
+                                      const uint32_t* hit_group, const uint8_t* occluded, const uint8_t* valid,
+                                      const uint32_t* py, uint32_t n, uint32_t H, const rt_light* lights,
+                                      uint32_t nlights, const rt_reflection_params* params, float* radiance_out,
+                                      uint8_t* lit_out) {
+  if (reflection_params_error(params) || !lights || nlights < 1 || nlights > (uint32_t)rt::kMaxLights || H == 0 ||
+      (n && (!rays || !hits || !hit_normal || !hit_group || !occluded || !valid || !py || !radiance_out)))
+    return RT_E_INVALID;
+  const uint32_t S = params->samples;
+  const float fheight = (float)H;
+  for (uint32_t i = 0; i < n; ++i) {
+    float* out = radiance_out + 4 * (size_t)i;
+    if (lit_out) std::memset(lit_out + (size_t)i * S * nlights, 0, (size_t)S * nlights);
+    if (!valid[i]) {
+      out[0] = out[1] = out[2] = out[3] = 0.0f;
+      continue;
+    }
+    const rt::V3 sky = rt::reflection_miss_color(py[i], fheight);
+    rt::ReflectionSum sum = rt::reflection_sum_zero();
+    for (uint32_t k = 0; k < S; ++k) {
+      const size_t j = (size_t)i * S + k;
+      if (hits[4 * j + 3] == 0u) {
+        rt::reflection_sum_add(sum, sky, params->tmax);
+        continue;
+      }
+      const float* r = rays + 8 * j;
+      float t2;
+      std::memcpy(&t2, hits + 4 * j, sizeof(t2));
+      const rt::V3 ro = rt::v3(r[0], r[1], r[2]), d = rt::v3(r[4], r[5], r[6]);
+      const rt::V3 n2 = rt::shading_normal(rt::v3(hit_normal[4 * j], hit_normal[4 * j + 1], hit_normal[4 * j + 2]),
+                                           hit_group[j]);
+      const rt::V3 P2 = rt::add(ro, rt::muls(d, t2));
+      float c = 0.0f;
+      for (uint32_t l = 0; l < nlights; ++l) {
+        rt::V3 L;
+        float nl;
+        if (rt::shadow_lit(n2, rt::v3(lights[l].position[0], lights[l].position[1], lights[l].position[2]), P2, L,
+                           nl)) {
+          if (lit_out) lit_out[j * nlights + l] = 1;
+          c = rt::reflection_light_add(c, nl, occluded[j * nlights + l] != 0);
+        }
+      }
+      c = rt::reflection_hit_color(c, nlights);
+      rt::reflection_sum_add(sum, rt::v3(c, c, c), t2);
+    }
+    rt::reflection_reduce(sum, S, out);
+  }
+  return RT_OK;
+}
+
+// Host service: rt_reflection_composite on host arrays through reflection_composite_pixel, the function
+// k_reflection_composite calls, after the device entry point's argument checks (less the 16-byte alignment); the camera
+// as in rt_host_shade_resolve. No context, no GPU call.
+rt_status rt_host_reflection_composite(uint32_t W, uint32_t H, const float cb[64],
+                                       const rt_reflection_composite_params* params, const float* color_in,
+                                       const float* radiance, const uint32_t* hits, const float* normal,
+                                       float* color_out, void* rgba8_out) {
+  rt_status st = RT_OK;
+  if (composite_args_error(W, H, params, color_in, radiance, hits, normal, color_out, rgba8_out, false, &st)) return st;
+  if (!cb) return RT_E_INVALID;
+  const rt::ReflComposite r = composite_of(W, H, cb, params, color_in, radiance, hits, normal, color_out, rgba8_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::reflection_composite_pixel(r, x, y);
   return RT_OK;
 }
 

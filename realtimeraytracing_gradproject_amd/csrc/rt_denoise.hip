@@ -17,9 +17,12 @@
 //   k_shade_resolve     the deferred resolve (rt_shade_resolve), one pixel per lane: G-buffer planes,
 //                       the per-light visibility planes and the AO plane -> the colour frame (one 16-byte store, and
 //                       4 bytes of RGBA8 when asked for). The lights and the camera ride in the kernel argument.
+//   k_reflection_composite  the Fresnel composite (rt_reflection_composite), one pixel per lane: the colour
+//                       frame, the reflection pass's radiance and the G-buffer's hits and normal planes -> the colour
+//                       frame (four 16-byte loads at most, one 16-byte store, 4 bytes of RGBA8 when asked for).
 //
-// The arithmetic of all five is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
-// resolve_pixel), which the host twins in rt_api.cpp call too: the kernels differ from them in where a value is read,
+// The arithmetic of all six is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
+// resolve_pixel, reflection_composite_pixel), which the host twins in rt_api.cpp call too: the kernels differ from them in where a value is read,
 // never in how it is used.
 // Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
 #include "rt_internal.hpp"
@@ -141,6 +144,13 @@ __global__ __launch_bounds__(256) void k_shade_resolve(Resolve r) {
   resolve_pixel(r, i % r.W, i / r.W);
 }
 
+// As k_shade_resolve: one-dimensional over the pixels. A pixel reads its own entries only, so color_out may be color_in.
+__global__ __launch_bounds__(256) void k_reflection_composite(ReflComposite r) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= r.W * r.H) return;
+  reflection_composite_pixel(r, i % r.W, i / r.W);
+}
+
 uint32_t tiles(uint32_t n, uint32_t t) { return (n + t - 1u) / t; }
 
 }  // namespace
@@ -161,6 +171,11 @@ hipError_t launch_ao_accumulate(const AoTemporal& a, hipStream_t stream) {
 
 hipError_t launch_shade_resolve(const Resolve& r, hipStream_t stream) {
   hipLaunchKernelGGL(k_shade_resolve, dim3(tiles(r.W * r.H, 256u)), dim3(256), 0, stream, r);
+  return hipGetLastError();
+}
+
+hipError_t launch_reflection_composite(const ReflComposite& r, hipStream_t stream) {
+  hipLaunchKernelGGL(k_reflection_composite, dim3(tiles(r.W * r.H, 256u)), dim3(256), 0, stream, r);
   return hipGetLastError();
 }
 

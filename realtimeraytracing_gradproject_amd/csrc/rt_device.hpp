@@ -960,6 +960,75 @@ RT_HD V3 shadow_direction(V3 lp, float radius, uint32_t base, uint32_t k, V3 P) 
 }
 
 // ------------------------------------------------------------------------------------------
+// Deferred reflections (rt_dispatch_reflection, rt_reflection_composite): the reflection pass's rays,
+// per-ray radiance and reduction, called by the reflection kernels per lane and by rt_host_reflection_rays /
+// rt_host_reflection_radiance per pixel (the composite's per-pixel function is below, with the resolve's). The AO
+// section's arithmetic rule holds; tests/reflection_reference.py restates all of it in numpy.
+// ------------------------------------------------------------------------------------------
+
+// rt_dispatch_reflection: the G-buffer launch's camera and frame size (gb's planes stay null), the context's lights,
+// rt_reflection_params' five values as checked by the entry point, and the output planes (4 words per pixel each,
+// entry orow * width + x as for a G-buffer plane; hits may be null).
+struct ReflectionParams {
+  GbufParams gb;
+  LightRec lights[kMaxLights];
+  uint32_t nlights;
+  uint32_t samples, seed;
+  float roughness, tmax, shadow_tmin;
+  float* radiance;
+  uint32_t* hits;
+};
+
+// The mirror direction of camera ray D about the unit normal nn: the frame kernels' reflection_ray expression
+// (ReflectRay + CastReflectionRay normalise three times) with the plain normalize.
+RT_HD V3 reflection_mirror(V3 D, V3 nn) { return normalize(normalize(reflect_dir(normalize(D), nn))); }
+
+// The hash base of a pixel's reflection samples: the AO pass's base under a seed of the pass's own.
+RT_HD uint32_t reflection_base(uint32_t px, uint32_t py, uint32_t seed) {
+  return ao_base(px, py, seed ^ ao_hash(0x100u));
+}
+
+// Direction of reflection ray k: the mirror direction m at roughness 0 (no sample is generated), else m perturbed by
+// roughness * ao_sphere(base, k) and renormalised (a vanishing sum falls back to m); a sample below the horizon of
+// the facing normal nf falls back to m as well.
+RT_HD V3 reflection_direction(V3 m, V3 nf, float roughness, uint32_t base, uint32_t k) {
+  if (roughness == 0.0f) return m;
+  const V3 v = add(m, muls(ao_sphere(base, k), roughness));
+  const V3 d = dot(v, v) < 1e-4f ? m : normalize(v);
+  return dot(d, nf) > 0.0f ? d : m;
+}
+
+// CastReflectionRay's offset origin (Common.hlsl:58-69): the ray starts 0.001 along its direction, tmin 0.001.
+RT_HD V3 reflection_origin(V3 P, V3 d) { return add(P, muls(d, 0.001f)); }
+
+// A reflection ray's colour where it hits nothing: the frame's miss colour at the pixel's row (Miss.hlsl:8).
+RT_HD V3 reflection_miss_color(uint32_t py, float fheight) {
+  const float ramp = (float)py / fheight;
+  return v3(0.0f, 0.2f, 0.7f - 0.3f * ramp);
+}
+
+// One lit light's term of a reflected hit's colour (shade_sample's RT_SHADE_LAMBERT_SHADOW expression), and the
+// division that ends the sum over the lights.
+RT_HD float reflection_light_add(float c, float nl, bool occluded) { return c + nl * (occluded ? 0.3f : 1.0f); }
+RT_HD float reflection_hit_color(float c, uint32_t nlights) { return c / (float)nlights; }
+
+// The running sums of a pixel's rays (colour and distance, from 0, k ascending) and their reduction to the plane's
+// entry: (mean colour, mean distance).
+struct ReflectionSum {
+  V3 L;
+  float t;
+};
+RT_HD ReflectionSum reflection_sum_zero() { return ReflectionSum{v3(0.0f, 0.0f, 0.0f), 0.0f}; }
+RT_HD void reflection_sum_add(ReflectionSum& s, V3 L, float t) {
+  s.L = add(s.L, L);
+  s.t = s.t + t;
+}
+RT_HD void reflection_reduce(const ReflectionSum& s, uint32_t samples, float out[4]) {
+  const float n = (float)samples;
+  out[0] = s.L.x / n, out[1] = s.L.y / n, out[2] = s.L.z / n, out[3] = s.t / n;
+}
+
+// ------------------------------------------------------------------------------------------
 // AO filter (rt_denoise_guide, rt_ao_accumulate, rt_ao_atrous): the per-pixel arithmetic, called by
 // the kernels of rt_denoise.hip per lane and by the rt_host_* twins per pixel. The AO section's rule: float32, no
 // contraction, IEEE quotients, only + - * / sqrtf, floorf, fabsf and comparisons, sums in the written order, so the
@@ -1140,6 +1209,50 @@ RT_HD void resolve_pixel(const Resolve& r, uint32_t x, uint32_t y) {
   const float out[4] = {col.x, col.y, col.z, 1.0f};
   st4(r.color_out + 4 * i, out);
   if (r.rgba8_out) r.rgba8_out[i] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | (255u << 24);
+}
+
+// The composite of the reflection section above (rt_reflection_composite); here for ld4 / st4.
+// Its launch: the camera, the frame's size, the two weights and the planes (rgba8_out may be null; color_out may be
+// color_in: a pixel reads its own entry of every plane before it writes).
+struct ReflComposite {
+  FrameCam cam;
+  uint32_t W, H;
+  float fwidth, fheight;
+  float strength, f0;
+  const float* color_in;
+  const float* radiance;
+  const uint32_t* hits;
+  const float* normal;
+  float* color_out;
+  uint32_t* rgba8_out;
+};
+
+// Pixel (x, y) of rt_reflection_composite: color_in where the primary ray missed or the normal cannot orient a
+// surface, else lerp(color_in, radiance, k) per channel (HLSL's x + s (y - x), Hit.hlsl:202) with k = strength * F and
+// F Schlick's Fresnel term at the facing normal: F = f0 + (1 - f0) x5, x = clamp01(1 - max(dot(nf, -D), 0)). With
+// strength 0, k is 0 and base + 0 * (refl - base) is base; with f0 1, F is 1 + 0 * x5 == 1 and k == strength.
+RT_HD void reflection_composite_pixel(const ReflComposite& r, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * r.W + x;
+  float out[4], nv[4];
+  ld4(r.color_in + 4 * i, out);
+  ld4(r.normal + 4 * i, nv);
+  const V3 N = v3(nv[0], nv[1], nv[2]);
+  if (r.hits[4 * i + 3] != 0u && ao_normal_valid(N)) {
+    float refl[4];
+    ld4(r.radiance + 4 * i, refl);
+    V3 O, D;
+    pixel_ray(r.cam, r.fwidth, r.fheight, x, y, O, D);
+    const V3 nf = ao_facing_normal(normalize(N), D);
+    const float f = clamp01(1.0f - maxf(dot(nf, neg(D)), 0.0f));
+    const float f2 = f * f;
+    const float f5 = (f2 * f2) * f;
+    const float F = r.f0 + (1.0f - r.f0) * f5;
+    const float k = r.strength * F;
+    for (int c = 0; c < 3; ++c) out[c] = out[c] + k * (refl[c] - out[c]);
+    out[3] = 1.0f;
+  }
+  st4(r.color_out + 4 * i, out);
+  if (r.rgba8_out) r.rgba8_out[i] = unorm8(out[0]) | (unorm8(out[1]) << 8) | (unorm8(out[2]) << 16) | (255u << 24);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -215,6 +215,15 @@ hipError_t launch_trace_shadow(const SceneView& scene, const ShadowParams& param
 // shared with rt_host_shade_resolve.
 hipError_t launch_shade_resolve(const Resolve& r, hipStream_t stream);
 
+// --- Deferred reflections (rt_trace.hip, rt_denoise.hip) -----------------------
+// The reflection pass (rt_dispatch_reflection): launch_trace_shadow's schedule rule and grids on the reflection
+// kernels; params.radiance (and params.hits, when given) are written, params.gb's planes are not read.
+hipError_t launch_trace_reflection(const SceneView& scene, const ReflectionParams& params, const uint32_t* d_rows,
+                                   unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
+// The composite (rt_reflection_composite): one launch, one pixel per lane; no scene, no scratch. Its per-pixel
+// arithmetic is rt_device.hpp's reflection_composite_pixel, shared with rt_host_reflection_composite.
+hipError_t launch_reflection_composite(const ReflComposite& r, hipStream_t stream);
+
 // --- AO filter (rt_denoise.hip) -----------------------------------------------
 // One launch each; no scene, no scratch. Their per-pixel arithmetic is rt_device.hpp's, shared with the host twins.
 hipError_t launch_denoise_guide(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,

@@ -2220,6 +2220,192 @@ __global__ __launch_bounds__(kBlock) void k_trace_shadow(SceneView sc, ShadowPar
   if (STATS) flush_stats<false>(cnt, stats);
 }
 
+// ------------------------------------------------------------------------------------------
+// Reflection pass (rt_dispatch_reflection): the shadow kernels' launch shapes, camera ray and primary
+// walk, then per pixel S closest-hit rays with back faces culled (the frame's CastReflectionRay) about the mirror
+// direction of the G-buffer's normal (rt_device.hpp's reflection_direction, shared with rt_host_reflection_rays), each
+// shaded as an RT_SHADE_LAMBERT_SHADOW sample is (one radius-0 shadow ray of the visibility pass per light the
+// reflected hit faces) or with the frame's miss colour, and one 16-byte entry per pixel: the mean colour and the mean
+// hit distance. A primary miss, or a hit whose normal cannot orient a surface, is four zeros with no ray traced.
+// The reference's counterpart is the mirror chain of InstanceID 0 and 1 (Hit.hlsl:176-203), inside its hit programs.
+// ------------------------------------------------------------------------------------------
+
+// rt_trace_rays' record of a reflection ray (k_trace_rays' expression).
+__device__ __forceinline__ uint4 reflection_record(bool f, const HitRec& h, float tmax) {
+  return make_uint4(__float_as_uint(f ? h.t : tmax), f ? h.inst : 0xffffffffu, f ? h.prim : 0xffffffffu, f ? 1u : 0u);
+}
+
+// The packet kernel's SGPR budget: the plain kernels' cap (the uniform state of the three walks and of the two loops
+// then spills 23 - 50 SGPRs to VGPR lanes, none to scratch), or with RT_REFLECT_PLAIN_SGPRS=0 the compiler's own (106
+// SGPRs, 0 - 13 spills). The kernel is bound by its 85 VGPRs either way (5 waves per SIMD capped, 6 uncapped), and the
+// two builds measure within each other's spread: the uncapped one 0.994 - 1.017 x the capped one's time on C2F at 1080p
+// and 1.001 - 1.008 x on REFLO at 720p; DESIGN §3.14 has the resource rows and the A/B of the two builds.
+#ifndef RT_REFLECT_PLAIN_SGPRS
+#define RT_REFLECT_PLAIN_SGPRS 1
+#endif
+#if RT_REFLECT_PLAIN_SGPRS
+#define RT_REFLECT_SGPR_ATTR RT_PLAIN_SGPR_ATTR
+#else
+#define RT_REFLECT_SGPR_ATTR
+#endif
+
+// Packet schedule: k_trace_shadow_packet's layout and closest-hit walk, then a wave-uniform loop over the samples:
+// every valid lane generates its ray k and the wave walks the 64 of them as one closest-hit packet with back faces
+// culled; then the shadow kernel's wave-uniform light loop on the reflected hits, one any-hit packet per light that
+// some lane's reflected hit faces. Lanes that missed, or whose normal is invalid, join every packet dead (a wave with
+// no valid lane skips the loop). One 16-B store per lane and plane: an 8-pixel tile row is a full 128-B line.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_REFLECT_SGPR_ATTR
+void k_trace_reflection_packet(SceneView sc, ReflectionParams rp, const uint32_t* __restrict__ rows,
+                               unsigned long long* __restrict__ stats) {
+  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
+  const GbufParams& gb = rp.gb;
+  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
+  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
+  const bool inimg = x < gb.width && orow < gb.nrows;
+  uint32_t py = 0;
+  if (inimg) py = rows ? rows[orow] : orow;
+  V3 O, D;
+  gbuffer_ray(gb, x, py, O, D);
+  Counters cnt;
+  if (STATS && inimg) ++cnt.primary;
+  HitRec hit;
+  bool found;
+  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  bool need = false;
+  V3 m = v3(0.0f, 0.0f, 1.0f), nf = m, P = O;  // a dead lane's ray: finite, never traced
+  if (inimg && found) {
+    const V3 n = ao_normal(sc, hit);
+    if (ao_normal_valid(n)) {
+      need = true;
+      const V3 nn = normalize(n);
+      m = reflection_mirror(D, nn);
+      nf = ao_facing_normal(nn, D);
+      P = add(O, muls(D, hit.t));  // GetWorldHitPoint, the frame's expression
+    }
+  }
+  const uint32_t base = reflection_base(x, py, rp.seed);
+  const uint32_t ns = wave_ballot(need) ? rp.samples : 0u;  // uniform
+  const V3 sky = reflection_miss_color(py, gb.fheight);
+  ReflectionSum sum = reflection_sum_zero();
+  uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t k = 0; k < ns; ++k) {
+    V3 d = reflection_direction(m, nf, rp.roughness, base, k);
+    V3 ro = reflection_origin(P, d);
+    if (STATS && need) ++cnt.refl;
+    HitRec h;
+    bool f;
+    trace_packet<false, STATS, 1, true, TT>(sc, &ro, &d, 0.001f, rp.tmax, &need, &f, &h, cnt);
+    const bool rh = need && f;
+    if (k == 0u && need) rec0 = reflection_record(f, h, rp.tmax);
+    V3 n2 = v3(0.0f, 0.0f, 0.0f), P2 = ro;  // a lane without a reflected hit faces no light
+    if (rh) {
+      n2 = shadow_normal(sc, h);
+      P2 = add(ro, muls(d, h.t));
+    }
+    float c = 0.0f;
+    for (uint32_t l = 0; l < rp.nlights; ++l) {
+      const LightRec& Lr = rp.lights[l];
+      const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+      V3 L;
+      float nl;
+      const bool lit = shadow_lit(n2, lp, P2, L, nl) && rh;
+      if (wave_ballot(lit)) {  // uniform
+        V3 sd = v3(0.0f, 0.0f, 1.0f);  // a dead lane's ray: finite, never traced
+        if (lit) sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+        if (STATS && lit) ++cnt.shadow;
+        HitRec hs;
+        bool occ;
+        trace_packet<true, STATS, 1, false, TT>(sc, &P2, &sd, rp.shadow_tmin, 100000.0f, &lit, &occ, &hs, cnt);
+        if (lit) c = reflection_light_add(c, nl, occ);
+      }
+    }
+    c = reflection_hit_color(c, rp.nlights);
+    if (need) reflection_sum_add(sum, rh ? v3(c, c, c) : sky, rh ? h.t : rp.tmax);
+  }
+  if (inimg) {
+    const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (need) reflection_reduce(sum, rp.samples, out);
+    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
+    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+  }
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_shadow's indexing, LDS stack and
+// per-launch HBM overflow; each lane loops over its own samples and, per reflected hit, over the lights.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_reflection(SceneView sc, ReflectionParams rp,
+                                                             const uint32_t* __restrict__ rows,
+                                                             unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const GbufParams& gb = rp.gb;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  Counters cnt;
+  if (px < gb.width && orow < gb.nrows) {
+    const uint32_t py = rows ? rows[orow] : orow;
+    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+    V3 O, D;
+    gbuffer_ray(gb, px, py, O, D);
+    HitRec hit;
+    if (STATS) ++cnt.primary;
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+    if (trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt)) {
+      const V3 n = ao_normal(sc, hit);
+      if (ao_normal_valid(n)) {
+        const V3 nn = normalize(n);
+        const V3 m = reflection_mirror(D, nn);
+        const V3 nf = ao_facing_normal(nn, D);
+        const V3 P = add(O, muls(D, hit.t));
+        const uint32_t base = reflection_base(px, py, rp.seed);
+        const V3 sky = reflection_miss_color(py, gb.fheight);
+        ReflectionSum sum = reflection_sum_zero();
+        for (uint32_t k = 0; k < rp.samples; ++k) {
+          const V3 d = reflection_direction(m, nf, rp.roughness, base, k);
+          const V3 ro = reflection_origin(P, d);
+          if (STATS) ++cnt.refl;
+          HitRec h;
+          const bool f = trace<false, STATS, true, TT>(sc, ro, d, 0.001f, rp.tmax, h, stk, cnt);
+          if (k == 0u) rec0 = reflection_record(f, h, rp.tmax);
+          if (!f) {
+            reflection_sum_add(sum, sky, rp.tmax);
+            continue;
+          }
+          const V3 n2 = shadow_normal(sc, h);
+          const V3 P2 = add(ro, muls(d, h.t));
+          float c = 0.0f;
+          for (uint32_t l = 0; l < rp.nlights; ++l) {
+            const LightRec& Lr = rp.lights[l];
+            const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+            V3 L;
+            float nl;
+            if (shadow_lit(n2, lp, P2, L, nl)) {
+              const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+              if (STATS) ++cnt.shadow;
+              HitRec hs;
+              c = reflection_light_add(c, nl, trace<true, STATS, false, TT>(sc, P2, sd, rp.shadow_tmin, 100000.0f, hs, stk, cnt));
+            }
+          }
+          c = reflection_hit_color(c, rp.nlights);
+          reflection_sum_add(sum, v3(c, c, c), h.t);
+        }
+        reflection_reduce(sum, rp.samples, out);
+      }
+    }
+    const uint32_t o = orow * gb.width + px;
+    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
+    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
 // Un-interleaves the gathered strips (rank-major blocks; rank k holds strips s % nranks == k) into the RGBA8 frame.
 // in_bpp 3: the strips are RGB8 and the constant alpha 255 is restored here (RayGen.hlsl:42 writes float4(c, 1)).
 __global__ void k_assemble(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
@@ -2933,6 +3119,25 @@ hipError_t launch_trace_shadow(const SceneView& sc, const ShadowParams& sp, cons
                              (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, sp, d_rows, d_stats);
         else
           hipLaunchKernelGGL((k_trace_shadow_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, sp,
+                             d_rows, d_stats);
+      },
+      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
+  return hipGetLastError();
+}
+
+// The reflection pass: launch_trace_shadow's schedule rule, grids and compile-time choices, on the reflection kernels.
+hipError_t launch_trace_reflection(const SceneView& sc, const ReflectionParams& rp, const uint32_t* d_rows,
+                                   unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
+  const bool packet = gbuffer_packet(sc, schedule);
+  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
+  const dim3 grid((rp.gb.width + tw - 1) / tw, (rp.gb.nrows + th - 1) / th);
+  lift(
+      [&](auto S, auto T) {
+        if (!packet)
+          hipLaunchKernelGGL((k_trace_reflection<S.value, T.value>), grid, dim3(kBlock),
+                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, rp, d_rows, d_stats);
+        else
+          hipLaunchKernelGGL((k_trace_reflection_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, rp,
                              d_rows, d_stats);
       },
       Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
