@@ -213,10 +213,21 @@ $(ASAN)/reflection_asan.o: tools/reflection_asan.cpp include/rt_api.h | $(ASAN)
 $(ASAN)/reflection_check: $(ASAN)/reflection_asan.o $(ASAN_API_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
+# the same for the PBR resolve's host twin (rt_host_shade_resolve_pbr: the material table and the instance map's
+# two range checks, every optional plane given and NULL, on exact-size heap blocks):
+#   make asan-materials && build/asan/materials_check
+asan-materials: $(ASAN)/materials_check
+
+$(ASAN)/materials_asan.o: tools/materials_asan.cpp include/rt_api.h | $(ASAN)
+	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
+
+$(ASAN)/materials_check: $(ASAN)/materials_asan.o $(ASAN_API_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
+
 $(ASAN):
 	mkdir -p $@
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VDIR)
 
-.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow asan-reflection
+.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials

@@ -37,7 +37,8 @@ extern "C" {
  * rt_shade_resolve, their host twins rt_host_shadow_rays and rt_host_shade_resolve, rt_shadow_params and
  * rt_resolve_inputs, and rt_dispatch_reflection, rt_reflection_composite, their host twins rt_host_reflection_rays,
  * rt_host_reflection_radiance and rt_host_reflection_composite, rt_reflection_params, rt_reflection_planes and
- * rt_reflection_composite_params. */
+ * rt_reflection_composite_params, and rt_shade_resolve_pbr, its host twin rt_host_shade_resolve_pbr, rt_material_table,
+ * rt_resolve_pbr_inputs and RT_MAX_MATERIALS. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -781,6 +782,66 @@ typedef struct {
 rt_status rt_shade_resolve(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_resolve_inputs* in, float* color_out,
                            void* rgba8_out, void* hip_stream);
 
+/* The material table of rt_shade_resolve_pbr (the reference's StructuredBuffer<Material> materials, t4, which
+ * CreateMaterialsBuffer sizes by materials.size() and UpdateMaterialsBuffer rewrites, D3D12HelloTriangle.cpp:1464-1479)
+ * and the map from an instance to its entry. The table belongs to the caller and is passed per call: the materials are
+ * copied during the call and travel by value with the launch, so an edit needs no upload and no wait; the map is a
+ * device plane like every other plane of the deferred route, ordered on the stream. The map's key is object[2i], the
+ * instance's INDEX in the rt_tlas_build list, not its instance_id. Material values are not validated (rt_set_shading
+ * does not validate its own either). */
+#define RT_MAX_MATERIALS 32
+typedef struct {
+  const rt_material* materials;         /* HOST array, copied during the call; nmaterials in 1..RT_MAX_MATERIALS */
+  uint32_t           nmaterials;
+  const uint32_t*    instance_material; /* DEVICE array of ninstances words, 4-byte aligned, or NULL: material 0
+                                           everywhere */
+  uint32_t           ninstances;        /* ignored when instance_material is NULL */
+} rt_material_table;
+
+/* Inputs of rt_shade_resolve_pbr: rt_resolve_inputs' six fields, exactly, and one more. */
+typedef struct {
+  const uint32_t* hits;   /* W*H x 4, rt_gbuffer.hits */
+  const float*    normal; /* W*H x 4, rt_gbuffer.normal */
+  const uint32_t* object; /* W*H x 2, rt_gbuffer.object */
+  const float*    vis;    /* nlights planes of W*H floats, or NULL: every light fully visible */
+  uint64_t        vis_stride; /* floats between planes; 0 = W*H */
+  const float*    ao;     /* W*H floats, or NULL: 1 */
+  const float*    refl;   /* W*H x 4 floats, rt_reflection_planes.radiance, 16-byte aligned, or NULL */
+} rt_resolve_pbr_inputs;
+
+/* The PBR resolve: rt_shade_resolve's contract (one pointwise launch, asynchronous on hip_stream, NULL
+ * = the context's stream; it allocates nothing, never waits and notes nothing in the context; it needs the context's
+ * camera and lights, rt_set_shading's mode, spp and material are NOT read; no TLAS; whole row-major frames) with the
+ * reference's hit programs in place of the grey Lambert term, and a material per instance. color_out, rgba8_out as
+ * rt_shade_resolve's.
+ * Pixel i = y W + x, (O, D) its camera ray, t = hits[4i] as float, P = O + D t, N = normal[4i..4i+2],
+ * a = ao ? ao[i] : 1, v_l = vis ? vis[l * stride + i] : 1, s_l = (0.3f * a) + (0.7f * v_l) (rt_shade_resolve's factor:
+ * exactly 1.0f without planes, exactly 0.3f at a = 1, v = 0):
+ *   hits[4i+3] == 0 (a miss): the frame's miss colour, as rt_shade_resolve.
+ *   object[2i+1] == RT_HITGROUP_PLANE: PlaneClosestHit (Hit.hlsl:207-241) as RT_SHADE_REF evaluates it:
+ *     ldir = normalize(lp_0 - P), li = max(0, dot(N, ldir)), c = (1.0f * li) * s_0, colour (c, c, c). Light 0 only and
+ *     no material: the reference's plane program reads none, so a coloured floor is a MODEL-group instance.
+ *   any other group: ClosestHit's surface colour (Hit.hlsl:83-174: the Lambert direct term plus the GGX / Smith /
+ *     Schlick term, tone-mapped) in RT_SHADE_REF's float32 sequence, operation for operation, with n = N, cam = O and
+ *     the material m of the pixel: m = instance_material ? (inst < ninstances ? instance_material[inst] : 0) : 0 with
+ *     inst = object[2i], then m = m < nmaterials ? m : 0 (no index reads outside either array). Per light the two
+ *     sums take the factor: cd += (albedo * lc) * (ti * s_l) and L0 += ((diff + spec) * radiance) * (NdotL * s_l).
+ *     Then, when refl is given, the material's reflectivity r != 0 and N is valid by rt_dispatch_reflection's rule:
+ *     colour = colour + r * (refl[4i..4i+2] - colour), HLSL's lerp as Hit.hlsl:203 uses it; at r == 1.0f the colour
+ *     is refl's rgb itself, bit for bit (the formula's x + (y - x) rounds to y only where y - x is exact). This
+ *     holds for ANY instance: the reference's "InstanceID 0 or 1" test is what a per-instance reflectivity replaces.
+ * The anchors: with one material, instance_material, ao and refl NULL and vis NULL, every miss and MODEL pixel equals
+ * rt_dispatch_rays' RT_SHADE_REF frame (that material, reflectivity 0, one sample) bit for bit, float and RGBA8; with
+ * vis from rt_dispatch_shadow at light_radius 0, samples 1, tmin 0.01, every PLANE pixel does. rt_host_shade_resolve_pbr
+ * agrees to the bit.
+ * Errors, nothing written, rt_last_error naming the cause: RT_E_INVALID for a NULL in, table, hits, normal, object,
+ * color_out or table->materials, nmaterials of 0 or above RT_MAX_MATERIALS, instance_material given with ninstances 0,
+ * a misaligned plane (hits, normal, refl, color_out: 16 bytes; object: 8; vis, ao, instance_material, rgba8_out: 4), an
+ * output equal to any input or to the other output (pointer EQUALITY, the filters' rule), W or H of 0, a non-zero
+ * vis_stride below W * H, no camera, no shading; RT_E_UNSUPPORTED for W * H >= 2^31. */
+rt_status rt_shade_resolve_pbr(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_resolve_pbr_inputs* in,
+                               const rt_material_table* table, float* color_out, void* rgba8_out, void* hip_stream);
+
 /* The weights of rt_reflection_composite: both finite, in [0, 1]. strength: the share of the reflection at F = 1;
  * f0: the Fresnel reflectance at normal incidence. */
 typedef struct { float strength; float f0; } rt_reflection_composite_params;
@@ -1100,6 +1161,13 @@ rt_status rt_host_shadow_rays(const float* cam_rays, const float* t, const float
  * the 16-byte alignment (4 bytes will do), the same per-pixel function, so the same bits. */
 rt_status rt_host_shade_resolve(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights, uint32_t nlights,
                                 const rt_resolve_inputs* in, float* color_out, void* rgba8_out);
+
+/* rt_shade_resolve_pbr on host arrays: cb and lights, nlights in place of the context's camera and lights as for
+ * rt_host_shade_resolve, every plane and table->instance_material a HOST array, no stream; the same checks less the
+ * 16-byte alignment (4 bytes will do), the same per-pixel function, so the same bits. */
+rt_status rt_host_shade_resolve_pbr(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights,
+                                    uint32_t nlights, const rt_resolve_pbr_inputs* in, const rt_material_table* table,
+                                    float* color_out, void* rgba8_out);
 
 /* The rays rt_dispatch_reflection traces for n pixels, on the host: the first half of the check of its planes (it
  * calls the functions the reflection kernels call; trace the rays with rt_trace_rays' closest-hit search under

@@ -103,6 +103,23 @@ class rt_resolve_inputs(ctypes.Structure):
                 ("vis", ctypes.c_void_p), ("vis_stride", ctypes.c_uint64), ("ao", ctypes.c_void_p)]
 
 
+RT_MAX_MATERIALS = 32
+
+
+class rt_material_table(ctypes.Structure):
+    """include/rt_api.h rt_material_table: a host array of materials and the optional instance -> material map (a
+    device array for rt_shade_resolve_pbr, a host array for rt_host_shade_resolve_pbr)."""
+    _fields_ = [("materials", ctypes.POINTER(rt_material)), ("nmaterials", ctypes.c_uint32),
+                ("instance_material", ctypes.c_void_p), ("ninstances", ctypes.c_uint32)]
+
+
+class rt_resolve_pbr_inputs(ctypes.Structure):
+    """include/rt_api.h rt_resolve_pbr_inputs: rt_resolve_inputs' fields and the reflection pass's radiance plane."""
+    _fields_ = [("hits", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("object", ctypes.c_void_p),
+                ("vis", ctypes.c_void_p), ("vis_stride", ctypes.c_uint64), ("ao", ctypes.c_void_p),
+                ("refl", ctypes.c_void_p)]
+
+
 class rt_reflection_params(ctypes.Structure):
     """include/rt_api.h rt_reflection_params: samples (1..64), seed, roughness, tmax, shadow_tmin of
     rt_dispatch_reflection."""
@@ -194,6 +211,8 @@ SIGNATURES = [
     ("rt_dispatch_ao", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_ao_params), _P, _P]),
     ("rt_dispatch_shadow", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_shadow_params), _P, ctypes.c_uint64, _P]),
     ("rt_shade_resolve", _I, [_P, _U32, _U32, ctypes.POINTER(rt_resolve_inputs), _P, _P, _P]),
+    ("rt_shade_resolve_pbr", _I, [_P, _U32, _U32, ctypes.POINTER(rt_resolve_pbr_inputs),
+                                  ctypes.POINTER(rt_material_table), _P, _P, _P]),
     ("rt_dispatch_reflection", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_reflection_params),
                                     ctypes.POINTER(rt_reflection_planes), _P]),
     ("rt_reflection_composite", _I, [_P, _U32, _U32, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P, _P,
@@ -252,6 +271,9 @@ SIGNATURES = [
                                  ctypes.POINTER(rt_shadow_params), _P, _P]),
     ("rt_host_shade_resolve", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_light), _U32, ctypes.POINTER(rt_resolve_inputs),
                                    _P, _P]),
+    ("rt_host_shade_resolve_pbr", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_light), _U32,
+                                       ctypes.POINTER(rt_resolve_pbr_inputs), ctypes.POINTER(rt_material_table), _P,
+                                       _P]),
     ("rt_host_reflection_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_reflection_params), _P, _P]),
     ("rt_host_reflection_radiance", _I, [_P, _P, _P, _P, _P, _P, _P, _U32, _U32, ctypes.POINTER(rt_light), _U32,
                                          ctypes.POINTER(rt_reflection_params), _P, _P]),
@@ -591,6 +613,52 @@ def host_shade_resolve(width: int, height: int, camera, lights, hits, normal, ob
     st = lib.rt_host_shade_resolve(width, height, _fptr(cb), arr, nl, ctypes.byref(inp), _vp(out), _vp(out8))
     if st != RT_OK:
         raise RtError(st, "rt_host_shade_resolve")
+    return (out, out8) if want_rgba8 else out
+
+
+def _materials_array(materials):
+    """An rt_material array from 6-tuples (albedo rgb, roughness, metallic, reflectivity), set_shading's material
+    format. The count is left to the library to refuse."""
+    materials = [tuple(float(v) for v in m) for m in materials]
+    arr = (rt_material * max(len(materials), 1))()
+    for k, m in enumerate(materials):
+        if len(m) != 6:
+            raise ValueError(f"material {k}: expected 6 values (albedo rgb, roughness, metallic, reflectivity), got "
+                             f"{len(m)}")
+        arr[k].albedo[:] = m[0:3]
+        arr[k].roughness, arr[k].metallic, arr[k].reflectivity = m[3:6]
+    return arr, len(materials)
+
+
+def host_shade_resolve_pbr(width: int, height: int, camera, lights, hits, normal, object, materials,  # noqa: A002
+                           instance_material=None, vis=None, ao=None, refl=None, want_rgba8: bool = False):
+    """rt_host_shade_resolve_pbr: the PBR resolve on the host (no GPU). camera, lights, hits, normal, object, vis, ao as
+    host_shade_resolve; materials: a sequence of 6-tuples, set_shading's material format (1..32 of them);
+    instance_material: uint32 material indices by instance index (object's first word), or None (material 0
+    everywhere); refl: (n, 4) float32, the reflection pass's radiance plane, or None. Returns color (n, 4) float32 and,
+    with want_rgba8, the (n, 4) uint8 frame as a second."""
+    n = width * height
+    cb = _f32(camera, 64)
+    arr = _lights_array(lights)
+    nl = len(arr)
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    oo = np.ascontiguousarray(object).view(np.uint32).reshape(-1)
+    if hh.size != 4 * n or oo.size != 2 * n:
+        raise ValueError(f"expected {4 * n} hit words and {2 * n} object words, got {hh.size} and {oo.size}")
+    nn = _f32(normal, 4 * n)
+    vv = None if vis is None else _f32(vis, nl * n)
+    aa = None if ao is None else _f32(ao, n)
+    rr = None if refl is None else _f32(refl, 4 * n)
+    mats, nm = _materials_array(materials)
+    im = None if instance_material is None else np.ascontiguousarray(instance_material, dtype=np.uint32).ravel()
+    inp = rt_resolve_pbr_inputs(_vp(hh), _vp(nn), _vp(oo), _vp(vv), 0, _vp(aa), _vp(rr))
+    table = rt_material_table(mats, nm, _vp(im), 0 if im is None else im.size)
+    out = np.zeros((n, 4), np.float32)
+    out8 = np.zeros((n, 4), np.uint8) if want_rgba8 else None
+    st = lib.rt_host_shade_resolve_pbr(width, height, _fptr(cb), arr, nl, ctypes.byref(inp), ctypes.byref(table),
+                                       _vp(out), _vp(out8))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_shade_resolve_pbr")
     return (out, out8) if want_rgba8 else out
 
 
@@ -1423,6 +1491,39 @@ class Context:
         self._check(self._lib.rt_shade_resolve(self._h, width, height, ctypes.byref(inp),
                                                self._plane(m, "color_out", color_out, 4 * n),
                                                self._plane(m, "rgba8_out", out8, n), stream), "rt_shade_resolve")
+
+    def shade_resolve_pbr(self, width: int, height: int, hits, normal, object, color_out, materials,  # noqa: A002
+                          instance_material=None, vis=None, ao=None, refl=None, rgba8_out=None, vis_stride: int = 0,
+                          stream: Optional[int] = None, nlights: Optional[int] = None):
+        """rt_shade_resolve_pbr: shade_resolve with the RT_SHADE_REF hit programs in place of the grey Lambert term and
+        a material per instance. materials: a sequence of 6-tuples, set_shading's material format (1..32 of them),
+        copied during the call; instance_material: a device tensor of uint32 / int32 material indices by instance
+        index (the object plane's first word: the position in tlas_build's list), or None (material 0 everywhere); an
+        index out of either range means material 0. refl: dispatch_reflection's radiance plane (width * height x 4
+        floats) or None: where given, a model pixel's colour is lerped towards it by its material's reflectivity. The
+        plane group is shaded as the reference's PlaneClosestHit (light 0, no material). With one material and no
+        optional plane the model and miss pixels are dispatch()'s RT_SHADE_REF frame bit for bit; with vis from
+        dispatch_shadow(samples=1, light_radius=0) the plane pixels are too. nlights: as for dispatch_shadow."""
+        n, m = width * height, "shade_resolve_pbr"
+        self._vis_planes(m, vis, n, vis_stride, nlights)
+        inp = rt_resolve_pbr_inputs(self._plane(m, "hits", hits, 4 * n), self._plane(m, "normal", normal, 4 * n),
+                                    self._plane(m, "object", object, 2 * n), _ptr(vis), vis_stride,
+                                    self._plane(m, "ao", ao, n), self._plane(m, "refl", refl, 4 * n))
+        mats, nm = _materials_array(materials)
+        ninst = 0
+        if instance_material is not None:
+            if isinstance(instance_material, int):
+                raise ValueError(f"{m}: instance_material must be a tensor (its length is the map's size)")
+            if instance_material.element_size() != 4 or not instance_material.is_contiguous():
+                raise ValueError(f"{m}: instance_material must be a contiguous tensor of 32-bit elements")
+            ninst = instance_material.numel()
+        table = rt_material_table(mats, nm, _ptr(instance_material), ninst)
+        out8 = rgba8_out.view(torch.int32) if isinstance(rgba8_out, torch.Tensor) and rgba8_out.dtype == torch.uint8 \
+            else rgba8_out
+        self._check(self._lib.rt_shade_resolve_pbr(self._h, width, height, ctypes.byref(inp), ctypes.byref(table),
+                                                   self._plane(m, "color_out", color_out, 4 * n),
+                                                   self._plane(m, "rgba8_out", out8, n), stream),
+                    "rt_shade_resolve_pbr")
 
     def dispatch_reflection(self, width: int, height: int, radiance, samples: int = 1, roughness: float = 0.0,
                             tmax: float = 1000.0, shadow_tmin: float = 0.01, seed: int = 0, hits=None,

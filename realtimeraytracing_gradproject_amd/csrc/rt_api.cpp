@@ -2581,6 +2581,73 @@ rt_status rt_shade_resolve(rt_ctx_t c, uint32_t W, uint32_t H, const rt_resolve_
   return RT_OK;
 }
 
+// ---- PBR resolve: the argument check shared by rt_shade_resolve_pbr and rt_host_shade_resolve_pbr
+// (align as above): the Lambert resolve's own check on the six fields the two input structures share, then the table
+// and the radiance plane ---------------------------------------------------------------------------------------
+namespace {
+
+const char* resolve_pbr_args_error(uint32_t W, uint32_t H, const rt_resolve_pbr_inputs* in,
+                                   const rt_material_table* table, const float* color_out, const void* rgba8_out,
+                                   bool align, rt_status* st) {
+  rt_resolve_inputs base = {};
+  if (in) base = {in->hits, in->normal, in->object, in->vis, in->vis_stride, in->ao};
+  if (const char* why = resolve_args_error(W, H, in ? &base : nullptr, color_out, rgba8_out, align, st)) return why;
+  if (!table) return "null table";
+  if (!table->materials) return "null materials array";
+  if (table->nmaterials < 1 || table->nmaterials > (uint32_t)RT_MAX_MATERIALS) return "nmaterials must be in [1,32]";
+  if (table->instance_material && table->ninstances == 0) return "instance_material given with ninstances 0";
+  if (misaligned(table->instance_material, 4)) return "instance_material not aligned to 4 bytes";
+  if (misaligned(in->refl, align ? 16 : 4)) return "refl plane misaligned";
+  for (const void* o : {(const void*)color_out, rgba8_out}) {
+    if (!o) continue;
+    if (o == in->refl || o == table->instance_material) return "an output is an input plane";
+  }
+  return nullptr;
+}
+
+rt::ResolvePbr resolve_pbr_of(uint32_t W, uint32_t H, const float cb[64], const rt::LightRec* lights, uint32_t nlights,
+                              const rt_resolve_pbr_inputs* in, const rt_material_table* table, float* color_out,
+                              void* rgba8_out) {
+  static_assert(RT_MAX_MATERIALS == rt::kMaxMaterials, "the table of the launch holds RT_MAX_MATERIALS entries");
+  static_assert(sizeof(rt_material) == sizeof(rt::MaterialRec), "rt_material is MaterialRec's layout");
+  rt::ResolvePbr r = {};
+  rt::frame_cam(cb, r.cam);
+  std::memcpy(r.lights, lights, sizeof(rt::LightRec) * nlights);
+  r.nlights = nlights;
+  r.W = W, r.H = H;
+  r.fwidth = (float)W, r.fheight = (float)H;  // as resolve_of's
+  r.hits = in->hits, r.normal = in->normal, r.object = in->object;
+  r.vis = in->vis, r.vis_stride = in->vis_stride ? in->vis_stride : (uint64_t)W * H;
+  r.ao = in->ao, r.refl = in->refl;
+  r.instance_material = table->instance_material;
+  r.ninstances = table->instance_material ? table->ninstances : 0u;
+  r.nmaterials = table->nmaterials;
+  for (uint32_t k = 0; k < table->nmaterials; ++k) {
+    std::memcpy(&r.table[k].m, &table->materials[k], sizeof(rt::MaterialRec));
+    rt::surface_consts(r.table[k].m, r.table[k].s);  // as rt_set_shading: the frame kernel's bits
+  }
+  r.color_out = color_out, r.rgba8_out = (uint32_t*)rgba8_out;
+  return r;
+}
+
+}  // namespace
+
+rt_status rt_shade_resolve_pbr(rt_ctx_t c, uint32_t W, uint32_t H, const rt_resolve_pbr_inputs* in,
+                               const rt_material_table* table, float* color_out, void* rgba8_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = resolve_pbr_args_error(W, H, in, table, color_out, rgba8_out, true, &st))
+    return fail(c, st, std::string("rt_shade_resolve_pbr: ") + why);
+  if (!c->have_camera) return fail(c, RT_E_INVALID, "rt_shade_resolve_pbr: camera not set");
+  if (!c->have_shading) return fail(c, RT_E_INVALID, "rt_shade_resolve_pbr: shading not set");
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_shade_resolve_pbr(
+      resolve_pbr_of(W, H, c->cam_cb, c->fp.lights, c->fp.nlights, in, table, color_out, rgba8_out),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "PBR resolve launch");
+  return RT_OK;
+}
+
 // ---- Fresnel composite: the argument check shared by rt_reflection_composite and
 // rt_host_reflection_composite (align as above) -------------------------------------------------------------------
 namespace {
@@ -3062,6 +3129,22 @@ rt_status rt_host_shade_resolve(uint32_t W, uint32_t H, const float cb[64], cons
       resolve_of(W, H, cb, reinterpret_cast<const rt::LightRec*>(lights), nlights, in, color_out, rgba8_out);
   for (uint32_t y = 0; y < H; ++y)
     for (uint32_t x = 0; x < W; ++x) rt::resolve_pixel(r, x, y);
+  return RT_OK;
+}
+
+// Host service: rt_shade_resolve_pbr on host arrays through resolve_pbr_pixel, the function k_shade_resolve_pbr calls,
+// after the device entry point's argument checks (less the 16-byte alignment); the instance map is a host array
+// here, the table is evaluated as the device entry point evaluates it. No context, no GPU call.
+rt_status rt_host_shade_resolve_pbr(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights,
+                                    uint32_t nlights, const rt_resolve_pbr_inputs* in, const rt_material_table* table,
+                                    float* color_out, void* rgba8_out) {
+  rt_status st = RT_OK;
+  if (resolve_pbr_args_error(W, H, in, table, color_out, rgba8_out, false, &st)) return st;
+  if (!cb || !lights || nlights < 1 || nlights > (uint32_t)rt::kMaxLights) return RT_E_INVALID;
+  const rt::ResolvePbr r = resolve_pbr_of(W, H, cb, reinterpret_cast<const rt::LightRec*>(lights), nlights, in, table,
+                                          color_out, rgba8_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::resolve_pbr_pixel(r, x, y);
   return RT_OK;
 }
 

@@ -20,10 +20,14 @@
 //   k_reflection_composite  the Fresnel composite (rt_reflection_composite), one pixel per lane: the colour
 //                       frame, the reflection pass's radiance and the G-buffer's hits and normal planes -> the colour
 //                       frame (four 16-byte loads at most, one 16-byte store, 4 bytes of RGBA8 when asked for).
+//   k_shade_resolve_pbr the PBR resolve (rt_shade_resolve_pbr), one pixel per lane: k_shade_resolve's
+//                       planes, the reflection pass's radiance and an instance -> material map -> the colour frame of
+//                       the RT_SHADE_REF hit programs. The lights, the camera and the material table (32 entries of
+//                       60 B) ride in the kernel argument.
 //
-// The arithmetic of all six is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
-// resolve_pixel, reflection_composite_pixel), which the host twins in rt_api.cpp call too: the kernels differ from them in where a value is read,
-// never in how it is used.
+// The arithmetic of all seven is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
+// resolve_pixel, reflection_composite_pixel, resolve_pbr_pixel), which the host twins in rt_api.cpp call too: the
+// kernels differ from them in where a value is read, never in how it is used.
 // Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
 #include "rt_internal.hpp"
 
@@ -151,9 +155,26 @@ __global__ __launch_bounds__(256) void k_reflection_composite(ReflComposite r) {
   reflection_composite_pixel(r, i % r.W, i / r.W);
 }
 
+// As k_shade_resolve: one-dimensional over the pixels. The light loop is wave-uniform (the lights are scalar loads
+// from the kernel argument); the material index is per lane: a lane reads its entry of r.table from the
+// kernel-argument segment, vector loads of constant memory at a per-lane address, no scratch. (A second form that
+// staged the table in LDS once per workgroup, 1920 B, tied with this one within the spread on both measured scenes and
+// was not kept: DESIGN §3.15.)
+static_assert(sizeof(ResolvePbr) <= 4096, "rt_shade_resolve_pbr's launch must fit the 4 KB kernel-argument segment");
+__global__ __launch_bounds__(256) void k_shade_resolve_pbr(ResolvePbr r) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= r.W * r.H) return;
+  resolve_pbr_pixel(r, i % r.W, i / r.W);
+}
+
 uint32_t tiles(uint32_t n, uint32_t t) { return (n + t - 1u) / t; }
 
 }  // namespace
+
+hipError_t launch_shade_resolve_pbr(const ResolvePbr& r, hipStream_t stream) {
+  hipLaunchKernelGGL(k_shade_resolve_pbr, dim3(tiles(r.W * r.H, 256u)), dim3(256), 0, stream, r);
+  return hipGetLastError();
+}
 
 hipError_t launch_denoise_guide(uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
                                 float* guide, hipStream_t stream) {

@@ -1255,6 +1255,152 @@ RT_HD void reflection_composite_pixel(const ReflComposite& r, uint32_t x, uint32
   if (r.rgba8_out) r.rgba8_out[i] = unorm8(out[0]) | (unorm8(out[1]) << 8) | (unorm8(out[2]) << 16) | (255u << 24);
 }
 
+// The PBR resolve (rt_shade_resolve_pbr): rt_shade_resolve's planes and a table of materials with a
+// per-instance index -> the colour frame of the RT_SHADE_REF hit programs, each light scaled by its visibility and the
+// AO plane. Called by k_shade_resolve_pbr per lane and by rt_host_shade_resolve_pbr per pixel;
+// tests/materials_reference.py restates it in float64.
+constexpr int kMaxMaterials = 32;  // RT_MAX_MATERIALS
+
+// A table entry: the material and its constants (surface_consts, evaluated by the host once per call as rt_set_shading
+// evaluates FrameParams::surf, so a pixel starts from the frame kernel's bits). 15 words.
+struct MaterialEntry {
+  MaterialRec m;
+  SurfaceConsts s;
+};
+
+// rt_shade_resolve_pbr's launch: Resolve's fields, the reflection pass's radiance plane, the instance map and the
+// table by value (vis, ao, refl, instance_material, rgba8_out may be null).
+struct ResolvePbr {
+  FrameCam cam;
+  LightRec lights[kMaxLights];
+  uint32_t nlights;
+  uint32_t W, H;
+  float fwidth, fheight;
+  uint32_t nmaterials, ninstances;
+  const uint32_t* hits;
+  const float* normal;
+  const uint32_t* object;
+  const float* vis;
+  uint64_t vis_stride;
+  const float* ao;
+  const float* refl;
+  const uint32_t* instance_material;
+  float* color_out;
+  uint32_t* rgba8_out;
+  MaterialEntry table[kMaxMaterials];
+};
+
+// ClosestHit's surface colour at P with the un-negated interpolated normal n, seen from cam: rt_trace.hip's
+// surface_ref restated operation for operation (its comment gives the pinning), with the material from a table entry
+// and each light's two terms scaled by s_l = (0.3f * a) + (0.7f * v_l). vis points at the pixel's entry of plane 0 (or
+// is null: v_l = 1). s_l == 1.0f leaves every product as it was (x * 1.0f == x), so without planes the bits are
+// surface_ref's.
+RT_HD V3 surface_pbr(const MaterialEntry& e, const LightRec* lights, uint32_t nlights, V3 P, V3 n, V3 cam, float a,
+                     const float* vis, uint64_t vis_stride) {
+  const V3 albedo = v3(e.m.albedo[0], e.m.albedo[1], e.m.albedo[2]);
+  const float a2 = e.s.a2, k = e.s.k, omk = e.s.omk;
+  const V3 F0 = v3(e.s.F0[0], e.s.F0[1], e.s.F0[2]);
+  const V3 kdA = v3(e.s.kdA[0], e.s.kdA[1], e.s.kdA[2]);
+  const V3 N = neg(muls(n, rcp_exact(sqrtf(dot(n, n)))));
+  const V3 Vd = sub(cam, P);
+  const V3 V = muls(Vd, rcp_exact(sqrtf(dot(Vd, Vd))));
+  const float NdotV = maxf(dot(N, V), 0.0f);
+  const float ggx2 = NdotV * rcp_exact(NdotV * omk + k);
+  const float v4 = 4.0f * NdotV;
+  const float sa = 0.3f * a;
+  V3 cd = v3(0.0f, 0.0f, 0.0f), L0 = v3(0.0f, 0.0f, 0.0f);
+  for (uint32_t l = 0; l < nlights; ++l) {
+    const LightRec& Lr = lights[l];
+    const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+    const V3 lc = v3(Lr.color[0], Lr.color[1], Lr.color[2]);
+    const float s = sa + (0.7f * (vis ? vis[(size_t)l * vis_stride] : 1.0f));
+    const V3 dv = sub(lp, P);
+    const float dist = sqrtf(dot(dv, dv));
+    const V3 L = muls(dv, rcp_exact(dist));
+    // CalculateDirectLighting
+    const float ti = maxf(0.0f, dot(n, neg(L)) * Lr.intensity);
+    cd = add(cd, muls(mul(albedo, lc), ti * s));
+    // CalculatePBRShading
+    const V3 Hd = add(V, L);
+    const V3 H = muls(Hd, rcp_exact(sqrtf(dot(Hd, Hd))));
+    const float att = rcp_exact(maxf(dist * dist, 1.0f));
+    const V3 radiance = muls(lc, att);
+    const float x = clamp01(1.0f - maxf(dot(H, V), 0.0f));
+    const float x2 = x * x;
+    const float x5 = (x2 * x2) * x;
+    const V3 F = v3(F0.x + (1.0f - F0.x) * x5, F0.y + (1.0f - F0.y) * x5, F0.z + (1.0f - F0.z) * x5);
+    const float NdotH = maxf(dot(N, H), 0.0f);
+    const float NdotH2 = NdotH * NdotH;
+    float denom = NdotH2 * (a2 - 1.0f) + 1.0f;
+    denom = (kPiF * denom) * denom;
+    const float NDF = a2 * rcp_exact(denom);
+    const float NdotL = maxf(dot(N, L), 0.0f);
+    const float ggx1 = NdotL * rcp_exact(NdotL * omk + k);
+    const float G = ggx1 * ggx2;
+    const float sp = (NDF * G) * rcp_exact(v4 * NdotL + 0.0001f);
+    const V3 spec = muls(F, sp);
+    const V3 diff = v3((1.0f - F.x) * kdA.x, (1.0f - F.y) * kdA.y, (1.0f - F.z) * kdA.z);
+    L0 = add(L0, muls(mul(add(diff, spec), radiance), NdotL * s));
+  }
+  V3 c = muls(L0, 0.2f);
+  c = v3(c.x * rcp_exact(c.x + 1.0f), c.y * rcp_exact(c.y + 1.0f), c.z * rcp_exact(c.z + 1.0f));
+  const float g = 1.0f / 2.2f;
+  return add(cd, v3(det_pow(c.x, g), det_pow(c.y, g), det_pow(c.z, g)));
+}
+
+// Pixel (x, y) of rt_shade_resolve_pbr:
+//   a miss: the miss colour, as resolve_pixel;
+//   the plane group: PlaneClosestHit as shade_ref evaluates it (light 0 only, no material), (1.0f * li) * s_0;
+//   any other group: surface_pbr with the material of the pixel's instance (object[2i] through instance_material, 0
+//   where either index is out of range), then HLSL's lerp towards refl by the material's reflectivity where that is
+//   not 0 and the normal is valid (ao_normal_valid, rt_dispatch_reflection's rule).
+RT_HD void resolve_pbr_pixel(const ResolvePbr& r, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * r.W + x;
+  float h[4];
+  ld4(reinterpret_cast<const float*>(r.hits) + 4 * i, h);  // bits only: (t, instance id, primitive, hit flag)
+  V3 col;
+  if (__builtin_bit_cast(uint32_t, h[3]) == 0u) {
+    const float ramp = (float)y / r.fheight;  // miss_color, Miss.hlsl:8
+    col = v3(0.0f, 0.2f, 0.7f - 0.3f * ramp);
+  } else {
+    V3 O, D;
+    pixel_ray(r.cam, r.fwidth, r.fheight, x, y, O, D);
+    const V3 P = add(O, muls(D, h[0]));  // GetWorldHitPoint, Common.hlsl:24-27
+    float nv[4];
+    ld4(r.normal + 4 * i, nv);
+    const V3 n = v3(nv[0], nv[1], nv[2]);
+    const uint32_t inst = r.object[2 * i], group = r.object[2 * i + 1];
+    const float a = r.ao ? r.ao[i] : 1.0f;
+    const float* vis = r.vis ? r.vis + i : nullptr;
+    if (group == 2u) {  // PlaneClosestHit, Hit.hlsl:207-241
+      const LightRec& L0 = r.lights[0];
+      const V3 ldir = normalize(sub(v3(L0.position[0], L0.position[1], L0.position[2]), P));
+      const float s = (0.3f * a) + (0.7f * (vis ? vis[0] : 1.0f));
+      const float li = maxf(0.0f, dot(n, ldir));
+      const float c = (1.0f * li) * s;
+      col = v3(c, c, c);
+    } else {  // ClosestHit, Hit.hlsl:183-204
+      uint32_t m = 0u;
+      if (r.instance_material && inst < r.ninstances) m = r.instance_material[inst];
+      if (m >= r.nmaterials) m = 0u;
+      const MaterialEntry& e = r.table[m];
+      col = surface_pbr(e, r.lights, r.nlights, P, n, O, a, vis, r.vis_stride);
+      const float rf = e.m.reflectivity;
+      if (r.refl && rf != 0.0f && ao_normal_valid(n)) {
+        float q[4];
+        ld4(r.refl + 4 * i, q);
+        // HLSL's lerp, x + s (y - x), Hit.hlsl:203. At s == 1 that is x + (y - x), which rounds to y only where y - x
+        // is exact, so a perfect mirror takes the plane's own bits.
+        col = rf == 1.0f ? v3(q[0], q[1], q[2])
+                         : v3(col.x + rf * (q[0] - col.x), col.y + rf * (q[1] - col.y), col.z + rf * (q[2] - col.z));
+      }
+    }
+  }
+  const float out[4] = {col.x, col.y, col.z, 1.0f};
+  st4(r.color_out + 4 * i, out);
+  if (r.rgba8_out) r.rgba8_out[i] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | (255u << 24);
+}
+
 // ------------------------------------------------------------------------------------------
 // Temporal upscaler (rt_upscale): the per-pixel arithmetic, called by the kernels of rt_upscale.hip per
 // lane and by rt_host_upscale per pixel. The AO filter's rule (above), less sqrtf; tests/upscale_reference.py restates

@@ -215,6 +215,11 @@ hipError_t launch_trace_shadow(const SceneView& scene, const ShadowParams& param
 // shared with rt_host_shade_resolve.
 hipError_t launch_shade_resolve(const Resolve& r, hipStream_t stream);
 
+// --- PBR resolve (rt_denoise.hip) ----------------------------------------------
+// One launch, one pixel per lane; no scene, no scratch. Its per-pixel arithmetic is rt_device.hpp's resolve_pbr_pixel,
+// shared with rt_host_shade_resolve_pbr; the material table rides in the kernel argument.
+hipError_t launch_shade_resolve_pbr(const ResolvePbr& r, hipStream_t stream);
+
 // --- Deferred reflections (rt_trace.hip, rt_denoise.hip) -----------------------
 // The reflection pass (rt_dispatch_reflection): launch_trace_shadow's schedule rule and grids on the reflection
 // kernels; params.radiance (and params.hits, when given) are written, params.gb's planes are not read.
