@@ -224,10 +224,23 @@ $(ASAN)/materials_asan.o: tools/materials_asan.cpp include/rt_api.h | $(ASAN)
 $(ASAN)/materials_check: $(ASAN)/materials_asan.o $(ASAN_API_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
+# the same for the PBR reflection pass's host twins (rt_host_reflection_rays_flags, rt_host_reflection_radiance_pbr:
+# per-sample, per-light and per-instance indexing, the material table and the map's two range checks, on exact-size
+# heap blocks):
+#   make asan-reflection-pbr && build/asan/reflection_pbr_check
+asan-reflection-pbr: $(ASAN)/reflection_pbr_check
+
+$(ASAN)/reflection_pbr_asan.o: tools/reflection_pbr_asan.cpp include/rt_api.h | $(ASAN)
+	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
+
+$(ASAN)/reflection_pbr_check: $(ASAN)/reflection_pbr_asan.o $(ASAN_API_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
+
 $(ASAN):
 	mkdir -p $@
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VDIR)
 
-.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials
+.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials \
+        asan-reflection-pbr

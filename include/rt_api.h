@@ -38,7 +38,9 @@ extern "C" {
  * rt_resolve_inputs, and rt_dispatch_reflection, rt_reflection_composite, their host twins rt_host_reflection_rays,
  * rt_host_reflection_radiance and rt_host_reflection_composite, rt_reflection_params, rt_reflection_planes and
  * rt_reflection_composite_params, and rt_shade_resolve_pbr, its host twin rt_host_shade_resolve_pbr, rt_material_table,
- * rt_resolve_pbr_inputs and RT_MAX_MATERIALS. */
+ * rt_resolve_pbr_inputs and RT_MAX_MATERIALS, and rt_dispatch_reflection_pbr, its host twins
+ * rt_host_reflection_rays_flags and rt_host_reflection_radiance_pbr, rt_reflection_pbr_params and the RT_REFLECT_*
+ * flags. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -842,6 +844,58 @@ typedef struct {
 rt_status rt_shade_resolve_pbr(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_resolve_pbr_inputs* in,
                                const rt_material_table* table, float* color_out, void* rgba8_out, void* hip_stream);
 
+/* Flags of rt_dispatch_reflection_pbr. RT_REFLECT_FRAME_RAY: the mirror direction is the frame kernels' own (about the
+ * G-buffer normal as stored, no renormalisation). RT_REFLECT_SHADOW_MODELS: a reflected MODEL hit traces one shadow
+ * ray per light it faces (the reference's ClosestHit traces none). */
+enum { RT_REFLECT_FRAME_RAY = 1u, RT_REFLECT_SHADOW_MODELS = 2u };
+
+/* Parameters of the PBR reflection pass: rt_reflection_params' five values, with its ranges, and the flags. */
+typedef struct { uint32_t samples; uint32_t seed; float roughness; float tmax; float shadow_tmin; uint32_t flags; }
+    rt_reflection_pbr_params;
+
+/* The PBR reflection pass: rt_dispatch_reflection with the reference's hit programs evaluated at each
+ * reflected hit, with that hit's material, in place of the grey RT_SHADE_LAMBERT_SHADOW term. Everything
+ * rt_dispatch_reflection documents about W, H, rows, nrows, the schedule rule and the per-lane fall-back,
+ * rt_set_triangle_test, streams, slot rings, the TLAS double buffer, the validity of the primary normal and the zero
+ * entries on a primary miss holds unchanged; `out` is that pass's structure. The table follows rt_shade_resolve_pbr's
+ * rules: the materials are a host array copied during the call (surface constants evaluated once per entry on the
+ * host) and travel by value with the launch; instance_material is a device array keyed by the instance's INDEX in the
+ * rt_tlas_build list; the material of instance inst is m = instance_material ? (inst < ninstances ?
+ * instance_material[inst] : 0) : 0, then m < nmaterials ? m : 0 (no read falls outside either array).
+ * Rays: with RT_REFLECT_FRAME_RAY clear, ray k is rt_dispatch_reflection's ray k to the bit, so for equal parameters
+ * the hits plane and radiance.w of the two passes are identical. With the flag set the mirror direction is
+ * m = normalize(normalize(reflect(normalize(D), N))) on the G-buffer normal N as stored (the frame kernels'
+ * ReflectRay expression: renormalising an already unit normal changes the ray's bits); roughness perturbs whichever m
+ * was chosen, and the horizon test still uses the facing normal of normalize(N).
+ * Colour of ray k (origin ro = P + d_k * 0.001f, direction d_k):
+ *   a miss: the frame's miss colour at the pixel's row, t_k = tmax, as rt_dispatch_reflection;
+ *   a hit at t2 in instance inst of hit group g2, G-buffer-form normal N2 (rt_gbuffer.normal's form: the face normal
+ *   of the plane group, the un-negated interpolated normal of every other), P2 = ro + d_k * t2, t_k = t2:
+ *     g2 == RT_HITGROUP_PLANE: PlaneClosestHit as RT_SHADE_REF evaluates it: ldir = normalize(lp_0 - P2); one any-hit
+ *       shadow ray (P2, shadow_tmin, normalize(ldir), 100000) is always traced; shadowed = dot(N2, ldir) < 0 ||
+ *       occluded; c = (1.0f * max(0, dot(N2, ldir))) * (shadowed ? 0.3f : 1.0f), colour (c, c, c). Light 0 only, no
+ *       material.
+ *     any other group: ClosestHit's surface colour in RT_SHADE_REF's float32 sequence, operation for operation (see
+ *       rt_shade_resolve_pbr), with n = N2, cam = ro (the reflection ray's WorldRayOrigin) and the material of inst;
+ *       per light the two sums take a factor s_l: 1.0f with no ray traced when RT_REFLECT_SHADOW_MODELS is clear (the
+ *       reference); with the flag, for each light the hit faces (dot(-N2, normalize(lp_l - P2)) > 0, the visibility
+ *       pass's rule) one radius-0 shadow ray of rt_dispatch_shadow from P2 with shadow_tmin is traced and
+ *       s_l = occluded ? 0.3f : 1.0f; a light the hit does not face has s_l = 1.0f and no ray.
+ *     The reflected hit's own reflectivity is not applied: one bounce.
+ *   The reduction, hits and radiance.w are rt_dispatch_reflection's.
+ * Hence the anchor: with samples 1, roughness 0, tmax 1000, shadow_tmin 0.01 and RT_REFLECT_FRAME_RAY, feeding
+ * rt_shade_resolve_pbr (vis from rt_dispatch_shadow at radius 0, samples 1, tmin 0.01) reproduces rt_dispatch_rays'
+ * RT_SHADE_REF frame with a reflective material bit for bit at every pixel whose mirror chain is at most one bounce.
+ * rt_set_stats: as rt_dispatch_reflection, with RT_STAT_SHADOW_RAYS growing by the reflected plane hits and, with
+ * RT_REFLECT_SHADOW_MODELS, by the lit (model hit, light) pairs as well.
+ * Errors (RT_E_INVALID, nothing written, rt_last_error naming the cause): every case of rt_dispatch_reflection, a NULL
+ * table or table->materials, nmaterials of 0 or above RT_MAX_MATERIALS, instance_material given with ninstances 0, a
+ * misaligned instance_material (4 bytes), a flag bit outside the two defined.
+ * Reference: ClosestHit / PlaneClosestHit as the hit programs of a reflection ray (Hit.hlsl:183-241). */
+rt_status rt_dispatch_reflection_pbr(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                     const rt_reflection_pbr_params* params, const rt_material_table* table,
+                                     const rt_reflection_planes* out, void* hip_stream);
+
 /* The weights of rt_reflection_composite: both finite, in [0, 1]. strength: the share of the reflection at F = 1;
  * f0: the Fresnel reflectance at normal incidence. */
 typedef struct { float strength; float f0; } rt_reflection_composite_params;
@@ -1194,6 +1248,26 @@ rt_status rt_host_reflection_radiance(const float* rays, const uint32_t* hits, c
                                       const uint32_t* py, uint32_t n, uint32_t H, const rt_light* lights,
                                       uint32_t nlights, const rt_reflection_params* params, float* radiance_out,
                                       uint8_t* lit_out);
+
+/* rt_host_reflection_rays for rt_dispatch_reflection_pbr: the same function with the pass's flags (of which
+ * RT_REFLECT_FRAME_RAY changes the rays). With flags 0 it returns rt_host_reflection_rays' bytes. A flag bit outside
+ * the two defined: RT_E_INVALID. */
+rt_status rt_host_reflection_rays_flags(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
+                                        const uint32_t* py, uint32_t n, const rt_reflection_pbr_params* params,
+                                        float* rays_out, uint8_t* valid_out);
+
+/* The radiance plane rt_dispatch_reflection_pbr writes for n pixels, on the host, from what the traced rays found:
+ * rt_host_reflection_radiance's arguments, and hit_inst: n x S words, each hit's instance index (not read for a
+ * miss); table: the materials and the map, instance_material a HOST array here. occluded is read at light 0 of every
+ * plane hit and, with RT_REFLECT_SHADOW_MODELS, where a model hit faces the light; lit_out (or NULL) is 1 exactly
+ * there: the shadow rays the pass traces. Errors as rt_host_reflection_radiance, and the table's and the flags' cases
+ * of rt_dispatch_reflection_pbr. */
+rt_status rt_host_reflection_radiance_pbr(const float* rays, const uint32_t* hits, const float* hit_normal,
+                                          const uint32_t* hit_group, const uint32_t* hit_inst, const uint8_t* occluded,
+                                          const uint8_t* valid, const uint32_t* py, uint32_t n, uint32_t H,
+                                          const rt_light* lights, uint32_t nlights,
+                                          const rt_reflection_pbr_params* params, const rt_material_table* table,
+                                          float* radiance_out, uint8_t* lit_out);
 
 /* rt_reflection_composite on host arrays: cb in place of the context's camera (rt_set_camera's layout; the origin and
  * the inverses are derived from it as rt_set_camera's are), no stream; the same checks less the 16-byte alignment

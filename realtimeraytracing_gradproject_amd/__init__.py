@@ -127,6 +127,17 @@ class rt_reflection_params(ctypes.Structure):
                 ("tmax", ctypes.c_float), ("shadow_tmin", ctypes.c_float)]
 
 
+RT_REFLECT_FRAME_RAY = 1
+RT_REFLECT_SHADOW_MODELS = 2
+
+
+class rt_reflection_pbr_params(ctypes.Structure):
+    """include/rt_api.h rt_reflection_pbr_params: rt_reflection_params' fields and the RT_REFLECT_* flags of
+    rt_dispatch_reflection_pbr."""
+    _fields_ = [("samples", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("roughness", ctypes.c_float),
+                ("tmax", ctypes.c_float), ("shadow_tmin", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
 class rt_reflection_planes(ctypes.Structure):
     """include/rt_api.h rt_reflection_planes: the planes rt_dispatch_reflection writes (hits may be None)."""
     _fields_ = [("radiance", ctypes.c_void_p), ("hits", ctypes.c_void_p)]
@@ -215,6 +226,8 @@ SIGNATURES = [
                                   ctypes.POINTER(rt_material_table), _P, _P, _P]),
     ("rt_dispatch_reflection", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_reflection_params),
                                     ctypes.POINTER(rt_reflection_planes), _P]),
+    ("rt_dispatch_reflection_pbr", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_reflection_pbr_params),
+                                        ctypes.POINTER(rt_material_table), ctypes.POINTER(rt_reflection_planes), _P]),
     ("rt_reflection_composite", _I, [_P, _U32, _U32, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P, _P,
                                      _P, _P, _P]),
     ("rt_denoise_guide", _I, [_P, _U32, _P, _P, _U32, _P, _P]),
@@ -277,6 +290,11 @@ SIGNATURES = [
     ("rt_host_reflection_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_reflection_params), _P, _P]),
     ("rt_host_reflection_radiance", _I, [_P, _P, _P, _P, _P, _P, _P, _U32, _U32, ctypes.POINTER(rt_light), _U32,
                                          ctypes.POINTER(rt_reflection_params), _P, _P]),
+    ("rt_host_reflection_rays_flags", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_reflection_pbr_params), _P,
+                                           _P]),
+    ("rt_host_reflection_radiance_pbr", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _U32, _U32, ctypes.POINTER(rt_light), _U32,
+                                             ctypes.POINTER(rt_reflection_pbr_params),
+                                             ctypes.POINTER(rt_material_table), _P, _P]),
     ("rt_host_reflection_composite", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P,
                                           _P, _P, _P]),
     ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
@@ -724,6 +742,74 @@ def host_reflection_radiance(rays, hits, hit_normal, hit_group, occluded, valid,
                                          nl, ctypes.byref(p), _vp(out), _vp(lit))
     if st != RT_OK:
         raise RtError(st, "rt_host_reflection_radiance")
+    return (out, lit) if want_lit else out
+
+
+def host_reflection_rays_flags(cam_rays, t, normal, px, py, samples: int = 1, roughness: float = 0.0,
+                               tmax: float = 1000.0, shadow_tmin: float = 0.01, seed: int = 0, flags: int = 0):
+    """rt_host_reflection_rays_flags: the rays rt_dispatch_reflection_pbr traces, on the host (no GPU):
+    host_reflection_rays' arguments and results, and the pass's flags (RT_REFLECT_FRAME_RAY: the frame kernels' mirror
+    direction, about the normal as stored). With flags 0 the bytes are host_reflection_rays'."""
+    cr = np.ascontiguousarray(cam_rays, dtype=np.float32).reshape(-1, 8)
+    n = cr.shape[0]
+    tt = _f32(t, n)
+    nr = _f32(normal, 4 * n)
+    x = np.ascontiguousarray(px, dtype=np.uint32).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if x.size != n or y.size != n:
+        raise ValueError(f"expected {n} pixel coordinates, got {x.size} and {y.size}")
+    if not 1 <= int(samples) <= 64:  # the function's own limit, checked before the output is sized by it
+        raise RtError(RT_E_INVALID, f"rt_host_reflection_rays_flags: samples {samples} outside 1..64")
+    p = rt_reflection_pbr_params(samples, seed, roughness, tmax, shadow_tmin, flags)
+    rays = np.zeros((n, int(samples), 8), np.float32)
+    valid = np.zeros(n, np.uint8)
+    st = lib.rt_host_reflection_rays_flags(_vp(cr), _vp(tt), _vp(nr), _vp(x), _vp(y), n, ctypes.byref(p), _vp(rays),
+                                           _vp(valid))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_reflection_rays_flags")
+    return rays, valid
+
+
+def host_reflection_radiance_pbr(rays, hits, hit_normal, hit_group, hit_inst, occluded, valid, py, height: int, lights,
+                                 materials, instance_material=None, roughness: float = 0.0, tmax: float = 1000.0,
+                                 shadow_tmin: float = 0.01, seed: int = 0, flags: int = 0, want_lit: bool = False):
+    """rt_host_reflection_radiance_pbr: rt_dispatch_reflection_pbr's radiance plane from what its rays found, on the
+    host (no GPU). host_reflection_radiance's arguments, and hit_inst: (n, S) instance indices of the hits; materials:
+    a sequence of 6-tuples (1..32); instance_material: uint32 material indices by instance index, or None. occluded is
+    read at light 0 of every plane hit and, with RT_REFLECT_SHADOW_MODELS, where a model hit faces the light. Returns
+    (n, 4) float32 and, with want_lit, the (n, S, nlights) uint8 mask of the shadow rays the pass traces."""
+    ry = np.ascontiguousarray(rays, dtype=np.float32)
+    if ry.ndim != 3 or ry.shape[2] != 8:
+        raise ValueError(f"rays must be (n, samples, 8), got {ry.shape}")
+    n, S = ry.shape[0], ry.shape[1]
+    arr = _lights_array(lights)
+    nl = len(arr)
+    if not 1 <= S <= 64:
+        raise RtError(RT_E_INVALID, f"rt_host_reflection_radiance_pbr: samples {S} outside 1..64")
+    if not 1 <= nl <= 16:
+        raise RtError(RT_E_INVALID, f"rt_host_reflection_radiance_pbr: {nl} lights, outside 1..16")
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    hn = _f32(hit_normal, 4 * n * S)
+    hg = np.ascontiguousarray(hit_group, dtype=np.uint32).ravel()
+    hi = np.ascontiguousarray(hit_inst, dtype=np.uint32).ravel()
+    oc = np.ascontiguousarray(occluded, dtype=np.uint8).ravel()
+    va = np.ascontiguousarray(valid, dtype=np.uint8).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if hh.size != 4 * n * S or hg.size != n * S or hi.size != n * S or oc.size != n * S * nl or va.size != n \
+            or y.size != n:
+        raise ValueError(f"expected {n} x {S} records, hit groups and instances, {n * S * nl} occlusion bytes and {n} "
+                         f"valid bytes and rows, got {hh.size // 4}, {hg.size}, {hi.size}, {oc.size}, {va.size} and "
+                         f"{y.size}")
+    mats, nm = _materials_array(materials)
+    im = None if instance_material is None else np.ascontiguousarray(instance_material, dtype=np.uint32).ravel()
+    table = rt_material_table(mats, nm, _vp(im), 0 if im is None else im.size)
+    p = rt_reflection_pbr_params(S, seed, roughness, tmax, shadow_tmin, flags)
+    out = np.zeros((n, 4), np.float32)
+    lit = np.zeros((n, S, nl), np.uint8) if want_lit else None
+    st = lib.rt_host_reflection_radiance_pbr(_vp(ry), _vp(hh), _vp(hn), _vp(hg), _vp(hi), _vp(oc), _vp(va), _vp(y), n,
+                                             height, arr, nl, ctypes.byref(p), ctypes.byref(table), _vp(out), _vp(lit))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_reflection_radiance_pbr")
     return (out, lit) if want_lit else out
 
 
@@ -1540,6 +1626,36 @@ class Context:
         p = rt_reflection_params(samples, seed, roughness, tmax, shadow_tmin)
         self._check(self._lib.rt_dispatch_reflection(self._h, width, height, rp, nr, ctypes.byref(p), ctypes.byref(g),
                                                      stream), "rt_dispatch_reflection")
+
+    def dispatch_reflection_pbr(self, width: int, height: int, radiance, materials, instance_material=None,
+                                samples: int = 1, roughness: float = 0.0, tmax: float = 1000.0,
+                                shadow_tmin: float = 0.01, seed: int = 0, flags: int = 0, hits=None,
+                                rows: Optional[np.ndarray] = None, stream: Optional[int] = None):
+        """rt_dispatch_reflection_pbr: dispatch_reflection with the RT_SHADE_REF hit programs at each reflected hit: the
+        plane group as the reference's PlaneClosestHit (light 0, one shadow ray), every other group as ClosestHit's
+        surface colour with the hit instance's material. materials, instance_material: as for shade_resolve_pbr.
+        flags: RT_REFLECT_FRAME_RAY (the frame kernels' mirror direction, about the normal as stored: what makes
+        shade_resolve_pbr(refl=...) equal dispatch()'s reflective RT_SHADE_REF frame bit for bit where the mirror chain
+        is one bounce long) and RT_REFLECT_SHADOW_MODELS (a shadow ray per light a reflected model hit faces). With
+        flags 0 the rays, the hits plane and radiance's .w are dispatch_reflection's. host_reflection_rays_flags and
+        host_reflection_radiance_pbr give the rays and the plane."""
+        m = "dispatch_reflection_pbr"
+        rp, nr, _keep = self._rows_arg(rows, height)
+        g = rt_reflection_planes()
+        self._set_planes(g, m, nr * width, (("radiance", radiance, 4), ("hits", hits, 4)))
+        mats, nm = _materials_array(materials)
+        ninst = 0
+        if instance_material is not None:
+            if isinstance(instance_material, int):
+                raise ValueError(f"{m}: instance_material must be a tensor (its length is the map's size)")
+            if instance_material.element_size() != 4 or not instance_material.is_contiguous():
+                raise ValueError(f"{m}: instance_material must be a contiguous tensor of 32-bit elements")
+            ninst = instance_material.numel()
+        table = rt_material_table(mats, nm, _ptr(instance_material), ninst)
+        p = rt_reflection_pbr_params(samples, seed, roughness, tmax, shadow_tmin, flags)
+        self._check(self._lib.rt_dispatch_reflection_pbr(self._h, width, height, rp, nr, ctypes.byref(p),
+                                                         ctypes.byref(table), ctypes.byref(g), stream),
+                    "rt_dispatch_reflection_pbr")
 
     def reflection_composite(self, width: int, height: int, color_in, radiance, hits, normal, color_out,
                              strength: float = 1.0, f0: float = 0.04, rgba8_out=None, stream: Optional[int] = None):

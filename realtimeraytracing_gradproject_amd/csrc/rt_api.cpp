@@ -2648,6 +2648,76 @@ rt_status rt_shade_resolve_pbr(rt_ctx_t c, uint32_t W, uint32_t H, const rt_reso
   return RT_OK;
 }
 
+// ---- PBR reflection pass: rt_dispatch_reflection's checks and launch sequence around the PBR
+// reflection kernels, with the PBR resolve's table rules. The checks of the parameters and of the table are shared
+// with the host twins ------------------------------------------------------------------------------------------
+namespace {
+
+const char* reflection_pbr_params_error(const rt_reflection_pbr_params* p, rt_reflection_params* base) {
+  if (!p) return "null params";
+  *base = {p->samples, p->seed, p->roughness, p->tmax, p->shadow_tmin};
+  if (const char* why = reflection_params_error(base)) return why;
+  if (p->flags & ~(uint32_t)(RT_REFLECT_FRAME_RAY | RT_REFLECT_SHADOW_MODELS)) return "unknown flag bits";
+  return nullptr;
+}
+
+const char* material_table_error(const rt_material_table* table) {
+  if (!table) return "null table";
+  if (!table->materials) return "null materials array";
+  if (table->nmaterials < 1 || table->nmaterials > (uint32_t)RT_MAX_MATERIALS) return "nmaterials must be in [1,32]";
+  if (table->instance_material && table->ninstances == 0) return "instance_material given with ninstances 0";
+  if (misaligned(table->instance_material, 4)) return "instance_material not aligned to 4 bytes";
+  return nullptr;
+}
+
+// The launch structure's part that the device entry point and the host twin fill alike (resolve_pbr_of's table code).
+void reflection_pbr_of(const rt_reflection_pbr_params* p, const rt_material_table* table, const rt::LightRec* lights,
+                       uint32_t nlights, rt::ReflectionPbrParams& pp) {
+  std::memcpy(pp.rp.lights, lights, sizeof(rt::LightRec) * nlights);
+  pp.rp.nlights = nlights;
+  pp.rp.samples = p->samples;
+  pp.rp.seed = p->seed;
+  pp.rp.roughness = p->roughness;
+  pp.rp.tmax = p->tmax;
+  pp.rp.shadow_tmin = p->shadow_tmin;
+  pp.flags = p->flags;
+  pp.instance_material = table->instance_material;
+  pp.ninstances = table->instance_material ? table->ninstances : 0u;
+  pp.nmaterials = table->nmaterials;
+  for (uint32_t k = 0; k < table->nmaterials; ++k) {
+    std::memcpy(&pp.table[k].m, &table->materials[k], sizeof(rt::MaterialRec));
+    rt::surface_consts(pp.table[k].m, pp.table[k].s);  // as rt_set_shading: the frame kernel's bits
+  }
+}
+
+}  // namespace
+
+rt_status rt_dispatch_reflection_pbr(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                     const rt_reflection_pbr_params* params, const rt_material_table* table,
+                                     const rt_reflection_planes* out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  const std::string fn = "rt_dispatch_reflection_pbr";
+  rt_reflection_params base;
+  if (const char* why = reflection_pbr_params_error(params, &base)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (const char* why = material_table_error(table)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (!out) return fail(c, RT_E_INVALID, fn + ": null output planes");
+  if (!out->radiance) return fail(c, RT_E_INVALID, fn + ": null radiance plane");
+  if ((uintptr_t)out->radiance % 16u) return fail(c, RT_E_INVALID, fn + ": radiance plane not aligned to 16 bytes");
+  if ((uintptr_t)out->hits % 16u) return fail(c, RT_E_INVALID, fn + ": hits plane not aligned to 16 bytes");
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  if (st != RT_OK) return st;
+  if (!c->have_shading) return fail(c, RT_E_INVALID, fn + ": shading not set");
+  rt::ReflectionPbrParams pp = {};
+  reflection_pbr_of(params, table, c->fp.lights, c->fp.nlights, pp);
+  pp.rp.radiance = out->radiance;
+  pp.rp.hits = out->hits;
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, pp.rp.gb, "PBR reflection launch",
+                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
+                            return rt::launch_trace_reflection_pbr(sv, pp, d_rows, c->d_stats, c->stats_on, c->schedule,
+                                                                   s);
+                          });
+}
+
 // ---- Fresnel composite: the argument check shared by rt_reflection_composite and
 // rt_host_reflection_composite (align as above) -------------------------------------------------------------------
 namespace {
@@ -3233,6 +3303,112 @@ rt_status rt_host_reflection_radiance(const float* rays, const uint32_t* hits, c
       }
       c = rt::reflection_hit_color(c, nlights);
       rt::reflection_sum_add(sum, rt::v3(c, c, c), t2);
+    }
+    rt::reflection_reduce(sum, S, out);
+  }
+  return RT_OK;
+}
+
+// Host service: the rays rt_dispatch_reflection_pbr traces: rt_host_reflection_rays' loop with the pass's mirror
+// direction (reflection_pbr_mirror, the function the PBR reflection kernels call). No context, no GPU call.
+rt_status rt_host_reflection_rays_flags(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
+                                        const uint32_t* py, uint32_t n, const rt_reflection_pbr_params* params,
+                                        float* rays_out, uint8_t* valid_out) {
+  rt_reflection_params base;
+  if (reflection_pbr_params_error(params, &base) || (n && (!cam_rays || !t || !normal || !px || !py || !rays_out)))
+    return RT_E_INVALID;
+  const uint32_t S = params->samples;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* cr = cam_rays + 8 * (size_t)i;
+    const float* nr = normal + 4 * (size_t)i;
+    float* out = rays_out + 8 * (size_t)i * S;
+    const rt::V3 O = rt::v3(cr[0], cr[1], cr[2]), D = rt::v3(cr[4], cr[5], cr[6]), nv = rt::v3(nr[0], nr[1], nr[2]);
+    const bool valid = rt::ao_normal_valid(nv);
+    if (valid_out) valid_out[i] = valid ? 1 : 0;
+    if (!valid) {
+      std::memset(out, 0, sizeof(float) * 8 * (size_t)S);
+      continue;
+    }
+    const rt::V3 nn = rt::normalize(nv);
+    const rt::V3 m = rt::reflection_pbr_mirror(D, nv, nn, params->flags);
+    const rt::V3 nf = rt::ao_facing_normal(nn, D);
+    const rt::V3 P = rt::add(O, rt::muls(D, t[i]));
+    const uint32_t base_k = rt::reflection_base(px[i], py[i], params->seed);
+    for (uint32_t k = 0; k < S; ++k) {
+      const rt::V3 d = rt::reflection_direction(m, nf, params->roughness, base_k, k);
+      const rt::V3 ro = rt::reflection_origin(P, d);
+      float* r = out + 8 * (size_t)k;
+      r[0] = ro.x, r[1] = ro.y, r[2] = ro.z, r[3] = 0.001f;
+      r[4] = d.x, r[5] = d.y, r[6] = d.z, r[7] = params->tmax;
+    }
+  }
+  return RT_OK;
+}
+
+// Host service: rt_dispatch_reflection_pbr's radiance plane for n pixels from the records, normals, hit groups,
+// instances and occlusion of the traced rays, through the functions the PBR reflection kernels call
+// (reflection_miss_color, reflection_plane_color, material_index, shadow_lit, the split surface form,
+// reflection_sum_add, reflection_reduce), in the kernels' order of operations. No context, no GPU call.
+rt_status rt_host_reflection_radiance_pbr(const float* rays, const uint32_t* hits, const float* hit_normal,
+                                          const uint32_t* hit_group, const uint32_t* hit_inst, const uint8_t* occluded,
+                                          const uint8_t* valid, const uint32_t* py, uint32_t n, uint32_t H,
+                                          const rt_light* lights, uint32_t nlights,
+                                          const rt_reflection_pbr_params* params, const rt_material_table* table,
+                                          float* radiance_out, uint8_t* lit_out) {
+  rt_reflection_params base;
+  if (reflection_pbr_params_error(params, &base) || material_table_error(table) || !lights || nlights < 1 ||
+      nlights > (uint32_t)rt::kMaxLights || H == 0 ||
+      (n && (!rays || !hits || !hit_normal || !hit_group || !hit_inst || !occluded || !valid || !py || !radiance_out)))
+    return RT_E_INVALID;
+  rt::ReflectionPbrParams pp = {};
+  reflection_pbr_of(params, table, reinterpret_cast<const rt::LightRec*>(lights), nlights, pp);
+  const uint32_t S = params->samples;
+  const bool shadow_models = (pp.flags & rt::kReflectShadowModels) != 0u;
+  const float fheight = (float)H;
+  for (uint32_t i = 0; i < n; ++i) {
+    float* out = radiance_out + 4 * (size_t)i;
+    if (lit_out) std::memset(lit_out + (size_t)i * S * nlights, 0, (size_t)S * nlights);
+    if (!valid[i]) {
+      out[0] = out[1] = out[2] = out[3] = 0.0f;
+      continue;
+    }
+    const rt::V3 sky = rt::reflection_miss_color(py[i], fheight);
+    rt::ReflectionSum sum = rt::reflection_sum_zero();
+    for (uint32_t k = 0; k < S; ++k) {
+      const size_t j = (size_t)i * S + k;
+      if (hits[4 * j + 3] == 0u) {
+        rt::reflection_sum_add(sum, sky, params->tmax);
+        continue;
+      }
+      const float* r = rays + 8 * j;
+      float t2;
+      std::memcpy(&t2, hits + 4 * j, sizeof(t2));
+      const rt::V3 ro = rt::v3(r[0], r[1], r[2]), d = rt::v3(r[4], r[5], r[6]);
+      const rt::V3 n2 = rt::v3(hit_normal[4 * j], hit_normal[4 * j + 1], hit_normal[4 * j + 2]);
+      const rt::V3 P2 = rt::add(ro, rt::muls(d, t2));
+      if (hit_group[j] == 2u) {
+        const rt::LightRec& L0 = pp.rp.lights[0];
+        if (lit_out) lit_out[j * nlights] = 1;
+        const float c = rt::reflection_plane_color(n2, rt::v3(L0.position[0], L0.position[1], L0.position[2]), P2,
+                                                   occluded[j * nlights] != 0);
+        rt::reflection_sum_add(sum, rt::v3(c, c, c), t2);
+        continue;
+      }
+      const uint32_t mi = rt::material_index(pp.instance_material, pp.ninstances, pp.nmaterials, hit_inst[j]);
+      rt::SurfaceSplit st = rt::surface_split_begin(pp.table[mi], P2, n2, ro);
+      for (uint32_t l = 0; l < nlights; ++l) {
+        const rt::LightRec& Lr = pp.rp.lights[l];
+        rt::V3 L;
+        float nl;
+        bool occ = false;
+        if (shadow_models &&
+            rt::shadow_lit(rt::neg(n2), rt::v3(Lr.position[0], Lr.position[1], Lr.position[2]), P2, L, nl)) {
+          if (lit_out) lit_out[j * nlights + l] = 1;
+          occ = occluded[j * nlights + l] != 0;
+        }
+        rt::surface_split_light(st, pp.table[mi], Lr, P2, n2, rt::reflection_model_factor(occ));
+      }
+      rt::reflection_sum_add(sum, rt::surface_split_end(st), t2);
     }
     rt::reflection_reduce(sum, S, out);
   }

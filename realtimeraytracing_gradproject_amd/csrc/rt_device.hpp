@@ -1402,6 +1402,120 @@ RT_HD void resolve_pbr_pixel(const ResolvePbr& r, uint32_t x, uint32_t y) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The PBR reflection pass (rt_dispatch_reflection_pbr): rt_dispatch_reflection's rays, reduction and
+// planes, with the reference's hit programs at each reflected hit: PlaneClosestHit for the plane group, ClosestHit's
+// surface colour with the hit instance's material for every other. Called by the PBR reflection kernels per lane and
+// by rt_host_reflection_rays_flags / rt_host_reflection_radiance_pbr per pixel; tests/reflection_pbr_reference.py
+// restates it in float64.
+// ------------------------------------------------------------------------------------------
+
+constexpr uint32_t kReflectFrameRay = 1u;      // RT_REFLECT_FRAME_RAY
+constexpr uint32_t kReflectShadowModels = 2u;  // RT_REFLECT_SHADOW_MODELS
+
+// rt_dispatch_reflection_pbr's launch: the reflection pass's, the flags, the instance map (may be null) and the table
+// by value, as in ResolvePbr.
+struct ReflectionPbrParams {
+  ReflectionParams rp;
+  uint32_t flags;
+  uint32_t nmaterials, ninstances;
+  const uint32_t* instance_material;
+  MaterialEntry table[kMaxMaterials];
+};
+
+// The mirror direction of the pass: rt_dispatch_reflection's (about the renormalised normal nn), or with
+// RT_REFLECT_FRAME_RAY the frame kernels' own (rt_trace.hip's reflection_ray: about the normal n as stored; its
+// rcp_exact normalise is the IEEE quotient's bits, as normalize's is).
+RT_HD V3 reflection_pbr_mirror(V3 D, V3 n, V3 nn, uint32_t flags) {
+  return reflection_mirror(D, (flags & kReflectFrameRay) ? n : nn);
+}
+
+// The table entry of instance `inst`: resolve_pbr_pixel's rule (no index reads outside either array).
+RT_HD uint32_t material_index(const uint32_t* instance_material, uint32_t ninstances, uint32_t nmaterials,
+                              uint32_t inst) {
+  uint32_t m = 0u;
+  if (instance_material && inst < ninstances) m = instance_material[inst];
+  return m < nmaterials ? m : 0u;
+}
+
+// PlaneClosestHit (Hit.hlsl:207-241) as rt_trace.hip's shade_ref evaluates it at P with the face normal n, light 0 at
+// lp and the answer of its one shadow ray (traced whether the plane faces the light or not).
+RT_HD float reflection_plane_color(V3 n, V3 lp, V3 P, bool occluded) {
+  const V3 ldir = normalize(sub(lp, P));
+  bool shadowed = dot(n, ldir) < 0.0f;
+  if (!shadowed) shadowed = occluded;
+  const float factor = shadowed ? 0.3f : 1.0f;
+  const float li = maxf(0.0f, dot(n, ldir));
+  return (1.0f * li) * factor;
+}
+
+// surface_pbr in three parts, for a caller that has work of its own between two lights (the trace kernels' light
+// loop is wave-uniform and walks a shadow packet per light): the pixel's invariants, one light's two terms scaled by
+// s, and the tone map. The operations are surface_pbr's, one for one and in its order; s == 1.0f leaves every product
+// as it was, so without shadow rays the bits are rt_trace.hip's surface_ref's.
+struct SurfaceSplit {
+  V3 N, V;
+  float ggx2, v4;
+  V3 cd, L0;
+};
+RT_HD SurfaceSplit surface_split_begin(const MaterialEntry& e, V3 P, V3 n, V3 cam) {
+  SurfaceSplit st;
+  st.N = neg(muls(n, rcp_exact(sqrtf(dot(n, n)))));
+  const V3 Vd = sub(cam, P);
+  st.V = muls(Vd, rcp_exact(sqrtf(dot(Vd, Vd))));
+  const float NdotV = maxf(dot(st.N, st.V), 0.0f);
+  st.ggx2 = NdotV * rcp_exact(NdotV * e.s.omk + e.s.k);
+  st.v4 = 4.0f * NdotV;
+  st.cd = v3(0.0f, 0.0f, 0.0f), st.L0 = v3(0.0f, 0.0f, 0.0f);
+  return st;
+}
+RT_HD void surface_split_light(SurfaceSplit& st, const MaterialEntry& e, const LightRec& Lr, V3 P, V3 n, float s) {
+  const V3 albedo = v3(e.m.albedo[0], e.m.albedo[1], e.m.albedo[2]);
+  const float a2 = e.s.a2, k = e.s.k, omk = e.s.omk;
+  const V3 F0 = v3(e.s.F0[0], e.s.F0[1], e.s.F0[2]);
+  const V3 kdA = v3(e.s.kdA[0], e.s.kdA[1], e.s.kdA[2]);
+  const V3 N = st.N, V = st.V;
+  const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+  const V3 lc = v3(Lr.color[0], Lr.color[1], Lr.color[2]);
+  const V3 dv = sub(lp, P);
+  const float dist = sqrtf(dot(dv, dv));
+  const V3 L = muls(dv, rcp_exact(dist));
+  // CalculateDirectLighting
+  const float ti = maxf(0.0f, dot(n, neg(L)) * Lr.intensity);
+  st.cd = add(st.cd, muls(mul(albedo, lc), ti * s));
+  // CalculatePBRShading
+  const V3 Hd = add(V, L);
+  const V3 H = muls(Hd, rcp_exact(sqrtf(dot(Hd, Hd))));
+  const float att = rcp_exact(maxf(dist * dist, 1.0f));
+  const V3 radiance = muls(lc, att);
+  const float x = clamp01(1.0f - maxf(dot(H, V), 0.0f));
+  const float x2 = x * x;
+  const float x5 = (x2 * x2) * x;
+  const V3 F = v3(F0.x + (1.0f - F0.x) * x5, F0.y + (1.0f - F0.y) * x5, F0.z + (1.0f - F0.z) * x5);
+  const float NdotH = maxf(dot(N, H), 0.0f);
+  const float NdotH2 = NdotH * NdotH;
+  float denom = NdotH2 * (a2 - 1.0f) + 1.0f;
+  denom = (kPiF * denom) * denom;
+  const float NDF = a2 * rcp_exact(denom);
+  const float NdotL = maxf(dot(N, L), 0.0f);
+  const float ggx1 = NdotL * rcp_exact(NdotL * omk + k);
+  const float G = ggx1 * st.ggx2;
+  const float sp = (NDF * G) * rcp_exact(st.v4 * NdotL + 0.0001f);
+  const V3 spec = muls(F, sp);
+  const V3 diff = v3((1.0f - F.x) * kdA.x, (1.0f - F.y) * kdA.y, (1.0f - F.z) * kdA.z);
+  st.L0 = add(st.L0, muls(mul(add(diff, spec), radiance), NdotL * s));
+}
+RT_HD V3 surface_split_end(const SurfaceSplit& st) {
+  V3 c = muls(st.L0, 0.2f);
+  c = v3(c.x * rcp_exact(c.x + 1.0f), c.y * rcp_exact(c.y + 1.0f), c.z * rcp_exact(c.z + 1.0f));
+  const float g = 1.0f / 2.2f;
+  return add(st.cd, v3(det_pow(c.x, g), det_pow(c.y, g), det_pow(c.z, g)));
+}
+
+// A model hit's factor of one light: the frame kernels' occl ? 0.3f : 1.0f where RT_REFLECT_SHADOW_MODELS traced a
+// shadow ray that found an occluder, 1.0f everywhere else (the reference's ClosestHit traces none).
+RT_HD float reflection_model_factor(bool occluded) { return occluded ? 0.3f : 1.0f; }
+
+// ------------------------------------------------------------------------------------------
 // Temporal upscaler (rt_upscale): the per-pixel arithmetic, called by the kernels of rt_upscale.hip per
 // lane and by rt_host_upscale per pixel. The AO filter's rule (above), less sqrtf; tests/upscale_reference.py restates
 // it in numpy.

@@ -225,6 +225,10 @@ hipError_t launch_shade_resolve_pbr(const ResolvePbr& r, hipStream_t stream);
 // kernels; params.radiance (and params.hits, when given) are written, params.gb's planes are not read.
 hipError_t launch_trace_reflection(const SceneView& scene, const ReflectionParams& params, const uint32_t* d_rows,
                                    unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
+// The PBR reflection pass (rt_dispatch_reflection_pbr): the same rule and grids on the PBR reflection
+// kernels; the material table rides in the kernel argument.
+hipError_t launch_trace_reflection_pbr(const SceneView& scene, const ReflectionPbrParams& params, const uint32_t* d_rows,
+                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
 // The composite (rt_reflection_composite): one launch, one pixel per lane; no scene, no scratch. Its per-pixel
 // arithmetic is rt_device.hpp's reflection_composite_pixel, shared with rt_host_reflection_composite.
 hipError_t launch_reflection_composite(const ReflComposite& r, hipStream_t stream);

@@ -2406,6 +2406,211 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection(SceneView sc, Refle
   if (STATS) flush_stats<false>(cnt, stats);
 }
 
+// ------------------------------------------------------------------------------------------
+// PBR reflection pass (rt_dispatch_reflection_pbr): the reflection kernels' launch shapes, primary walk,
+// ray generation, reduction and planes, with the reference's hit programs at each reflected hit (rt_device.hpp:
+// reflection_plane_color for the plane group, the split surface form with the hit instance's table entry for every
+// other) in place of the grey Lambert term. The two flags are wave-uniform run-time values of the kernel argument (an
+// SGPR test each: one select of the mirror's normal, one term of the shadow packets' lane mask), so the pass has the
+// reflection pass's four instantiations per kernel and no more. The table entry is read from the kernel-argument
+// segment at a per-lane index, as k_shade_resolve_pbr reads it.
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(SceneView) + sizeof(ReflectionPbrParams) + 2 * sizeof(void*) <= 4096,
+              "rt_dispatch_reflection_pbr's launch must fit the 4 KB kernel-argument segment");
+
+// The G-buffer-form normal of a reflected hit (ao_normal's expression) and its instance's hit group.
+__device__ __forceinline__ V3 reflection_pbr_normal(const SceneView& sc, const HitRec& hit, bool& plane) {
+  const HitInstance ir = load_hit_instance(sc, hit.inst);
+  plane = ir.hit_group == 2u;
+  return plane ? face_world_normal(ir, hit.prim) : interpolated_world_normal(ir, hit.prim, hit.u, hit.v);
+}
+
+// Packet schedule: k_trace_reflection_packet's, with one wave-uniform light loop per sample in which a light's any-hit
+// packet carries the plane hits' ray to light 0 and, with RT_REFLECT_SHADOW_MODELS, the model hits' rays to the lights
+// they face; the model lanes then add that light's two terms to their sums. A light no lane needs a ray for walks no
+// packet.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_REFLECT_SGPR_ATTR
+void k_trace_reflection_pbr_packet(SceneView sc, ReflectionPbrParams pp, const uint32_t* __restrict__ rows,
+                                   unsigned long long* __restrict__ stats) {
+  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
+  const ReflectionParams& rp = pp.rp;
+  const GbufParams& gb = rp.gb;
+  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
+  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
+  const bool inimg = x < gb.width && orow < gb.nrows;
+  uint32_t py = 0;
+  if (inimg) py = rows ? rows[orow] : orow;
+  V3 O, D;
+  gbuffer_ray(gb, x, py, O, D);
+  Counters cnt;
+  if (STATS && inimg) ++cnt.primary;
+  HitRec hit;
+  bool found;
+  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  bool need = false;
+  V3 m = v3(0.0f, 0.0f, 1.0f), nf = m, P = O;  // a dead lane's ray: finite, never traced
+  if (inimg && found) {
+    const V3 n = ao_normal(sc, hit);
+    if (ao_normal_valid(n)) {
+      need = true;
+      const V3 nn = normalize(n);
+      m = reflection_pbr_mirror(D, n, nn, pp.flags);
+      nf = ao_facing_normal(nn, D);
+      P = add(O, muls(D, hit.t));  // GetWorldHitPoint, the frame's expression
+    }
+  }
+  const bool shadow_models = (pp.flags & kReflectShadowModels) != 0u;  // uniform
+  const uint32_t base = reflection_base(x, py, rp.seed);
+  const uint32_t ns = wave_ballot(need) ? rp.samples : 0u;  // uniform
+  const V3 sky = reflection_miss_color(py, gb.fheight);
+  ReflectionSum sum = reflection_sum_zero();
+  uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t k = 0; k < ns; ++k) {
+    V3 d = reflection_direction(m, nf, rp.roughness, base, k);
+    V3 ro = reflection_origin(P, d);
+    if (STATS && need) ++cnt.refl;
+    HitRec h;
+    bool f;
+    trace_packet<false, STATS, 1, true, TT>(sc, &ro, &d, 0.001f, rp.tmax, &need, &f, &h, cnt);
+    const bool rh = need && f;
+    if (k == 0u && need) rec0 = reflection_record(f, h, rp.tmax);
+    V3 n2 = v3(0.0f, 0.0f, 1.0f), P2 = ro;  // a lane without a reflected hit: finite, shades nothing
+    bool plane = false;
+    uint32_t mi = 0u;
+    if (rh) {
+      n2 = reflection_pbr_normal(sc, h, plane);
+      P2 = add(ro, muls(d, h.t));
+      mi = material_index(pp.instance_material, pp.ninstances, pp.nmaterials, h.inst);
+    }
+    const bool model = rh && !plane, floor = rh && plane;
+    SurfaceSplit st{};
+    if (model) st = surface_split_begin(pp.table[mi], P2, n2, ro);
+    float cp = 0.0f;
+    for (uint32_t l = 0; l < rp.nlights; ++l) {
+      const LightRec& Lr = rp.lights[l];
+      const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+      V3 L;
+      float nl;
+      const bool lit = shadow_models && model && shadow_lit(neg(n2), lp, P2, L, nl);
+      const bool tr = lit || (floor && l == 0u);
+      bool occ = false;
+      if (wave_ballot(tr)) {  // uniform
+        V3 sd = v3(0.0f, 0.0f, 1.0f);  // a dead lane's ray: finite, never traced
+        if (tr) sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+        if (STATS && tr) ++cnt.shadow;
+        HitRec hs;
+        bool o;
+        trace_packet<true, STATS, 1, false, TT>(sc, &P2, &sd, rp.shadow_tmin, 100000.0f, &tr, &o, &hs, cnt);
+        occ = tr && o;
+      }
+      if (floor && l == 0u) cp = reflection_plane_color(n2, lp, P2, occ);
+      if (model) surface_split_light(st, pp.table[mi], Lr, P2, n2, reflection_model_factor(occ));
+    }
+    V3 col = sky;
+    if (floor) col = v3(cp, cp, cp);
+    if (model) col = surface_split_end(st);
+    if (need) reflection_sum_add(sum, col, rh ? h.t : rp.tmax);
+  }
+  if (inimg) {
+    const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (need) reflection_reduce(sum, rp.samples, out);
+    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
+    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+  }
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_reflection's, each lane shading
+// its own reflected hits.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, ReflectionPbrParams pp,
+                                                                 const uint32_t* __restrict__ rows,
+                                                                 unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const ReflectionParams& rp = pp.rp;
+  const GbufParams& gb = rp.gb;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  Counters cnt;
+  if (px < gb.width && orow < gb.nrows) {
+    const uint32_t py = rows ? rows[orow] : orow;
+    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+    V3 O, D;
+    gbuffer_ray(gb, px, py, O, D);
+    HitRec hit;
+    if (STATS) ++cnt.primary;
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+    if (trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt)) {
+      const V3 n = ao_normal(sc, hit);
+      if (ao_normal_valid(n)) {
+        const V3 nn = normalize(n);
+        const V3 m = reflection_pbr_mirror(D, n, nn, pp.flags);
+        const V3 nf = ao_facing_normal(nn, D);
+        const V3 P = add(O, muls(D, hit.t));
+        const bool shadow_models = (pp.flags & kReflectShadowModels) != 0u;
+        const uint32_t base = reflection_base(px, py, rp.seed);
+        const V3 sky = reflection_miss_color(py, gb.fheight);
+        ReflectionSum sum = reflection_sum_zero();
+        for (uint32_t k = 0; k < rp.samples; ++k) {
+          const V3 d = reflection_direction(m, nf, rp.roughness, base, k);
+          const V3 ro = reflection_origin(P, d);
+          if (STATS) ++cnt.refl;
+          HitRec h;
+          const bool f = trace<false, STATS, true, TT>(sc, ro, d, 0.001f, rp.tmax, h, stk, cnt);
+          if (k == 0u) rec0 = reflection_record(f, h, rp.tmax);
+          if (!f) {
+            reflection_sum_add(sum, sky, rp.tmax);
+            continue;
+          }
+          bool plane;
+          const V3 n2 = reflection_pbr_normal(sc, h, plane);
+          const V3 P2 = add(ro, muls(d, h.t));
+          if (plane) {
+            const LightRec& L0 = rp.lights[0];
+            const V3 lp = v3(L0.position[0], L0.position[1], L0.position[2]);
+            const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+            if (STATS) ++cnt.shadow;
+            HitRec hs;
+            const bool occ = trace<true, STATS, false, TT>(sc, P2, sd, rp.shadow_tmin, 100000.0f, hs, stk, cnt);
+            const float c = reflection_plane_color(n2, lp, P2, occ);
+            reflection_sum_add(sum, v3(c, c, c), h.t);
+            continue;
+          }
+          const uint32_t mi = material_index(pp.instance_material, pp.ninstances, pp.nmaterials, h.inst);
+          SurfaceSplit st = surface_split_begin(pp.table[mi], P2, n2, ro);
+          for (uint32_t l = 0; l < rp.nlights; ++l) {
+            const LightRec& Lr = rp.lights[l];
+            const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+            V3 L;
+            float nl;
+            bool occ = false;
+            if (shadow_models && shadow_lit(neg(n2), lp, P2, L, nl)) {
+              const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+              if (STATS) ++cnt.shadow;
+              HitRec hs;
+              occ = trace<true, STATS, false, TT>(sc, P2, sd, rp.shadow_tmin, 100000.0f, hs, stk, cnt);
+            }
+            surface_split_light(st, pp.table[mi], Lr, P2, n2, reflection_model_factor(occ));
+          }
+          reflection_sum_add(sum, surface_split_end(st), h.t);
+        }
+        reflection_reduce(sum, rp.samples, out);
+      }
+    }
+    const uint32_t o = orow * gb.width + px;
+    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
+    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
 // Un-interleaves the gathered strips (rank-major blocks; rank k holds strips s % nranks == k) into the RGBA8 frame.
 // in_bpp 3: the strips are RGB8 and the constant alpha 255 is restored here (RayGen.hlsl:42 writes float4(c, 1)).
 __global__ void k_assemble(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
@@ -3139,6 +3344,26 @@ hipError_t launch_trace_reflection(const SceneView& sc, const ReflectionParams& 
         else
           hipLaunchKernelGGL((k_trace_reflection_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, rp,
                              d_rows, d_stats);
+      },
+      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
+  return hipGetLastError();
+}
+
+// The PBR reflection pass: launch_trace_reflection's schedule rule, grids and compile-time choices, on the PBR
+// reflection kernels.
+hipError_t launch_trace_reflection_pbr(const SceneView& sc, const ReflectionPbrParams& pp, const uint32_t* d_rows,
+                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
+  const bool packet = gbuffer_packet(sc, schedule);
+  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
+  const dim3 grid((pp.rp.gb.width + tw - 1) / tw, (pp.rp.gb.nrows + th - 1) / th);
+  lift(
+      [&](auto S, auto T) {
+        if (!packet)
+          hipLaunchKernelGGL((k_trace_reflection_pbr<S.value, T.value>), grid, dim3(kBlock),
+                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, pp, d_rows, d_stats);
+        else
+          hipLaunchKernelGGL((k_trace_reflection_pbr_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc,
+                             pp, d_rows, d_stats);
       },
       Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
   return hipGetLastError();
