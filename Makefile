@@ -154,87 +154,45 @@ $(ASAN)/liboracle.so: oracle/rt_oracle.c oracle/rt_raster_oracle.c oracle/rt_ora
 $(ASAN)/obj_ingest_fuzz: tools/obj_ingest_fuzz.cpp $(ASAN)/rt_host.o | $(ASAN)
 	g++ -O1 -g -std=c++17 $(SANFLAGS) -o $@ $^
 
-# a standalone driver of rt_host_ao_rays (rt_api.cpp: it needs the HIP compiler, so its HOST side is compiled with
-# clang's sanitizers and the program linked by hipcc; no Python in the process, no GPU call; CPU only):
-#   make asan-ao && build/asan/ao_rays_check
+# Standalone drivers of rt_api.cpp's host twins (tools/NAME_asan.cpp -> build/asan/NAME_check). rt_api.cpp needs the
+# HIP compiler, so its HOST side is compiled with clang's sanitizers and the program linked by hipcc; no Python in the
+# process, no GPU call; CPU only:   make asan-ao && build/asan/ao_rays_check
+#   asan-ao              rt_host_ao_rays
+#   asan-denoise         the AO filter's host twins (rt_host_denoise_guide, rt_host_ao_accumulate, rt_host_ao_atrous:
+#                        stencils with edge handling on exact-size heap blocks)
+#   asan-upscale         the upscaler's host twin and the jitter helpers (rt_host_upscale, rt_camera_jitter,
+#                        rt_jitter_halton)
+#   asan-shadow          the soft-shadow host twins (rt_host_shadow_rays, rt_host_shade_resolve: per-light, per-sample
+#                        and strided-plane indexing on exact-size heap blocks)
+#   asan-reflection      the reflection host twins (rt_host_reflection_rays, rt_host_reflection_radiance,
+#                        rt_host_reflection_composite: per-sample and per-light indexing on exact-size heap blocks)
+#   asan-materials       the PBR resolve's host twin (rt_host_shade_resolve_pbr: the material table and the instance
+#                        map's two range checks, every optional plane given and NULL, on exact-size heap blocks)
+#   asan-reflection-pbr  the PBR reflection pass's host twins (rt_host_reflection_rays_flags,
+#                        rt_host_reflection_radiance_pbr: per-sample, per-light and per-instance indexing, the material
+#                        table and the map's two range checks, on exact-size heap blocks)
+ASAN_CHECKS := asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials asan-reflection-pbr
 asan-ao: $(ASAN)/ao_rays_check
+asan-denoise: $(ASAN)/denoise_check
+asan-upscale: $(ASAN)/upscale_check
+asan-shadow: $(ASAN)/shadow_check
+asan-reflection: $(ASAN)/reflection_check
+asan-materials: $(ASAN)/materials_check
+asan-reflection-pbr: $(ASAN)/reflection_pbr_check
 
 $(ASAN)/rt_api.o: $(SRC)/rt_api.cpp $(HDRS) | $(ASAN)
 	$(HIPCC) $(HIPFLAGS) -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -c $< -o $@
 
-$(ASAN)/ao_rays_asan.o: tools/ao_rays_asan.cpp include/rt_api.h | $(ASAN)
-	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
-
 ASAN_API_OBJS := $(ASAN)/rt_api.o $(BUILD)/rt_comm.o $(BUILD)/rt_host.o $(BUILD)/rt_lbvh.o $(BUILD)/rt_trace.o $(BUILD)/rt_raster.o \
                  $(BUILD)/rt_denoise.o $(BUILD)/rt_upscale.o
-$(ASAN)/ao_rays_check: $(ASAN)/ao_rays_asan.o $(ASAN_API_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
-# the same for the AO filter's host twins (rt_host_denoise_guide, rt_host_ao_accumulate, rt_host_ao_atrous: stencils
-# with edge handling on exact-size heap blocks):
-#   make asan-denoise && build/asan/denoise_check
-asan-denoise: $(ASAN)/denoise_check
-
-$(ASAN)/denoise_asan.o: tools/denoise_asan.cpp include/rt_api.h | $(ASAN)
+$(ASAN)/%_asan.o: tools/%_asan.cpp include/rt_api.h | $(ASAN)
 	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
 
-$(ASAN)/denoise_check: $(ASAN)/denoise_asan.o $(ASAN_API_OBJS)
+$(ASAN)/%_check: $(ASAN)/%_asan.o $(ASAN_API_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
 
-# the same for the upscaler's host twin and the jitter helpers (rt_host_upscale, rt_camera_jitter, rt_jitter_halton):
-#   make asan-upscale && build/asan/upscale_check
-asan-upscale: $(ASAN)/upscale_check
-
-$(ASAN)/upscale_asan.o: tools/upscale_asan.cpp include/rt_api.h | $(ASAN)
-	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
-
-$(ASAN)/upscale_check: $(ASAN)/upscale_asan.o $(ASAN_API_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
-
-# the same for the soft-shadow host twins (rt_host_shadow_rays, rt_host_shade_resolve: per-light, per-sample and
-# strided-plane indexing on exact-size heap blocks):
-#   make asan-shadow && build/asan/shadow_check
-asan-shadow: $(ASAN)/shadow_check
-
-$(ASAN)/shadow_asan.o: tools/shadow_asan.cpp include/rt_api.h | $(ASAN)
-	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
-
-$(ASAN)/shadow_check: $(ASAN)/shadow_asan.o $(ASAN_API_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
-
-# the same for the reflection host twins (rt_host_reflection_rays, rt_host_reflection_radiance,
-# rt_host_reflection_composite: per-sample and per-light indexing on exact-size heap blocks):
-#   make asan-reflection && build/asan/reflection_check
-asan-reflection: $(ASAN)/reflection_check
-
-$(ASAN)/reflection_asan.o: tools/reflection_asan.cpp include/rt_api.h | $(ASAN)
-	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
-
-$(ASAN)/reflection_check: $(ASAN)/reflection_asan.o $(ASAN_API_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
-
-# the same for the PBR resolve's host twin (rt_host_shade_resolve_pbr: the material table and the instance map's
-# two range checks, every optional plane given and NULL, on exact-size heap blocks):
-#   make asan-materials && build/asan/materials_check
-asan-materials: $(ASAN)/materials_check
-
-$(ASAN)/materials_asan.o: tools/materials_asan.cpp include/rt_api.h | $(ASAN)
-	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
-
-$(ASAN)/materials_check: $(ASAN)/materials_asan.o $(ASAN_API_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
-
-# the same for the PBR reflection pass's host twins (rt_host_reflection_rays_flags, rt_host_reflection_radiance_pbr:
-# per-sample, per-light and per-instance indexing, the material table and the map's two range checks, on exact-size
-# heap blocks):
-#   make asan-reflection-pbr && build/asan/reflection_pbr_check
-asan-reflection-pbr: $(ASAN)/reflection_pbr_check
-
-$(ASAN)/reflection_pbr_asan.o: tools/reflection_pbr_asan.cpp include/rt_api.h | $(ASAN)
-	$(ROCM)/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $< -o $@
-
-$(ASAN)/reflection_pbr_check: $(ASAN)/reflection_pbr_asan.o $(ASAN_API_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o $@ $^ -ldl -Wl,-rpath,$(ROCM)/lib
+.PRECIOUS: $(ASAN)/%_asan.o
 
 $(ASAN):
 	mkdir -p $@
@@ -242,5 +200,4 @@ $(ASAN):
 clean:
 	rm -rf $(BUILD) $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VDIR)
 
-.PHONY: all clean ref asan asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials \
-        asan-reflection-pbr
+.PHONY: all clean ref asan $(ASAN_CHECKS)

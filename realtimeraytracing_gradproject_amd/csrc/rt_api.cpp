@@ -2054,12 +2054,13 @@ static void grid_pass_frame(rt_ctx* c, uint32_t W, uint32_t H, uint32_t nrows, r
 }
 
 // ... and what every such pass does once its checks are through: the pixel-count limit, grid_pass_frame, the row
-// list's and the overflow stack's slots, launch(scene view, device rows, stream) -> hipError_t, the launch record and
-// the host-side counters.
-using GridLaunch = std::function<hipError_t(const rt::SceneView&, const uint32_t*, hipStream_t)>;
+// list's and the overflow stack's slots, launch_grid_pass of p (the pass's parameter structure, which picks the
+// kernels; gb: the GbufParams inside it), the launch record and the host-side counters. A template cannot have C
+// linkage, and it stands here, next to the statics of this extern "C" region that it uses: hence the linkage block.
+extern "C++" {
+template <typename P>
 static rt_status grid_pass_launch(rt_ctx* c, const std::string& fn, uint32_t W, uint32_t H, const uint32_t* rows,
-                                  uint32_t nrows, void* stream, rt::GbufParams& gb, const char* what,
-                                  const GridLaunch& launch) {
+                                  uint32_t nrows, void* stream, const P& p, rt::GbufParams& gb, const char* what) {
   // the kernels index a plane's entries with 32 bits, as the frame kernels index their pixels
   if ((uint64_t)nrows * W >= 0xffffffffull) return fail(c, RT_E_UNSUPPORTED, fn + ": more than 2^32 pixels");
   (void)hipSetDevice(c->device);
@@ -2073,13 +2074,15 @@ static rt_status grid_pass_launch(rt_ctx* c, const std::string& fn, uint32_t W, 
   // the per-lane kernel's overflow stack: 16 x 16 pixel workgroups
   const size_t lanes = rt::gbuffer_packet(L.sv, c->schedule) ? 0 : (size_t)((W + 15) / 16) * ((nrows + 15) / 16) * 256;
   if ((st = L.take_overflow_and_order(lanes)) != RT_OK) return st;
-  if ((st = L.finish(launch(L.sv, d_rows, L.s), what)) != RT_OK) return st;
+  const hipError_t e = rt::launch_grid_pass(L.sv, p, d_rows, c->d_stats, c->stats_on, c->schedule, L.s);
+  if ((st = L.finish(e, what)) != RT_OK) return st;
   if (c->stats_on) {
     c->dispatches += 1;
     c->pixels += (uint64_t)W * nrows;
   }
   return RT_OK;
 }
+}  // extern "C++"
 
 // The checks of a launch that writes G-buffer planes (fn names the entry point in the messages; *nrows becomes H
 // without a row list), and its planes, cameras and motion records into mp.
@@ -2117,12 +2120,8 @@ static rt_status gbuffer_dispatch(rt_ctx_t c, const std::string& fn, bool motion
   rt::GbufParams& gb = mp.gb;
   const rt_status st = gbuffer_params(c, fn, W, H, rows, &nrows, out, prev_cb, mp);
   if (st != RT_OK) return st;
-  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, gb, "G-buffer launch",
-                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
-                            return motion_kernels
-                                       ? rt::launch_trace_gbuffer(sv, mp, d_rows, c->d_stats, c->stats_on, c->schedule, s)
-                                       : rt::launch_trace_gbuffer(sv, gb, d_rows, c->d_stats, c->stats_on, c->schedule, s);
-                          });
+  return motion_kernels ? grid_pass_launch(c, fn, W, H, rows, nrows, stream, mp, gb, "G-buffer launch")
+                        : grid_pass_launch(c, fn, W, H, rows, nrows, stream, gb, gb, "G-buffer launch");
 }
 
 rt_status rt_dispatch_gbuffer(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
@@ -2190,10 +2189,7 @@ rt_status rt_dispatch_ao(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* row
   ap.radius = params->radius;
   ap.tmin = params->tmin;
   ap.ao = ao_dev;
-  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, ap.gb, "AO launch",
-                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
-                            return rt::launch_trace_ao(sv, ap, d_rows, c->d_stats, c->stats_on, c->schedule, s);
-                          });
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, ap, ap.gb, "AO launch");
 }
 
 // What is wrong with an rt_shadow_params, or null (rt_dispatch_shadow and rt_host_shadow_rays check alike).
@@ -2227,10 +2223,7 @@ rt_status rt_dispatch_shadow(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t*
   sp.tmin = params->tmin;
   sp.vis = vis_dev;
   sp.plane_stride = plane_stride ? plane_stride : (uint64_t)nrows * W;
-  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, sp.gb, "shadow launch",
-                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
-                            return rt::launch_trace_shadow(sv, sp, d_rows, c->d_stats, c->stats_on, c->schedule, s);
-                          });
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, sp, sp.gb, "shadow launch");
 }
 
 // What is wrong with an rt_reflection_params, or null (rt_dispatch_reflection and its host twins check alike).
@@ -2268,10 +2261,7 @@ rt_status rt_dispatch_reflection(rt_ctx_t c, uint32_t W, uint32_t H, const uint3
   rp.shadow_tmin = params->shadow_tmin;
   rp.radiance = out->radiance;
   rp.hits = out->hits;
-  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, rp.gb, "reflection launch",
-                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
-                            return rt::launch_trace_reflection(sv, rp, d_rows, c->d_stats, c->stats_on, c->schedule, s);
-                          });
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, rp, rp.gb, "reflection launch");
 }
 
 // ---- AO filter: the argument checks, shared by the device entry points and their host twins (align:
@@ -2711,11 +2701,7 @@ rt_status rt_dispatch_reflection_pbr(rt_ctx_t c, uint32_t W, uint32_t H, const u
   reflection_pbr_of(params, table, c->fp.lights, c->fp.nlights, pp);
   pp.rp.radiance = out->radiance;
   pp.rp.hits = out->hits;
-  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, pp.rp.gb, "PBR reflection launch",
-                          [&](const rt::SceneView& sv, const uint32_t* d_rows, hipStream_t s) {
-                            return rt::launch_trace_reflection_pbr(sv, pp, d_rows, c->d_stats, c->stats_on, c->schedule,
-                                                                   s);
-                          });
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, pp, pp.rp.gb, "PBR reflection launch");
 }
 
 // ---- Fresnel composite: the argument check shared by rt_reflection_composite and

@@ -191,24 +191,21 @@ hipError_t launch_trace_rays(const SceneView& scene, const float* rays, uint32_t
                              uint32_t* hits, float* uv, unsigned long long* d_stats, bool stats,
                              hipStream_t stream);
 
-// The G-buffer pass (rt_dispatch_gbuffer): the plain grid of the packet kernel, or (gbuffer_packet false: the
-// per-lane schedule, or trees too deep for the packet stack) the per-lane kernel over 16 x 16 pixel workgroups, whose
+// The passes on the G-buffer's pixel grid: the plain grid of the pass's packet kernel, or (gbuffer_packet false: the
+// per-lane schedule, or trees too deep for the packet stack) its per-lane kernel over 16 x 16 pixel workgroups, whose
 // scene view carries the launch's overflow stack. Counters when `stats`; the triangle test is sc.tri_test.
 bool gbuffer_packet(const SceneView& scene, int schedule);
-// P: GbufParams (rt_dispatch_gbuffer, the four-plane kernels) or GbufMotionParams (rt_dispatch_gbuffer_motion: the
-// same pass with the motion plane, the motion kernels on the same grids); both instantiated in rt_trace.hip
+// P, the launch's parameter structure, picks the kernels; instantiated in rt_trace.hip for
+//   GbufParams           rt_dispatch_gbuffer: the four planes of params are written
+//   GbufMotionParams     rt_dispatch_gbuffer_motion: the same pass with the motion plane
+//   AoParams             rt_dispatch_ao: params.ao is written
+//   ShadowParams         rt_dispatch_shadow (§3.13): params.vis's planes are written
+//   ReflectionParams     rt_dispatch_reflection (§3.14): params.radiance and, when given, params.hits are written
+//   ReflectionPbrParams  rt_dispatch_reflection_pbr (§3.16): likewise; the material table rides in the kernel argument
+// The last four read the camera and the frame size of their params.gb and none of its planes.
 template <typename P>
-hipError_t launch_trace_gbuffer(const SceneView& scene, const P& params, const uint32_t* d_rows,
-                                unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
-// The ambient-occlusion pass (rt_dispatch_ao): launch_trace_gbuffer's schedule rule (gbuffer_packet) and grids on
-// the AO kernels; params.ao is written, params.gb's planes are not read.
-hipError_t launch_trace_ao(const SceneView& scene, const AoParams& params, const uint32_t* d_rows,
-                           unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
-
-// The visibility pass (rt_dispatch_shadow): launch_trace_ao's schedule rule and grids on the shadow kernels;
-// params.vis's planes are written, params.gb's planes are not read.
-hipError_t launch_trace_shadow(const SceneView& scene, const ShadowParams& params, const uint32_t* d_rows,
-                               unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
+hipError_t launch_grid_pass(const SceneView& scene, const P& params, const uint32_t* d_rows,
+                            unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
 
 // --- Deferred resolve (rt_denoise.hip) ----------------------------------------
 // One launch, one pixel per lane; no scene, no scratch. Its per-pixel arithmetic is rt_device.hpp's resolve_pixel,
@@ -221,16 +218,9 @@ hipError_t launch_shade_resolve(const Resolve& r, hipStream_t stream);
 hipError_t launch_shade_resolve_pbr(const ResolvePbr& r, hipStream_t stream);
 
 // --- Deferred reflections (rt_trace.hip, rt_denoise.hip) -----------------------
-// The reflection pass (rt_dispatch_reflection): launch_trace_shadow's schedule rule and grids on the reflection
-// kernels; params.radiance (and params.hits, when given) are written, params.gb's planes are not read.
-hipError_t launch_trace_reflection(const SceneView& scene, const ReflectionParams& params, const uint32_t* d_rows,
-                                   unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
-// The PBR reflection pass (rt_dispatch_reflection_pbr): the same rule and grids on the PBR reflection
-// kernels; the material table rides in the kernel argument.
-hipError_t launch_trace_reflection_pbr(const SceneView& scene, const ReflectionPbrParams& params, const uint32_t* d_rows,
-                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
-// The composite (rt_reflection_composite): one launch, one pixel per lane; no scene, no scratch. Its per-pixel
-// arithmetic is rt_device.hpp's reflection_composite_pixel, shared with rt_host_reflection_composite.
+// The reflection passes are launch_grid_pass's, above. The composite (rt_reflection_composite): one launch, one pixel
+// per lane; no scene, no scratch. Its per-pixel arithmetic is rt_device.hpp's reflection_composite_pixel, shared with
+// rt_host_reflection_composite.
 hipError_t launch_reflection_composite(const ReflComposite& r, hipStream_t stream);
 
 // --- AO filter (rt_denoise.hip) -----------------------------------------------

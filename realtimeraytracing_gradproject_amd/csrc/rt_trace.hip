@@ -53,6 +53,7 @@ struct HitRec {
 };
 
 __device__ __forceinline__ V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
+__device__ __forceinline__ V3 light_pos(const LightRec& Lr) { return ld3(Lr.position); }
 
 // Scene data is read through explicit global (address space 1) pointers: pointers loaded from
 // memory (instance records) would otherwise become flat accesses, which wait on both vmcnt and
@@ -1139,7 +1140,7 @@ __device__ V3 surface_ref(const FrameParams& fp, V3 P, V3 n, V3 cam) {
   V3 cd = v3(0.0f, 0.0f, 0.0f), L0 = v3(0.0f, 0.0f, 0.0f);
   for (uint32_t l = 0; l < fp.nlights; ++l) {
     const LightRec& Lr = fp.lights[l];
-    const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+    const V3 lp = light_pos(Lr);
     const V3 lc = v3(Lr.color[0], Lr.color[1], Lr.color[2]);
     const V3 dv = sub(lp, P);
     const float dist = sqrtf(dot(dv, dv));
@@ -1235,7 +1236,7 @@ __device__ V3 shade_ref(const SceneView& sc, const FrameParams& fp, uint32_t py,
       const V3 P = add(ro, muls(rd, hit.t));  // GetWorldHitPoint, Common.hlsl:24-27
       if (ir.hit_group == 2u) {
         const LightRec& L0 = fp.lights[0];
-        const V3 ldir = normalize(sub(v3(L0.position[0], L0.position[1], L0.position[2]), P));
+        const V3 ldir = normalize(sub(light_pos(L0), P));
         const V3 n = face_world_normal(ir, hit.prim);
         bool shadowed = dot(n, ldir) < 0.0f;
         const bool occl = shadow_ray<STATS, TT>(sc, P, ldir, stk, cnt);
@@ -1308,7 +1309,7 @@ __device__ V3 shade_sample(const SceneView& sc, const FrameParams& fp, const Fra
   float c = 0.0f;
   for (uint32_t l = 0; l < fp.nlights; ++l) {
     const LightRec& Lr = fp.lights[l];
-    const V3 L = normalize(sub(v3(Lr.position[0], Lr.position[1], Lr.position[2]), P));
+    const V3 L = normalize(sub(light_pos(Lr), P));
     const float nl = dot(n, L);
     if (nl > 0.0f) {
       float factor = 1.0f;
@@ -1451,7 +1452,7 @@ __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, 
           P[r] = add(ro[r], muls(rd[r], hit[r].t));
           if (ir.hit_group == 2u) {
             const LightRec& L0 = fp.lights[0];
-            ldir[r] = normalize_x<true>(sub(v3(L0.position[0], L0.position[1], L0.position[2]), P[r]));
+            ldir[r] = normalize_x<true>(sub(light_pos(L0), P[r]));
             nf[r] = face_world_normal<true>(ir, hit[r].prim);
             need[r] = true;
             sd[r] = normalize_x<true>(ldir[r]);
@@ -1514,7 +1515,7 @@ __device__ void shade_sample_packet(const SceneView& sc, const FrameParams& fp, 
     float nl[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const V3 L = normalize(sub(v3(Lr.position[0], Lr.position[1], Lr.position[2]), P[r]));
+      const V3 L = normalize(sub(light_pos(Lr), P[r]));
       nl[r] = dot(n[r], L);
       need[r] = found[r] && nl[r] > 0.0f;
       sd[r] = normalize(L);
@@ -1581,6 +1582,14 @@ __device__ __forceinline__ void flush_stats(const Counters& c, unsigned long lon
 #define RT_TRACE_ATTR
 #endif
 
+// A lane's pixel in the plain kernels' 16 x 16 pixel workgroup (four waves, an 8 x 8 tile each): column px, entry
+// orow of the row list.
+__device__ __forceinline__ void plain_pixel(uint32_t& px, uint32_t& orow) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
+  orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+}
+
 template <int MODE, bool STATS, int TT = 0>
 __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void k_trace_frame(SceneView sc, FrameParams fp,
                                                         const uint32_t* __restrict__ rows,
@@ -1588,9 +1597,8 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void k_trace_frame(SceneView 
                                                         float4* __restrict__ rgba32f,
                                                         unsigned long long* __restrict__ stats) {
   extern __shared__ int s_stack[];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  uint32_t px, orow;
+  plain_pixel(px, orow);
   Counters cnt;
   if (px < fp.width && orow < fp.nrows) {
     const uint32_t py = rows ? rows[orow] : orow;
@@ -1625,9 +1633,8 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void k_trace_frame_gbuffer(Sc
                                                                 unsigned long long* __restrict__ stats,
                                                                 GbufMotionParams gbuf) {
   extern __shared__ int s_stack[];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  uint32_t px, orow;
+  plain_pixel(px, orow);
   Counters cnt;
   if (px < fp.width && orow < fp.nrows) {
     const uint32_t py = rows ? rows[orow] : orow;
@@ -1815,11 +1822,32 @@ __device__ __forceinline__ void gbuffer_ray(const GbufParams& gb, uint32_t px, u
   D = normalize(v3(dw[0], dw[1], dw[2]));  // CastDefaultRay
 }
 
+// The G-buffer-form normal of a hit, and whether its instance is the plane group: the model group's is
+// CalculateInterpolatedWorldNormal un-negated (EX false: its negation is what the Lambert kernels shade with, bit for
+// bit), the plane group's the face normal through the normal matrix (not renormalised).
+// LAMBERT: the form the Lambert kernels shade the hit with instead (shade_sample's expression: the model group's
+// negated).
+template <bool LAMBERT = false>
+__device__ __forceinline__ V3 hit_normal(const SceneView& sc, const HitRec& hit, bool& plane) {
+  const HitInstance ir = load_hit_instance(sc, hit.inst);
+  plane = ir.hit_group == 2u;
+  if (LAMBERT)
+    return plane ? face_world_normal(ir, hit.prim) : neg(interpolated_world_normal(ir, hit.prim, hit.u, hit.v));
+  return plane ? face_world_normal(ir, hit.prim) : interpolated_world_normal(ir, hit.prim, hit.u, hit.v);
+}
+__device__ __forceinline__ V3 ao_normal(const SceneView& sc, const HitRec& hit) {
+  bool plane;
+  return hit_normal(sc, hit, plane);
+}
+__device__ __forceinline__ V3 shadow_normal(const SceneView& sc, const HitRec& hit) {
+  bool plane;
+  return hit_normal<true>(sc, hit, plane);
+}
+
 // One pixel's planes: entry o of each plane the launch asked for (the pointers are kernel arguments: one uniform
 // branch per plane). hits / normal are one 16-B store per lane (an 8-pixel tile row is a full 128-B line), uv /
-// object one 8-B store. A miss: t = tmax, flag 0, ids ~0, zeros elsewhere, by the same stores. The model group's
-// normal is CalculateInterpolatedWorldNormal un-negated (EX false: its negation is what the Lambert kernels shade
-// with, bit for bit), the plane group's the face normal through the normal matrix (not renormalised).
+// object one 8-B store. A miss: t = tmax, flag 0, ids ~0, zeros elsewhere, by the same stores. The normal is
+// hit_normal's.
 __device__ __forceinline__ void gbuffer_store(const SceneView& sc, const GbufParams& gb, uint32_t o, bool f,
                                               const HitRec& hit) {
   if (gb.hits)
@@ -1893,31 +1921,72 @@ __host__ __device__ __forceinline__ const GbufParams& gbuf(const GbufParams& p) 
 __host__ __device__ __forceinline__ const GbufParams& gbuf(const GbufMotionParams& p) { return p.gb; }
 __device__ __forceinline__ void gbuffer_motion_store(const SceneView&, const GbufParams&, uint32_t, bool, const HitRec&,
                                                      V3, V3) {}
+// ... and the camera and frame size of the later passes on the same grid, whose structures begin with a GbufParams
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const AoParams& p) { return p.gb; }
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const ShadowParams& p) { return p.gb; }
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const ReflectionParams& p) { return p.gb; }
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const ReflectionPbrParams& p) { return p.rp.gb; }
+
+// The opening of every kernel on the G-buffer's grid, once per schedule: the lane's pixel, its camera ray and the
+// primary closest-hit walk. x: the pixel's column, orow: its entry of the row list (and of the planes: entry
+// orow * width + x, < 2^32 by rt_api.cpp's check), py: its row of the frame, inimg: the lane has a pixel.
+struct GridLane {
+  uint32_t x, orow, py;
+  bool inimg;
+};
 
 // Packet schedule: the frame kernel's one-sample layout (a wave = an 8 x 8 pixel tile, a workgroup RT_PACKET_WX x
 // RT_PACKET_WY waves, the plain grid), one closest-hit packet walk per wave. Rays outside the image or the row list
-// join the packet dead; only in-image pixels are stored.
+// join the packet dead (inimg false: a finite ray of pixel (x, 0), never stored). The opening statements of a packet
+// kernel's body, with sc, rows, STATS and TT in scope; it declares x, orow, py, inimg, O, D, cnt, hit and found there.
+// A macro, because the kernels must compile to the instructions they had with these lines written out: as a
+// forceinline function (GridLane returned or filled) the watertight kernels issue their multiplies in another order.
+#define RT_GRID_PACKET_PRIMARY(gb)                                                                                 \
+  stage_top_nodes<packet_block(1)>(sc); /* RT_LDS_TOP only */                                                      \
+  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);                                                         \
+  const uint32_t lane = threadIdx.x & 63u;                                                                         \
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); /* uniform: an SGPR */     \
+  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);                                         \
+  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);                                      \
+  const bool inimg = x < (gb).width && orow < (gb).nrows;                                                          \
+  uint32_t py = 0;                                                                                                 \
+  if (inimg) py = rows ? rows[orow] : orow;                                                                        \
+  V3 O, D;                                                                                                         \
+  gbuffer_ray(gb, x, py, O, D);                                                                                    \
+  Counters cnt;                                                                                                    \
+  if (STATS && inimg) ++cnt.primary;                                                                               \
+  HitRec hit;                                                                                                      \
+  bool found;                                                                                                      \
+  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt)
+
+// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack), in two steps, because the kernels keep
+// the test around their bodies (with it inside one helper the compiler lays the kernels out differently, and some
+// then take more VGPRs). grid_lane_pixel: k_trace_frame's indexing (plain_pixel); false: the lane has no pixel.
+// grid_lane_primary, for a lane with one: the row, the LDS stack and per-launch HBM overflow, the camera ray and the
+// closest-hit walk; true: a hit.
+__device__ __forceinline__ bool grid_lane_pixel(const GbufParams& gb, GridLane& g) {
+  plain_pixel(g.x, g.orow);
+  g.inimg = g.x < gb.width && g.orow < gb.nrows;
+  return g.inimg;
+}
+template <bool STATS, int TT>
+__device__ __forceinline__ bool grid_lane_primary(const SceneView& sc, const GbufParams& gb, const uint32_t* rows,
+                                                  int* s_stack, GridLane& g, LaneStack& stk, V3& O, V3& D, HitRec& hit,
+                                                  Counters& cnt) {
+  g.py = rows ? rows[g.orow] : g.orow;
+  stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+  gbuffer_ray(gb, g.x, g.py, O, D);
+  if (STATS) ++cnt.primary;
+  return trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
+}
+
+// The G-buffer packet kernels' body: the planes of the primary hit.
 template <bool STATS, int TT, typename P>
 __device__ __forceinline__ void gbuffer_packet_body(const SceneView& sc, const P& p,
                                                     const uint32_t* __restrict__ rows,
                                                     unsigned long long* __restrict__ stats) {
-  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
   const GbufParams& gb = gbuf(p);
-  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
-  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
-  const bool inimg = x < gb.width && orow < gb.nrows;
-  uint32_t py = 0;
-  if (inimg) py = rows ? rows[orow] : orow;
-  V3 O, D;
-  gbuffer_ray(gb, x, py, O, D);
-  Counters cnt;
-  if (STATS && inimg) ++cnt.primary;
-  HitRec hit;
-  bool found;
-  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  RT_GRID_PACKET_PRIMARY(gb);
   if (inimg) {
     const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
     gbuffer_store(sc, gb, o, found, hit);
@@ -1941,28 +2010,22 @@ void k_trace_gbuffer_motion_packet(SceneView sc, GbufMotionParams mp, const uint
   gbuffer_packet_body<STATS, TT>(sc, mp, rows, stats);
 }
 
-// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_frame's indexing, LDS stack
-// and per-launch HBM overflow.
+// Per-lane schedule: grid_lane_primary, then the same stores.
 template <bool STATS, int TT, typename P>
 __global__ __launch_bounds__(kBlock) void k_trace_gbuffer(SceneView sc, P p, const uint32_t* __restrict__ rows,
                                                           unsigned long long* __restrict__ stats) {
   extern __shared__ int s_stack[];
   const GbufParams& gb = gbuf(p);
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  GridLane g;
   Counters cnt;
-  if (px < gb.width && orow < gb.nrows) {
-    const uint32_t py = rows ? rows[orow] : orow;
-    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+  if (grid_lane_pixel(gb, g)) {
+    LaneStack stk;
     V3 O, D;
-    gbuffer_ray(gb, px, py, O, D);
     HitRec hit;
-    if (STATS) ++cnt.primary;
-    const bool f = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
-    const uint32_t o = orow * gb.width + px;
-    gbuffer_store(sc, gb, o, f, hit);
-    gbuffer_motion_store(sc, p, o, f, hit, O, D);
+    const bool found = grid_lane_primary<STATS, TT>(sc, gb, rows, s_stack, g, stk, O, D, hit, cnt);
+    const uint32_t o = g.orow * gb.width + g.x;
+    gbuffer_store(sc, gb, o, found, hit);
+    gbuffer_motion_store(sc, p, o, found, hit, O, D);
   }
   if (STATS) flush_stats<false>(cnt, stats);
 }
@@ -1976,12 +2039,6 @@ __global__ __launch_bounds__(kBlock) void k_trace_gbuffer(SceneView sc, P p, con
 // "Constant ambient light for now").
 // ------------------------------------------------------------------------------------------
 
-// The hit's normal as gbuffer_store computes it for the normal plane.
-__device__ __forceinline__ V3 ao_normal(const SceneView& sc, const HitRec& hit) {
-  const HitInstance ir = load_hit_instance(sc, hit.inst);
-  return ir.hit_group == 2u ? face_world_normal(ir, hit.prim) : interpolated_world_normal(ir, hit.prim, hit.u, hit.v);
-}
-
 // The packet kernel's SGPR budget: the plain kernels' cap (8 waves per SIMD; the two walks' uniform state then spills
 // 12 - 34 SGPRs to VGPR lanes, none to scratch), or with RT_AO_PLAIN_SGPRS=0 the compiler's own; DESIGN §3.9 has the
 // A/B of the two builds.
@@ -1994,31 +2051,16 @@ __device__ __forceinline__ V3 ao_normal(const SceneView& sc, const HitRec& hit) 
 #define RT_AO_SGPR_ATTR
 #endif
 
-// Packet schedule: gbuffer_packet_body's layout (a wave = an 8 x 8 pixel tile on the plain grid) and its closest-hit
-// walk, then a wave-uniform loop over the samples: every lane generates its ray k and the wave walks the 64 of them
-// as one any-hit packet; lanes that missed, or whose normal is invalid, join every packet dead (a wave with no live
-// lane skips the loop). One 4-B store per lane: an 8-pixel tile row is 32 contiguous bytes.
+// Packet schedule: RT_GRID_PACKET_PRIMARY, then a wave-uniform loop over the samples: every lane generates its ray k and
+// the wave walks the 64 of them as one any-hit packet; lanes that missed, or whose normal is invalid, join every
+// packet dead (a wave with no live lane skips the loop). One 4-B store per lane: an 8-pixel tile row is 32 contiguous
+// bytes.
 template <bool STATS, int TT>
 __global__ __launch_bounds__(packet_block(1)) RT_AO_SGPR_ATTR
 void k_trace_ao_packet(SceneView sc, AoParams ap, const uint32_t* __restrict__ rows,
                        unsigned long long* __restrict__ stats) {
-  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
   const GbufParams& gb = ap.gb;
-  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
-  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
-  const bool inimg = x < gb.width && orow < gb.nrows;
-  uint32_t py = 0;
-  if (inimg) py = rows ? rows[orow] : orow;
-  V3 O, D;
-  gbuffer_ray(gb, x, py, O, D);
-  Counters cnt;
-  if (STATS && inimg) ++cnt.primary;
-  HitRec hit;
-  bool found;
-  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  RT_GRID_PACKET_PRIMARY(gb);
   bool need = false;
   V3 nf = v3(0.0f, 0.0f, 1.0f), P = O;  // a dead lane's ray: finite, never traced
   if (inimg && found) {
@@ -2044,31 +2086,26 @@ void k_trace_ao_packet(SceneView sc, AoParams ap, const uint32_t* __restrict__ r
   if (STATS) flush_stats<true>(cnt, stats);
 }
 
-// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_gbuffer's indexing, LDS stack
-// and per-launch HBM overflow; each lane loops over its own samples.
+// Per-lane schedule: grid_lane_primary; each lane loops over its own samples.
 template <bool STATS, int TT>
 __global__ __launch_bounds__(kBlock) void k_trace_ao(SceneView sc, AoParams ap, const uint32_t* __restrict__ rows,
                                                      unsigned long long* __restrict__ stats) {
   extern __shared__ int s_stack[];
   const GbufParams& gb = ap.gb;
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  GridLane g;
   Counters cnt;
-  if (px < gb.width && orow < gb.nrows) {
-    const uint32_t py = rows ? rows[orow] : orow;
-    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+  if (grid_lane_pixel(gb, g)) {
+    LaneStack stk;
     V3 O, D;
-    gbuffer_ray(gb, px, py, O, D);
     HitRec hit;
-    if (STATS) ++cnt.primary;
+    const bool found = grid_lane_primary<STATS, TT>(sc, gb, rows, s_stack, g, stk, O, D, hit, cnt);
     float ao = 1.0f;
-    if (trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt)) {
+    if (found) {
       const V3 n = ao_normal(sc, hit);
       if (ao_normal_valid(n)) {
         const V3 nf = ao_facing_normal(n, D);
         const V3 P = add(O, muls(D, hit.t));
-        const uint32_t base = ao_base(px, py, ap.seed);
+        const uint32_t base = ao_base(g.x, g.py, ap.seed);
         uint32_t clear = 0;
         for (uint32_t k = 0; k < ap.samples; ++k) {
           const V3 d = ao_direction(nf, ao_sphere(base, k));
@@ -2079,7 +2116,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_ao(SceneView sc, AoParams ap, 
         ao = (float)clear / (float)ap.samples;
       }
     }
-    ap.ao[orow * gb.width + px] = ao;
+    ap.ao[g.orow * gb.width + g.x] = ao;
   }
   if (STATS) flush_stats<false>(cnt, stats);
 }
@@ -2094,12 +2131,6 @@ __global__ __launch_bounds__(kBlock) void k_trace_ao(SceneView sc, AoParams ap, 
 // light 0, Hit.hlsl:207-241).
 // ------------------------------------------------------------------------------------------
 
-// The normal the Lambert kernels shade the hit with: shade_sample's expression.
-__device__ __forceinline__ V3 shadow_normal(const SceneView& sc, const HitRec& hit) {
-  const HitInstance ir = load_hit_instance(sc, hit.inst);
-  return ir.hit_group == 2u ? face_world_normal(ir, hit.prim) : neg(interpolated_world_normal(ir, hit.prim, hit.u, hit.v));
-}
-
 // The packet kernel's SGPR budget: the plain kernels' cap (8 waves per SIMD; the walks' and the light loop's uniform
 // state then spills 20 - 47 SGPRs to VGPR lanes, none to scratch), or with RT_SHADOW_PLAIN_SGPRS=0 the compiler's own
 // (102 SGPRs, no spills, 7 waves), measured 1.05 - 1.06 x slower on C2 at 1080p and 1.01 - 1.03 x on REF at 720p;
@@ -2113,31 +2144,16 @@ __device__ __forceinline__ V3 shadow_normal(const SceneView& sc, const HitRec& h
 #define RT_SHADOW_SGPR_ATTR
 #endif
 
-// Packet schedule: k_trace_ao_packet's layout and closest-hit walk, then a wave-uniform loop over the lights and inside
-// it a wave-uniform loop over the samples: every lit lane generates its ray k and the wave walks the 64 of them as one
-// any-hit packet; lanes that missed or do not face the light join every packet dead, and a light no lane of the wave
-// faces skips its sample loop. One 4-B store per lane per light: an 8-pixel tile row is 32 contiguous bytes.
+// Packet schedule: RT_GRID_PACKET_PRIMARY, then a wave-uniform loop over the lights and inside it a wave-uniform loop over
+// the samples: every lit lane generates its ray k and the wave walks the 64 of them as one any-hit packet; lanes that
+// missed or do not face the light join every packet dead, and a light no lane of the wave faces skips its sample loop.
+// One 4-B store per lane per light: an 8-pixel tile row is 32 contiguous bytes.
 template <bool STATS, int TT>
 __global__ __launch_bounds__(packet_block(1)) RT_SHADOW_SGPR_ATTR
 void k_trace_shadow_packet(SceneView sc, ShadowParams sp, const uint32_t* __restrict__ rows,
                            unsigned long long* __restrict__ stats) {
-  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
   const GbufParams& gb = sp.gb;
-  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
-  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
-  const bool inimg = x < gb.width && orow < gb.nrows;
-  uint32_t py = 0;
-  if (inimg) py = rows ? rows[orow] : orow;
-  V3 O, D;
-  gbuffer_ray(gb, x, py, O, D);
-  Counters cnt;
-  if (STATS && inimg) ++cnt.primary;
-  HitRec hit;
-  bool found;
-  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  RT_GRID_PACKET_PRIMARY(gb);
   const bool live = inimg && found;
   V3 ns = v3(0.0f, 0.0f, 0.0f), P = O;  // a dead lane faces no light
   if (live) {
@@ -2147,7 +2163,7 @@ void k_trace_shadow_packet(SceneView sc, ShadowParams sp, const uint32_t* __rest
   float* out = sp.vis + (orow * gb.width + x);  // < 2^32 pixels (rt_api.cpp); dereferenced by in-image lanes only
   for (uint32_t l = 0; l < sp.nlights; ++l) {
     const LightRec& Lr = sp.lights[l];
-    const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+    const V3 lp = light_pos(Lr);
     V3 L;
     float nl;
     const bool need = shadow_lit(ns, lp, P, L, nl) && live;
@@ -2169,41 +2185,35 @@ void k_trace_shadow_packet(SceneView sc, ShadowParams sp, const uint32_t* __rest
   if (STATS) flush_stats<true>(cnt, stats);
 }
 
-// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_ao's indexing, LDS stack and
-// per-launch HBM overflow; each lane loops over its own lights and samples.
+// Per-lane schedule: grid_lane_primary; each lane loops over its own lights and samples.
 template <bool STATS, int TT>
 __global__ __launch_bounds__(kBlock) void k_trace_shadow(SceneView sc, ShadowParams sp, const uint32_t* __restrict__ rows,
                                                          unsigned long long* __restrict__ stats) {
   extern __shared__ int s_stack[];
   const GbufParams& gb = sp.gb;
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  GridLane g;
   Counters cnt;
-  if (px < gb.width && orow < gb.nrows) {
-    const uint32_t py = rows ? rows[orow] : orow;
-    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+  if (grid_lane_pixel(gb, g)) {
+    LaneStack stk;
     V3 O, D;
-    gbuffer_ray(gb, px, py, O, D);
     HitRec hit;
-    if (STATS) ++cnt.primary;
-    const bool found = trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt);
+    const bool found = grid_lane_primary<STATS, TT>(sc, gb, rows, s_stack, g, stk, O, D, hit, cnt);
     V3 ns = v3(0.0f, 0.0f, 0.0f), P = O;
     if (found) {
       ns = shadow_normal(sc, hit);
       P = add(O, muls(D, hit.t));
     }
-    float* out = sp.vis + (orow * gb.width + px);
+    float* out = sp.vis + (g.orow * gb.width + g.x);
     for (uint32_t l = 0; l < sp.nlights; ++l) {
       const LightRec& Lr = sp.lights[l];
-      const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+      const V3 lp = light_pos(Lr);
       float vis = 1.0f;
       if (found) {
         V3 L;
         float nl;
         vis = 0.0f;
         if (shadow_lit(ns, lp, P, L, nl)) {
-          const uint32_t base = shadow_base(px, py, sp.seed, l);
+          const uint32_t base = shadow_base(g.x, g.py, sp.seed, l);
           uint32_t clear = 0;
           for (uint32_t k = 0; k < sp.samples; ++k) {
             const V3 d = shadow_direction(lp, sp.light_radius, base, k, P);
@@ -2249,32 +2259,28 @@ __device__ __forceinline__ uint4 reflection_record(bool f, const HitRec& h, floa
 #define RT_REFLECT_SGPR_ATTR
 #endif
 
-// Packet schedule: k_trace_shadow_packet's layout and closest-hit walk, then a wave-uniform loop over the samples:
-// every valid lane generates its ray k and the wave walks the 64 of them as one closest-hit packet with back faces
-// culled; then the shadow kernel's wave-uniform light loop on the reflected hits, one any-hit packet per light that
-// some lane's reflected hit faces. Lanes that missed, or whose normal is invalid, join every packet dead (a wave with
-// no valid lane skips the loop). One 16-B store per lane and plane: an 8-pixel tile row is a full 128-B line.
+// The two reflection passes' kernels (this pass's and the PBR pass's, below) open with the grid's shared opening and
+// end with reflection_store; their set-up and sample loops are written out per pass and schedule (the passes differ
+// in the mirror direction and in how a reflected hit is shaded), which keeps each kernel's instructions what they
+// were before the opening was shared: DESIGN §3.7.
+// Entry o of the two planes: the reduced samples, or four zeros (out), and the record of sample 0. One 16-B store per
+// lane and plane: an 8-pixel tile row is a full 128-B line.
+__device__ __forceinline__ void reflection_store(const ReflectionParams& rp, uint32_t o, const float out[4],
+                                                 uint4 rec0) {
+  reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
+  if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+}
+
+// Packet schedule: RT_GRID_PACKET_PRIMARY, then a wave-uniform loop over the samples: every valid lane generates its
+// ray k and the wave walks the 64 of them as one closest-hit packet with back faces culled; then the shadow kernel's
+// wave-uniform light loop on the reflected hits, one any-hit packet per light that some lane's reflected hit faces.
+// Lanes that missed, or whose normal is invalid, join every packet dead (a wave with no valid lane skips the loop).
 template <bool STATS, int TT>
 __global__ __launch_bounds__(packet_block(1)) RT_REFLECT_SGPR_ATTR
 void k_trace_reflection_packet(SceneView sc, ReflectionParams rp, const uint32_t* __restrict__ rows,
                                unsigned long long* __restrict__ stats) {
-  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
   const GbufParams& gb = rp.gb;
-  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
-  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
-  const bool inimg = x < gb.width && orow < gb.nrows;
-  uint32_t py = 0;
-  if (inimg) py = rows ? rows[orow] : orow;
-  V3 O, D;
-  gbuffer_ray(gb, x, py, O, D);
-  Counters cnt;
-  if (STATS && inimg) ++cnt.primary;
-  HitRec hit;
-  bool found;
-  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  RT_GRID_PACKET_PRIMARY(gb);
   bool need = false;
   V3 m = v3(0.0f, 0.0f, 1.0f), nf = m, P = O;  // a dead lane's ray: finite, never traced
   if (inimg && found) {
@@ -2309,7 +2315,7 @@ void k_trace_reflection_packet(SceneView sc, ReflectionParams rp, const uint32_t
     float c = 0.0f;
     for (uint32_t l = 0; l < rp.nlights; ++l) {
       const LightRec& Lr = rp.lights[l];
-      const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+      const V3 lp = light_pos(Lr);
       V3 L;
       float nl;
       const bool lit = shadow_lit(n2, lp, P2, L, nl) && rh;
@@ -2330,42 +2336,36 @@ void k_trace_reflection_packet(SceneView sc, ReflectionParams rp, const uint32_t
     const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
     float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (need) reflection_reduce(sum, rp.samples, out);
-    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
-    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+    reflection_store(rp, o, out, rec0);
   }
   if (STATS) flush_stats<true>(cnt, stats);
 }
 
-// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_shadow's indexing, LDS stack and
-// per-launch HBM overflow; each lane loops over its own samples and, per reflected hit, over the lights.
+// Per-lane schedule: grid_lane_primary; each lane loops over its own samples and, per reflected hit, over the lights.
 template <bool STATS, int TT>
 __global__ __launch_bounds__(kBlock) void k_trace_reflection(SceneView sc, ReflectionParams rp,
                                                              const uint32_t* __restrict__ rows,
                                                              unsigned long long* __restrict__ stats) {
   extern __shared__ int s_stack[];
   const GbufParams& gb = rp.gb;
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  GridLane g;
   Counters cnt;
-  if (px < gb.width && orow < gb.nrows) {
-    const uint32_t py = rows ? rows[orow] : orow;
-    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+  if (grid_lane_pixel(gb, g)) {
+    LaneStack stk;
     V3 O, D;
-    gbuffer_ray(gb, px, py, O, D);
     HitRec hit;
-    if (STATS) ++cnt.primary;
+    const bool found = grid_lane_primary<STATS, TT>(sc, gb, rows, s_stack, g, stk, O, D, hit, cnt);
     float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
-    if (trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt)) {
+    if (found) {
       const V3 n = ao_normal(sc, hit);
       if (ao_normal_valid(n)) {
         const V3 nn = normalize(n);
         const V3 m = reflection_mirror(D, nn);
         const V3 nf = ao_facing_normal(nn, D);
         const V3 P = add(O, muls(D, hit.t));
-        const uint32_t base = reflection_base(px, py, rp.seed);
-        const V3 sky = reflection_miss_color(py, gb.fheight);
+        const uint32_t base = reflection_base(g.x, g.py, rp.seed);
+        const V3 sky = reflection_miss_color(g.py, gb.fheight);
         ReflectionSum sum = reflection_sum_zero();
         for (uint32_t k = 0; k < rp.samples; ++k) {
           const V3 d = reflection_direction(m, nf, rp.roughness, base, k);
@@ -2383,7 +2383,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection(SceneView sc, Refle
           float c = 0.0f;
           for (uint32_t l = 0; l < rp.nlights; ++l) {
             const LightRec& Lr = rp.lights[l];
-            const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+            const V3 lp = light_pos(Lr);
             V3 L;
             float nl;
             if (shadow_lit(n2, lp, P2, L, nl)) {
@@ -2399,9 +2399,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection(SceneView sc, Refle
         reflection_reduce(sum, rp.samples, out);
       }
     }
-    const uint32_t o = orow * gb.width + px;
-    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
-    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+    reflection_store(rp, g.orow * gb.width + g.x, out, rec0);
   }
   if (STATS) flush_stats<false>(cnt, stats);
 }
@@ -2418,39 +2416,17 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection(SceneView sc, Refle
 static_assert(sizeof(SceneView) + sizeof(ReflectionPbrParams) + 2 * sizeof(void*) <= 4096,
               "rt_dispatch_reflection_pbr's launch must fit the 4 KB kernel-argument segment");
 
-// The G-buffer-form normal of a reflected hit (ao_normal's expression) and its instance's hit group.
-__device__ __forceinline__ V3 reflection_pbr_normal(const SceneView& sc, const HitRec& hit, bool& plane) {
-  const HitInstance ir = load_hit_instance(sc, hit.inst);
-  plane = ir.hit_group == 2u;
-  return plane ? face_world_normal(ir, hit.prim) : interpolated_world_normal(ir, hit.prim, hit.u, hit.v);
-}
-
-// Packet schedule: k_trace_reflection_packet's, with one wave-uniform light loop per sample in which a light's any-hit
-// packet carries the plane hits' ray to light 0 and, with RT_REFLECT_SHADOW_MODELS, the model hits' rays to the lights
-// they face; the model lanes then add that light's two terms to their sums. A light no lane needs a ray for walks no
-// packet.
+// Packet schedule: k_trace_reflection_packet's set-up, sample packets and stores, with one wave-uniform light loop per
+// sample in which a light's any-hit packet carries the plane hits' ray to light 0 and, with RT_REFLECT_SHADOW_MODELS,
+// the model hits' rays to the lights they face; the model lanes then add that light's two terms to their sums. A light
+// no lane needs a ray for walks no packet.
 template <bool STATS, int TT>
 __global__ __launch_bounds__(packet_block(1)) RT_REFLECT_SGPR_ATTR
 void k_trace_reflection_pbr_packet(SceneView sc, ReflectionPbrParams pp, const uint32_t* __restrict__ rows,
                                    unsigned long long* __restrict__ stats) {
-  stage_top_nodes<packet_block(1)>(sc);  // RT_LDS_TOP only
   const ReflectionParams& rp = pp.rp;
   const GbufParams& gb = rp.gb;
-  constexpr uint32_t WX = packet_wx(1), WY = packet_wy(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: an SGPR
-  const uint32_t x = blockIdx.x * (8u * WX) + (w % WX) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * (8u * WY) + (w / WX) * 8u + (lane >> 3);
-  const bool inimg = x < gb.width && orow < gb.nrows;
-  uint32_t py = 0;
-  if (inimg) py = rows ? rows[orow] : orow;
-  V3 O, D;
-  gbuffer_ray(gb, x, py, O, D);
-  Counters cnt;
-  if (STATS && inimg) ++cnt.primary;
-  HitRec hit;
-  bool found;
-  trace_packet<false, STATS, 1, false, TT>(sc, &O, &D, 0.0f, 100000.0f, &inimg, &found, &hit, cnt);
+  RT_GRID_PACKET_PRIMARY(gb);
   bool need = false;
   V3 m = v3(0.0f, 0.0f, 1.0f), nf = m, P = O;  // a dead lane's ray: finite, never traced
   if (inimg && found) {
@@ -2482,7 +2458,7 @@ void k_trace_reflection_pbr_packet(SceneView sc, ReflectionPbrParams pp, const u
     bool plane = false;
     uint32_t mi = 0u;
     if (rh) {
-      n2 = reflection_pbr_normal(sc, h, plane);
+      n2 = hit_normal(sc, h, plane);
       P2 = add(ro, muls(d, h.t));
       mi = material_index(pp.instance_material, pp.ninstances, pp.nmaterials, h.inst);
     }
@@ -2492,7 +2468,7 @@ void k_trace_reflection_pbr_packet(SceneView sc, ReflectionPbrParams pp, const u
     float cp = 0.0f;
     for (uint32_t l = 0; l < rp.nlights; ++l) {
       const LightRec& Lr = rp.lights[l];
-      const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+      const V3 lp = light_pos(Lr);
       V3 L;
       float nl;
       const bool lit = shadow_models && model && shadow_lit(neg(n2), lp, P2, L, nl);
@@ -2519,14 +2495,13 @@ void k_trace_reflection_pbr_packet(SceneView sc, ReflectionPbrParams pp, const u
     const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
     float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (need) reflection_reduce(sum, rp.samples, out);
-    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
-    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+    reflection_store(rp, o, out, rec0);
   }
   if (STATS) flush_stats<true>(cnt, stats);
 }
 
-// Per-lane schedule (RT_SCHED_LANE, and trees too deep for the packet stack): k_trace_reflection's, each lane shading
-// its own reflected hits.
+// Per-lane schedule: k_trace_reflection's, each lane shading its own reflected hits: a plane hit with its one ray to
+// light 0, a model hit with the light loop.
 template <bool STATS, int TT>
 __global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, ReflectionPbrParams pp,
                                                                  const uint32_t* __restrict__ rows,
@@ -2534,20 +2509,16 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, R
   extern __shared__ int s_stack[];
   const ReflectionParams& rp = pp.rp;
   const GbufParams& gb = rp.gb;
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (w & 1u) * 8u + (lane & 7u);
-  const uint32_t orow = blockIdx.y * 16u + (w >> 1) * 8u + (lane >> 3);
+  GridLane g;
   Counters cnt;
-  if (px < gb.width && orow < gb.nrows) {
-    const uint32_t py = rows ? rows[orow] : orow;
-    const LaneStack stk = lane_stack(sc, s_stack, (blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x);
+  if (grid_lane_pixel(gb, g)) {
+    LaneStack stk;
     V3 O, D;
-    gbuffer_ray(gb, px, py, O, D);
     HitRec hit;
-    if (STATS) ++cnt.primary;
+    const bool found = grid_lane_primary<STATS, TT>(sc, gb, rows, s_stack, g, stk, O, D, hit, cnt);
     float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
-    if (trace<false, STATS, false, TT>(sc, O, D, 0.0f, 100000.0f, hit, stk, cnt)) {
+    if (found) {
       const V3 n = ao_normal(sc, hit);
       if (ao_normal_valid(n)) {
         const V3 nn = normalize(n);
@@ -2555,8 +2526,8 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, R
         const V3 nf = ao_facing_normal(nn, D);
         const V3 P = add(O, muls(D, hit.t));
         const bool shadow_models = (pp.flags & kReflectShadowModels) != 0u;
-        const uint32_t base = reflection_base(px, py, rp.seed);
-        const V3 sky = reflection_miss_color(py, gb.fheight);
+        const uint32_t base = reflection_base(g.x, g.py, rp.seed);
+        const V3 sky = reflection_miss_color(g.py, gb.fheight);
         ReflectionSum sum = reflection_sum_zero();
         for (uint32_t k = 0; k < rp.samples; ++k) {
           const V3 d = reflection_direction(m, nf, rp.roughness, base, k);
@@ -2570,11 +2541,11 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, R
             continue;
           }
           bool plane;
-          const V3 n2 = reflection_pbr_normal(sc, h, plane);
+          const V3 n2 = hit_normal(sc, h, plane);
           const V3 P2 = add(ro, muls(d, h.t));
           if (plane) {
             const LightRec& L0 = rp.lights[0];
-            const V3 lp = v3(L0.position[0], L0.position[1], L0.position[2]);
+            const V3 lp = light_pos(L0);
             const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
             if (STATS) ++cnt.shadow;
             HitRec hs;
@@ -2587,7 +2558,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, R
           SurfaceSplit st = surface_split_begin(pp.table[mi], P2, n2, ro);
           for (uint32_t l = 0; l < rp.nlights; ++l) {
             const LightRec& Lr = rp.lights[l];
-            const V3 lp = v3(Lr.position[0], Lr.position[1], Lr.position[2]);
+            const V3 lp = light_pos(Lr);
             V3 L;
             float nl;
             bool occ = false;
@@ -2604,9 +2575,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, R
         reflection_reduce(sum, rp.samples, out);
       }
     }
-    const uint32_t o = orow * gb.width + px;
-    reinterpret_cast<float4*>(rp.radiance)[o] = make_float4(out[0], out[1], out[2], out[3]);
-    if (rp.hits) reinterpret_cast<uint4*>(rp.hits)[o] = rec0;
+    reflection_store(rp, g.orow * gb.width + g.x, out, rec0);
   }
   if (STATS) flush_stats<false>(cnt, stats);
 }
@@ -3263,111 +3232,65 @@ bool gbuffer_packet(const SceneView& sc, int schedule) {
   return schedule == RT_SCHED_PACKET && sc.packet_cap < kPacketStack;  // packet_geometry's rule
 }
 
-// counters and the triangle test (sc.tri_test: the watertight instantiations on the vertex-form pool) are
-// compile-time choices, as for the frame kernels; P: the launch's parameter structure, which picks the kernels
+// The kernel of a pass on the G-buffer's grid: P, the launch's parameter structure, picks the pair, `packet` the
+// schedule; counters and the triangle test are compile-time choices, as for the frame kernels.
 template <typename P>
-hipError_t launch_trace_gbuffer(const SceneView& sc, const P& p, const uint32_t* d_rows, unsigned long long* d_stats,
-                                bool stats, int schedule, hipStream_t s) {
+using GridKernel = void (*)(SceneView, P, const uint32_t*, unsigned long long*);
+template <bool S, int T>
+GridKernel<GbufParams> grid_kernel(const GbufParams&, bool packet) {
+  return packet ? k_trace_gbuffer_packet<S, T> : k_trace_gbuffer<S, T, GbufParams>;
+}
+template <bool S, int T>
+GridKernel<GbufMotionParams> grid_kernel(const GbufMotionParams&, bool packet) {
+  return packet ? k_trace_gbuffer_motion_packet<S, T> : k_trace_gbuffer<S, T, GbufMotionParams>;
+}
+template <bool S, int T>
+GridKernel<AoParams> grid_kernel(const AoParams&, bool packet) {
+  return packet ? k_trace_ao_packet<S, T> : k_trace_ao<S, T>;
+}
+template <bool S, int T>
+GridKernel<ShadowParams> grid_kernel(const ShadowParams&, bool packet) {
+  return packet ? k_trace_shadow_packet<S, T> : k_trace_shadow<S, T>;
+}
+template <bool S, int T>
+GridKernel<ReflectionParams> grid_kernel(const ReflectionParams&, bool packet) {
+  return packet ? k_trace_reflection_packet<S, T> : k_trace_reflection<S, T>;
+}
+template <bool S, int T>
+GridKernel<ReflectionPbrParams> grid_kernel(const ReflectionPbrParams&, bool packet) {
+  return packet ? k_trace_reflection_pbr_packet<S, T> : k_trace_reflection_pbr<S, T>;
+}
+
+// The packet kernel's plain grid (a workgroup = RT_PACKET_WX x RT_PACKET_WY tiles of 8 x 8 pixels), or the per-lane
+// kernel's 16 x 16 pixel workgroups with their LDS stacks.
+template <typename P>
+hipError_t launch_grid_pass(const SceneView& sc, const P& p, const uint32_t* d_rows, unsigned long long* d_stats,
+                            bool stats, int schedule, hipStream_t s) {
   const GbufParams& gb = gbuf(p);
   const bool packet = gbuffer_packet(sc, schedule);
   const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
   const dim3 grid((gb.width + tw - 1) / tw, (gb.nrows + th - 1) / th);
+  const dim3 block(packet ? packet_block(1) : kBlock);
+  const size_t lds = packet ? 0 : (size_t)sc.lds_cap * kBlock * sizeof(int);
   lift(
       [&](auto S, auto T) {
-        if (!packet)
-          hipLaunchKernelGGL((k_trace_gbuffer<S.value, T.value, P>), grid, dim3(kBlock),
-                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, p, d_rows, d_stats);
-        else if constexpr (std::is_same_v<P, GbufMotionParams>)
-          hipLaunchKernelGGL((k_trace_gbuffer_motion_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, p,
-                             d_rows, d_stats);
-        else
-          hipLaunchKernelGGL((k_trace_gbuffer_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, p,
-                             d_rows, d_stats);
+        hipLaunchKernelGGL((grid_kernel<S.value, T.value>(p, packet)), grid, block, lds, s, sc, p, d_rows, d_stats);
       },
       Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
   return hipGetLastError();
 }
-template hipError_t launch_trace_gbuffer(const SceneView&, const GbufParams&, const uint32_t*, unsigned long long*, bool,
-                                         int, hipStream_t);
-template hipError_t launch_trace_gbuffer(const SceneView&, const GbufMotionParams&, const uint32_t*, unsigned long long*,
-                                         bool, int, hipStream_t);
-
-// The AO pass: launch_trace_gbuffer's schedule rule, grids and compile-time choices, on the AO kernels.
-hipError_t launch_trace_ao(const SceneView& sc, const AoParams& ap, const uint32_t* d_rows, unsigned long long* d_stats,
-                           bool stats, int schedule, hipStream_t s) {
-  const bool packet = gbuffer_packet(sc, schedule);
-  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
-  const dim3 grid((ap.gb.width + tw - 1) / tw, (ap.gb.nrows + th - 1) / th);
-  lift(
-      [&](auto S, auto T) {
-        if (!packet)
-          hipLaunchKernelGGL((k_trace_ao<S.value, T.value>), grid, dim3(kBlock),
-                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, ap, d_rows, d_stats);
-        else
-          hipLaunchKernelGGL((k_trace_ao_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, ap, d_rows,
-                             d_stats);
-      },
-      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
-  return hipGetLastError();
-}
-
-// The visibility pass: launch_trace_ao's schedule rule, grids and compile-time choices, on the shadow kernels.
-hipError_t launch_trace_shadow(const SceneView& sc, const ShadowParams& sp, const uint32_t* d_rows,
-                               unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
-  const bool packet = gbuffer_packet(sc, schedule);
-  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
-  const dim3 grid((sp.gb.width + tw - 1) / tw, (sp.gb.nrows + th - 1) / th);
-  lift(
-      [&](auto S, auto T) {
-        if (!packet)
-          hipLaunchKernelGGL((k_trace_shadow<S.value, T.value>), grid, dim3(kBlock),
-                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, sp, d_rows, d_stats);
-        else
-          hipLaunchKernelGGL((k_trace_shadow_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, sp,
-                             d_rows, d_stats);
-      },
-      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
-  return hipGetLastError();
-}
-
-// The reflection pass: launch_trace_shadow's schedule rule, grids and compile-time choices, on the reflection kernels.
-hipError_t launch_trace_reflection(const SceneView& sc, const ReflectionParams& rp, const uint32_t* d_rows,
-                                   unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
-  const bool packet = gbuffer_packet(sc, schedule);
-  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
-  const dim3 grid((rp.gb.width + tw - 1) / tw, (rp.gb.nrows + th - 1) / th);
-  lift(
-      [&](auto S, auto T) {
-        if (!packet)
-          hipLaunchKernelGGL((k_trace_reflection<S.value, T.value>), grid, dim3(kBlock),
-                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, rp, d_rows, d_stats);
-        else
-          hipLaunchKernelGGL((k_trace_reflection_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc, rp,
-                             d_rows, d_stats);
-      },
-      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
-  return hipGetLastError();
-}
-
-// The PBR reflection pass: launch_trace_reflection's schedule rule, grids and compile-time choices, on the PBR
-// reflection kernels.
-hipError_t launch_trace_reflection_pbr(const SceneView& sc, const ReflectionPbrParams& pp, const uint32_t* d_rows,
-                                       unsigned long long* d_stats, bool stats, int schedule, hipStream_t s) {
-  const bool packet = gbuffer_packet(sc, schedule);
-  const uint32_t tw = packet ? 8u * (uint32_t)packet_wx(1) : 16u, th = packet ? 8u * (uint32_t)packet_wy(1) : 16u;
-  const dim3 grid((pp.rp.gb.width + tw - 1) / tw, (pp.rp.gb.nrows + th - 1) / th);
-  lift(
-      [&](auto S, auto T) {
-        if (!packet)
-          hipLaunchKernelGGL((k_trace_reflection_pbr<S.value, T.value>), grid, dim3(kBlock),
-                             (size_t)sc.lds_cap * kBlock * sizeof(int), s, sc, pp, d_rows, d_stats);
-        else
-          hipLaunchKernelGGL((k_trace_reflection_pbr_packet<S.value, T.value>), grid, dim3(packet_block(1)), 0, s, sc,
-                             pp, d_rows, d_stats);
-      },
-      Flag{stats}, OneOf<0, 1>{sc.tri_test ? 1 : 0});
-  return hipGetLastError();
-}
+template hipError_t launch_grid_pass(const SceneView&, const GbufParams&, const uint32_t*, unsigned long long*, bool, int,
+                                     hipStream_t);
+template hipError_t launch_grid_pass(const SceneView&, const GbufMotionParams&, const uint32_t*, unsigned long long*,
+                                     bool, int, hipStream_t);
+template hipError_t launch_grid_pass(const SceneView&, const AoParams&, const uint32_t*, unsigned long long*, bool, int,
+                                     hipStream_t);
+template hipError_t launch_grid_pass(const SceneView&, const ShadowParams&, const uint32_t*, unsigned long long*, bool,
+                                     int, hipStream_t);
+template hipError_t launch_grid_pass(const SceneView&, const ReflectionParams&, const uint32_t*, unsigned long long*,
+                                     bool, int, hipStream_t);
+template hipError_t launch_grid_pass(const SceneView&, const ReflectionPbrParams&, const uint32_t*, unsigned long long*,
+                                     bool, int, hipStream_t);
 
 hipError_t launch_assemble_strips(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
                                   const void* gathered, void* out, hipStream_t s, uint32_t rank_stride_rows,
