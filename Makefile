@@ -45,14 +45,17 @@ HDRS      := include/rt_api.h $(SRC)/rt_device.hpp $(SRC)/rt_internal.hpp $(SRC)
 #   wavetimes RT_WAVE_TIMES=1: the per-wave clock records of tools/wave_times.py
 #   ldstop    RT_LDS_TOP=21: the largest BLAS's top two BFS levels staged in LDS per packet workgroup (the north
 #             star's "LDS node packets", measured slower than the scalar-cache node loads: DESIGN §9)
-#   popcullblas RT_POP_CULL_BLAS=1: the pop cull checks the BLAS entries as well as the TLAS entries (C2 -3.8 %, but
-#             C4 +1.0 ... +1.6 %: DESIGN §3.2), and
+#   popcullblas RT_POP_CULL_BLAS=1: the pop cull checks the BLAS entries as well as the TLAS entries, in every instance
+#             visit (C2 -3.8 %, but C4 +1.0 ... +1.6 %: DESIGN §3.2; RT_POP_CULL_BLAS=2 decides it per visit), and
 #   popcullstats RT_POP_CULL_BLAS=1 RT_POP_CULL_STATS=1: ... in the counting kernels too, so the cull shows in the
 #             device counters (both in tests/test_gpu_pop_cull.py)
+#   popcullvisit RT_POP_CULL_BLAS=2: the BLAS entries checked in the instance visits that switch it on at their root
+#             (C2 -0.9 % on top of the leaf's early exit, but C2F +2.3 %, C3 +1.6 %, C5 +1.2 %: DESIGN §3.2;
+#             tests/test_gpu_tri_exit.py)
 VDIR      := $(LIBDIR)/variants
 VSRCS     := $(SRC)/rt_api.cpp $(SRC)/rt_comm.cpp $(SRC)/rt_lbvh.hip $(SRC)/rt_trace.hip $(SRC)/rt_raster.hip \
              $(SRC)/rt_denoise.hip $(SRC)/rt_upscale.hip $(SRC)/rt_host.cpp $(HDRS) tools/build_variant.sh
-VARIANTS  := n1 n1root rays2 alt wavetimes ldstop popcullblas popcullstats
+VARIANTS  := n1 n1root rays2 alt wavetimes ldstop popcullblas popcullstats popcullvisit
 VLIBS     := $(foreach v,$(VARIANTS),$(VDIR)/$(v)/librtamd.so)
 DEFS_n1        := -DRT_SHADOW_COMPACT=1 -DRT_HYBRID_T=8
 DEFS_n1root    := -DRT_HYBRID_T=16 -DRT_HYBRID_ROOT=1
@@ -62,6 +65,7 @@ DEFS_wavetimes := -DRT_WAVE_TIMES=1
 DEFS_ldstop    := -DRT_LDS_TOP=21
 DEFS_popcullblas  := -DRT_POP_CULL_BLAS=1
 DEFS_popcullstats := -DRT_POP_CULL_BLAS=1 -DRT_POP_CULL_STATS=1
+DEFS_popcullvisit := -DRT_POP_CULL_BLAS=2
 
 all: $(LIB) $(APP) $(ORACLE) $(BASELINE) $(RCPCHECK) $(OCCPROBE) $(CLKPROBE) $(DSPPROBE) $(VLIBS)
 

@@ -38,10 +38,20 @@
 #ifndef RT_POP_CULL_STATS
 #define RT_POP_CULL_STATS 0
 #endif
-// The BLAS entries are checked too (the popcullblas variant): C2 -3.8 % instead of -1.9 % with the TLAS entries alone,
-// but C4 +1.0 ... +1.6 % and C5 +0.3 ... +0.5 % (the per-push minimum and LDS write where few pops are stale), so off.
+// The BLAS entries are checked too. 1: always (the popcullblas variant): C2 -3.8 % instead of -1.9 % with the TLAS
+// entries alone, but C4 +1.0 ... +1.6 % and C5 +0.3 ... +0.5 % (the per-push minimum and LDS write where few pops are
+// stale). 2: decided once per instance visit, at the BLAS root (on when some lane's ray starts inside or in front of
+// an entered child's box: its entry distance is tmin), and with the switch off a walk pays a uniform branch per push
+// and per pop instead of the minimum, the LDS write and the LDS read (rt_trace.hip packet_blas_walk).
 #ifndef RT_POP_CULL_BLAS
 #define RT_POP_CULL_BLAS 0
+#endif
+// The packet leaf's Moller-Trumbore test ends early, by one wave-uniform branch, when no lane that owns the triangle
+// can still accept it (rt_trace.hip packet_tri): after u, when no owning lane has 0 <= u <= 1 (C2 -5.0 %,
+// no config slower). 0: the whole test always. One ray per lane only. A second exit after v (none with v >= 0 and
+// u + v <= 1) was measured and not kept.
+#ifndef RT_TRI_EXIT
+#define RT_TRI_EXIT 1
 #endif
 #ifndef RT_POP_CULL_SLOTS
 #define RT_POP_CULL_SLOTS 8  // stack slots (from the bottom) whose entries are checked: 512 B of LDS each per workgroup
@@ -569,20 +579,35 @@ RT_HD bool moller_trumbore(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float face, float& t
 // Moller-Trumbore without early exits: every lane runs the same instructions (the wave-packet
 // path, where a divergent early exit costs exec-mask SALU work on the busiest pipe). Accepts
 // exactly what moller_trumbore accepts, with the same u, v, t.
-RT_HD bool moller_trumbore_flat(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float face, float& t, float& u, float& v) {
+//
+// In two stages, so the packet leaf can leave between them when no lane can accept (rt_trace.hip packet_tri,
+// RT_TRI_EXIT): mt_flat_u gives det, 1 / det, s and u; mt_flat_vt gives v, t and the acceptance from them. The
+// operations and their operands are those of the one-piece form, so u, v, t and the result are the same bits.
+struct MtFlat {
+  V3 s;
+  float det, inv;
+};
+RT_HD float mt_flat_u(V3 o, V3 d, V3 v0, V3 e1, V3 e2, MtFlat& m) {
   const V3 p = mt_cross(d, e2);
-  const float det = mt_dot(e1, p);
-  const float inv = mt_rcp(det);
-  const V3 s = sub(o, v0);
-  u = mt_dot(s, p) * inv;
-  const V3 q = mt_cross(s, e1);
-  v = mt_dot(d, q) * inv;
-  t = mt_dot(e2, q) * inv;
+  m.det = mt_dot(e1, p);
+  m.inv = mt_rcp(m.det);
+  m.s = sub(o, v0);
+  return mt_dot(m.s, p) * m.inv;
+}
+RT_HD bool mt_flat_vt(V3 d, V3 e1, V3 e2, float face, const MtFlat& m, float u, float& t, float& v) {
+  const V3 q = mt_cross(m.s, e1);
+  v = mt_dot(d, q) * m.inv;
+  t = mt_dot(e2, q) * m.inv;
   // Bitwise & (no exec-mask region), with two terms fewer than the early-exit form. u <= 1 is implied: v >= 0
   // (not NaN) makes u + v >= u exactly, and rounding is monotone, so fl(u + v) <= 1 gives u <= 1 (a NaN u fails
   // u + v <= 1). min(u, v) >= 0 is u >= 0 and v >= 0 for non-NaN u, v (-0 included); a NaN one (the min returns
   // the other) fails u + v <= 1 anyway (tests/test_acceptance.py).
-  return (det != 0.0f) & !culled(det, face) & (__builtin_fminf(u, v) >= 0.0f) & (u + v <= 1.0f);
+  return (m.det != 0.0f) & !culled(m.det, face) & (__builtin_fminf(u, v) >= 0.0f) & (u + v <= 1.0f);
+}
+RT_HD bool moller_trumbore_flat(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float face, float& t, float& u, float& v) {
+  MtFlat m;
+  u = mt_flat_u(o, d, v0, e1, e2, m);
+  return mt_flat_vt(d, e1, e2, face, m, u, t, v);
 }
 
 // ------------------------------------------------------------------------------------------

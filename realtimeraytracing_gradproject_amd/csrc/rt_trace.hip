@@ -420,10 +420,11 @@ template <bool ANY_HIT, bool STATS, int R>
 __device__ constexpr bool pop_cull() {
   return RT_POP_CULL_ON && !ANY_HIT && R == 1 && (!STATS || RT_POP_CULL_STATS);
 }
-// ... and of the BLAS entries among them (RT_POP_CULL_BLAS 0: the TLAS entries alone are checked)
+// ... and of the BLAS entries among them: RT_POP_CULL_BLAS, 0 where pop_cull() is false (0: the TLAS entries alone
+// are checked, 1: every BLAS walk's entries too, 2: those of the instance visits that switch it on at their root).
 template <bool ANY_HIT, bool STATS, int R>
-__device__ constexpr bool pop_cull_blas() {
-  return pop_cull<ANY_HIT, STATS, R>() && RT_POP_CULL_BLAS;
+__device__ constexpr int pop_cull_blas() {
+  return pop_cull<ANY_HIT, STATS, R>() ? RT_POP_CULL_BLAS : 0;
 }
 // the entry pushed to `slot` (uniform): this lane's entry distance
 __device__ __forceinline__ void pop_cull_put(int slot, float n) {
@@ -480,8 +481,22 @@ __device__ __forceinline__ void packet_tri(const RT_CONST TriRec* tpool, int ref
       else s = wt_shear_tri<-1>(A, B, C, ry.o[r], wt[r]);
       ok = wt_hit(s, wt[r], face, t, u, v);
     } else {
-      ok = moller_trumbore_flat(ry.o[r], ry.d[r], v3(ta.x, ta.y, ta.z), v3(tb.x, tb.y, tb.z), v3(tc.x, tc.y, tc.z),
-                                face, t, u, v);
+      const V3 e1 = v3(tb.x, tb.y, tb.z), e2 = v3(tc.x, tc.y, tc.z);
+      MtFlat m;
+      u = mt_flat_u(ry.o[r], ry.d[r], v3(ta.x, ta.y, ta.z), e1, e2, m);
+      // Early exit (RT_TRI_EXIT), one wave-uniform branch on an SGPR pair, no exec-mask region. `take` below needs
+      // `ok`, and `ok` needs fmin(u, v) >= 0 && u + v <= 1. That gives 0 <= u <= 1 for every float pair: v >= 0
+      // makes u + v >= u exactly and rounding is monotone, so fl(u + v) <= 1 gives u <= 1; u >= 0 holds for -0 too;
+      // a NaN u or v fails u + v <= 1 (rt_device.hpp mt_flat_vt, tests/test_tri_exit_acceptance.py). `take` also needs
+      // the lane in own[r]. So cand == 0 means no lane takes: no HitRec changes and, in an any-hit walk, no lane
+      // leaves the packet; the rest of the test is dead and is skipped. Lanes of own[r] that died since the slab
+      // ballot may stay in cand: the exit is only rarer for it. The counters above are already counted.
+      if (RT_TRI_EXIT && R == 1) {
+        // one ballot per compare, combined as masks: the ballot of an `&` of two compares goes through a VGPR
+        const uint64_t cand = wave_ballot(u >= 0.0f) & wave_ballot(u <= 1.0f) & own[r];
+        if (cand == 0) return;
+      }
+      ok = mt_flat_vt(ry.d[r], e1, e2, face, m, u, t, v);
     }
     HitRec& h = hit[r];
     // bitwise & / | (no short-circuit): no exec-mask branches around the compares (-2 %)
@@ -774,6 +789,9 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
   (void)lds_root;
   (void)lds_n;
   const int base = sp;
+  constexpr int kCullBlas = pop_cull_blas<ANY_HIT, STATS, R>();
+  int cullb = 2;  // RT_POP_CULL_BLAS 2: this visit's switch (uniform; 2 until the root node decides it)
+  (void)cullb;
 #if RT_HYBRID_T
   // the same pools for per-lane (vector) loads in lane_subtree
   const RT_GLOBAL char* gpool = (const RT_GLOBAL char*)pool;
@@ -860,6 +878,15 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
       }
     }
 #endif
+    // The per-visit switch of the BLAS pop cull (RT_POP_CULL_BLAS 2), decided at the root node, the first of the
+    // walk, from the keys its slab tests left: on when some lane enters a child at distance tmin, i.e. its ray starts
+    // inside or in front of that child's box (dead lanes and rejected children hold +inf). Every entry above `base`
+    // is pushed and popped within this walk, after the decision, so an entry is checked exactly when a distance was
+    // stored for it; the argument above pop_cull_put is unchanged.
+    if (kCullBlas == 2 && cullb == 2) {
+      const uint32_t m = min(min(vkey[0][0], vkey[0][1]), min(vkey[0][2], vkey[0][3]));
+      cullb = wave_ballot(__uint_as_float(m) == tmin) != 0 ? 1 : 0;
+    }
     const uint32_t imask = (uint32_t)ch[6];
     uint32_t tl = ent & ~imask;
     ent &= imask;
@@ -899,27 +926,19 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
         // keys elsewhere), lowest slot on ties, and that child's ref (first_inner + slot: internal
         // children sit in the lowest slots), packed as ref << 2 | slot; the lead lane's answer, one
         // readlane, is the packet's
-        uint32_t idx = 0, m1 = 0, m2 = 0;
+        uint32_t idx = 0, kc[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           uint32_t kk[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) kk[k] = key_if_entered(vkey[r][k], ent, k);
-          uint32_t m;
-          if (pop_cull_blas<ANY_HIT, STATS, R>()) {
-            // the lane's smallest and second smallest key (the second of the four is the median of the two pairs'
-            // minima and the smaller of their maxima)
-            const uint32_t lo01 = min(kk[0], kk[1]), hi01 = max(kk[0], kk[1]);
-            const uint32_t lo23 = min(kk[2], kk[3]), hi23 = max(kk[2], kk[3]);
-            m = min(lo01, lo23);
-            asm("v_med3_u32 %0, %1, %2, %3" : "=v"(m2) : "v"(lo01), "v"(lo23), "v"(min(hi01, hi23)));
-            m1 = m;
-          } else {
-            m = min(min(kk[0], kk[1]), min(kk[2], kk[3]));
-          }
+          const uint32_t m = min(min(kk[0], kk[1]), min(kk[2], kk[3]));
           const uint32_t ir = kk[0] == m ? 0u : kk[1] == m ? 1u : kk[2] == m ? 2u : 3u;
           const uint32_t pr = (((uint32_t)ch[5] + ir) << 2) | ir;
           idx = (r == 0 || pl.lead_r == (uint32_t)r) ? pr : idx;
+          if (r == 0)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) kc[k] = kk[k];
         }
         const uint32_t pk = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)pl.lead_l);
         ib = pk & 3u;
@@ -927,9 +946,17 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
         // Pop cull: the entry pushed below (two or more entered, so some child stays pending) goes to slot sp with
         // the lane's smallest key over the pending children, the entered ones but the packet's choice `ib`: the
         // lane's own smallest where its choice is another child (idx != pk: that child stays pending), else its
-        // second smallest. Unsigned order is float order on |n| and +inf; two keys at least are distances, so the
-        // all-ones keys of the children not entered are never stored.
-        if (pop_cull_blas<ANY_HIT, STATS, R>()) pop_cull_put(sp, __uint_as_float(idx == pk ? m2 : m1));
+        // second smallest (the second of the four is the median of the two pairs' minima and the smaller of their
+        // maxima). Unsigned order is float order on |n| and +inf; two keys at least are distances, so the all-ones
+        // keys of the children not entered are never stored. With the per-visit switch off (a uniform branch) the
+        // second minimum and the LDS write are skipped; the entry is then popped unchecked.
+        if (kCullBlas == 1 || (kCullBlas == 2 && cullb != 0)) {
+          const uint32_t lo01 = min(kc[0], kc[1]), hi01 = max(kc[0], kc[1]);
+          const uint32_t lo23 = min(kc[2], kc[3]), hi23 = max(kc[2], kc[3]);
+          uint32_t m2;
+          asm("v_med3_u32 %0, %1, %2, %3" : "=v"(m2) : "v"(lo01), "v"(lo23), "v"(min(hi01, hi23)));
+          pop_cull_put(sp, __uint_as_float(idx == pk ? m2 : min(lo01, lo23)));
+        }
       }
       if (STATS && (ent & ~(1u << ib)) && sp + 1 > cap)  // never: cap bounds the entries (one per level)
 #pragma unroll
@@ -941,7 +968,7 @@ __device__ __forceinline__ bool packet_blas_walk(const RT_CONST char* pool, cons
       // pending slots, and the whole entry is dropped at its first pop
     pop:
       if (sp == base) return true;
-      if (pop_cull_blas<ANY_HIT, STATS, R>() && pop_cull_dead(sp - 1, hit[0])) {
+      if ((kCullBlas == 1 || (kCullBlas == 2 && cullb != 0)) && pop_cull_dead(sp - 1, hit[0])) {
         --sp;
         goto pop;
       }
