@@ -40,7 +40,8 @@ extern "C" {
  * rt_reflection_composite_params, and rt_shade_resolve_pbr, its host twin rt_host_shade_resolve_pbr, rt_material_table,
  * rt_resolve_pbr_inputs and RT_MAX_MATERIALS, and rt_dispatch_reflection_pbr, its host twins
  * rt_host_reflection_rays_flags and rt_host_reflection_radiance_pbr, rt_reflection_pbr_params and the RT_REFLECT_*
- * flags. */
+ * flags, and rt_radiance_accumulate, rt_radiance_atrous, their host twins rt_host_radiance_accumulate and
+ * rt_host_radiance_atrous, rt_radiance_temporal_params and rt_radiance_atrous_params. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -684,6 +685,71 @@ typedef struct { uint32_t iterations; float depth_tol; float normal_cos; } rt_ao
 rt_status rt_ao_atrous(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
                        const float* guide, float* ao_out, float* tmp, void* hip_stream);
 
+/* ---- Radiance filter: the AO filter's pair for planes of 4-float entries ---------------------------
+ * A variance-guided (SVGF-style) temporal accumulation and a-trous blur for any W*H x 4 float plane; today that is
+ * rt_dispatch_reflection's radiance (mean colour, mean reflection distance). Everything the AO filter's preamble says
+ * holds unchanged: whole row-major W x H planes, asynchronous on hip_stream, a context only, no allocation, aliasing
+ * detected by pointer equality, nothing written on RT_E_INVALID, the same RT_E_UNSUPPORTED limits, the same
+ * arithmetic rules (so the device and the rt_host_radiance_* twins agree to the bit). The guide planes are
+ * rt_denoise_guide's.
+ *   lum(c) = (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2].
+ * Known limit: history is fetched by SURFACE motion, so a mirror reflection ghosts under camera parallax; reprojection
+ * by the filtered .w (the mean reflection distance, which both passes carry like a colour channel) is what this
+ * plane layout leaves room for. */
+
+/* As rt_ao_temporal_params. The Python binding's defaults: 32, 0.02, 0.9. */
+typedef struct { uint32_t max_history; float depth_tol; float normal_cos; } rt_radiance_temporal_params;
+
+/* Temporal accumulation with luminance moments. rad_*, moments_*, motion, guide_*: W*H x 4 floats, 16-byte aligned.
+ * rad_prev, moments_prev, guide_prev: the previous frame's rad_out, moments_out and guide, or all three NULL. A
+ * moments entry is (m1, m2, hist, var): the running means of lum and of lum squared, the history length, and the
+ * variance estimate rt_radiance_atrous reads. For pixel (x, y), i = y W + x, g = guide_cur[i], c = rad_cur[i],
+ * l = lum(c):
+ *   g.w == 0: rad_out = c, moments_out = (0, 0, 0, 0).
+ *   Reprojection: rt_ao_accumulate's, exactly: its conditions on m = motion[i] and fx, fy, its four taps in its order
+ *   with its weights, its skips and its three tests against guide_prev. An accepted tap adds sw += w; per channel k,
+ *   sc[k] += w * rad_prev[tap][k]; s1 += w * mp.x; s2 += w * mp.y; sh += w * mp.z with mp = moments_prev[tap].
+ *   sw >= 0.01f: n = minf(sh / sw + 1.0f, (float)max_history), a = 1.0f / n; per channel (.w, the distance, included)
+ *   p = sc[k] / sw, rad_out[k] = n == 1 ? c[k] : p + a * (c[k] - p); m1 likewise from s1 / sw and l, m2 likewise from
+ *   s2 / sw and l * l; hist = n. Otherwise (a disocclusion, or the first frame) rad_out = c, m1 = l, m2 = l * l,
+ *   hist = 1.
+ *   hist >= 4: var = maxf(0, m2 - m1 * m1). hist < 4: a spatial estimate from rad_cur: the taps (x + dx, y + dy), dx,
+ *   dy in -2..2, dy outer, both ascending; a tap outside the frame or with q = guide_cur[tap], q.w == 0 is skipped;
+ *   the centre weighs w = 1, another tap w = wz * wn with wz = maxf(0, 1 - fabsf(q.w - g.w) / (depth_tol * g.w)) and
+ *   wn = rt_ao_atrous's expression with this call's normal_cos; tw += w; t1 += w * lt; t2 += w * (lt * lt) with lt =
+ *   lum(rad_cur[tap]); M1 = t1 / tw, M2 = t2 / tw, var = maxf(0, M2 - M1 * M1) * (4.0f / hist). m1 and m2 stay the
+ *   temporal ones.
+ * RT_E_INVALID: an output equal to ANY input (rad_cur included: its neighbours are read, so there is no in-place form)
+ * or to the other output; a null or misaligned plane; only some of the prev planes; null or out-of-range params; W or
+ * H of 0. */
+rt_status rt_radiance_accumulate(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_radiance_temporal_params* params,
+                                 const float* rad_cur, const float* motion, const float* guide_cur,
+                                 const float* rad_prev, const float* moments_prev, const float* guide_prev,
+                                 float* rad_out, float* moments_out, void* hip_stream);
+
+/* iterations: 1..5; depth_tol, normal_cos: as rt_ao_atrous_params; sigma_l: finite and > 0, the luminance weight's
+ * width in standard deviations. The Python binding's defaults: 3, 0.02, 0.9, 4. */
+typedef struct { uint32_t iterations; float depth_tol; float normal_cos; float sigma_l; } rt_radiance_atrous_params;
+
+/* Variance-guided a-trous blur. rad_in, rad_out, tmp: W*H x 4 floats, 16-byte aligned; var_out, var_tmp: W*H floats;
+ * moments: rt_radiance_accumulate's moments_out, of which only .w is read (iteration 0's variance input, at stride 4);
+ * tmp and var_tmp may be NULL only when iterations == 1. Iteration k has step s = 1 << k, reads the previous
+ * iteration's colour and variance (the first: rad_in and moments.w; neither is ever written) and writes rad_out /
+ * var_out when iterations - 1 - k is even, else tmp / var_tmp. For pixel p = (x, y) with g = guide[p]:
+ *   g.w == 0 copies colour and variance.
+ *   vg, the prefiltered variance: the taps (x + dx s, y + dy s), dx, dy in -1..1, dy outer, both ascending, with the
+ *   weights {1/16, 1/8, 1/16; 1/8, 1/4, 1/8; 1/16, 1/8, 1/16}; the in-frame taps only (with or without a surface):
+ *   pw += w; pv += w * var[tap]; vg = pv / pw.
+ *   lden = sigma_l * sqrtf(vg) + 1e-4f. The 25 taps, k, and the skips are rt_ao_atrous's, and so are wz and wn;
+ *   wl = maxf(0, 1 - fabsf(lum(in[tap]) - lum(in[p])) / lden); e = (wz * wn) * wl; w = k * (e * e), and w = k at the
+ *   centre; sw += w; per channel sc[c] += w * in[tap][c]; sv += (w * w) * var[tap].
+ *   Colour out: sc[c] / sw; variance out: sv / (sw * sw).
+ * RT_E_INVALID: rt_ao_atrous's cases (any two of the seven pointers equal; a null plane, tmp and var_tmp only when
+ * iterations > 1; a misaligned plane; null or out-of-range params; W or H of 0) and a sigma_l not finite or <= 0. */
+rt_status rt_radiance_atrous(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_radiance_atrous_params* params,
+                             const float* rad_in, const float* moments, const float* guide, float* rad_out,
+                             float* var_out, float* tmp, float* var_tmp, void* hip_stream);
+
 /* ---- Temporal upscaler of the colour frame --------------------------------------------------------
  * rt_upscale reconstructs a W x H display frame from a jittered w x h render (rt_dispatch_rays' rgba32f_dev under a
  * camera from rt_camera_jitter), that render's motion plane (rt_gbuffer_motion.motion under the same camera) and its
@@ -1191,6 +1257,15 @@ rt_status rt_host_ao_accumulate(uint32_t W, uint32_t H, const rt_ao_temporal_par
                                 const float* hist_prev, const float* guide_prev, float* ao_out, float* hist_out);
 rt_status rt_host_ao_atrous(uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
                             const float* guide, float* ao_out, float* tmp);
+
+/* rt_radiance_accumulate and rt_radiance_atrous on host arrays, likewise. */
+rt_status rt_host_radiance_accumulate(uint32_t W, uint32_t H, const rt_radiance_temporal_params* params,
+                                      const float* rad_cur, const float* motion, const float* guide_cur,
+                                      const float* rad_prev, const float* moments_prev, const float* guide_prev,
+                                      float* rad_out, float* moments_out);
+rt_status rt_host_radiance_atrous(uint32_t W, uint32_t H, const rt_radiance_atrous_params* params,
+                                  const float* rad_in, const float* moments, const float* guide, float* rad_out,
+                                  float* var_out, float* tmp, float* var_tmp);
 
 /* rt_upscale on host arrays, likewise: the same arguments less the context and the stream, the same checks less the
  * 16-byte alignment (4 bytes will do, rgba8_out included), the same per-pixel function, so the same bits. */

@@ -158,6 +158,18 @@ class rt_ao_atrous_params(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
 
 
+class rt_radiance_temporal_params(ctypes.Structure):
+    """include/rt_api.h rt_radiance_temporal_params: rt_ao_temporal_params' fields, for rt_radiance_accumulate."""
+    _fields_ = [("max_history", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float)]
+
+
+class rt_radiance_atrous_params(ctypes.Structure):
+    """include/rt_api.h rt_radiance_atrous_params: iterations (1..5), depth_tol, normal_cos, sigma_l (> 0) of
+    rt_radiance_atrous."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("depth_tol", ctypes.c_float), ("normal_cos", ctypes.c_float),
+                ("sigma_l", ctypes.c_float)]
+
+
 class rt_upscale_params(ctypes.Structure):
     """include/rt_api.h rt_upscale_params: the two frames' jitters (render pixels), max_history (1..1024), depth_tol."""
     _fields_ = [("jitter_cur", ctypes.c_float * 2), ("jitter_prev", ctypes.c_float * 2),
@@ -234,6 +246,10 @@ SIGNATURES = [
     ("rt_ao_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P,
                               _P]),
     ("rt_ao_atrous", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P, _P]),
+    ("rt_radiance_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_radiance_temporal_params), _P, _P, _P, _P, _P,
+                                    _P, _P, _P, _P]),
+    ("rt_radiance_atrous", _I, [_P, _U32, _U32, ctypes.POINTER(rt_radiance_atrous_params), _P, _P, _P, _P, _P, _P, _P,
+                                _P]),
     ("rt_upscale", _I, [_P, _U32, _U32, _U32, _U32, ctypes.POINTER(rt_upscale_params), _P, _P, _P, _P, _P, _P, _P, _P,
                         _P]),
     ("rt_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _P]),
@@ -300,6 +316,10 @@ SIGNATURES = [
     ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
     ("rt_host_ao_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rt_host_ao_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P]),
+    ("rt_host_radiance_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_radiance_temporal_params), _P, _P, _P, _P, _P,
+                                         _P, _P, _P]),
+    ("rt_host_radiance_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_radiance_atrous_params), _P, _P, _P, _P, _P, _P,
+                                     _P]),
     ("rt_host_upscale", _I, [_U32, _U32, _U32, _U32, ctypes.POINTER(rt_upscale_params), _P, _P, _P, _P, _P, _P, _P,
                              _P]),
     ("rt_camera_jitter", _I, [_FP, _U32, _U32, ctypes.c_float, ctypes.c_float, _FP]),
@@ -883,6 +903,44 @@ def host_ao_atrous(width: int, height: int, ao_in, guide, iterations: int = 3, d
     if st != RT_OK:
         raise RtError(st, "rt_host_ao_atrous")
     return out
+
+
+def host_radiance_accumulate(width: int, height: int, rad_cur, motion, guide_cur, rad_prev=None, moments_prev=None,
+                             guide_prev=None, max_history: int = 32, depth_tol: float = 0.02,
+                             normal_cos: float = 0.9):
+    """rt_host_radiance_accumulate: the radiance filter's temporal pass on the host (no GPU). rad_cur, motion,
+    guide_cur: (width * height, 4); rad_prev, moments_prev, guide_prev: the previous frame's outputs and guide, or all
+    None (the first frame). Returns (rad_out, moments_out), (width * height, 4) float32 each; a moments entry is (m1,
+    m2, hist, var)."""
+    n = width * height
+    cur, mo, gc = _f32(rad_cur, 4 * n), _f32(motion, 4 * n), _f32(guide_cur, 4 * n)
+    rp = None if rad_prev is None else _f32(rad_prev, 4 * n)
+    mp = None if moments_prev is None else _f32(moments_prev, 4 * n)
+    gp = None if guide_prev is None else _f32(guide_prev, 4 * n)
+    p = rt_radiance_temporal_params(max_history, depth_tol, normal_cos)
+    rad, mom = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+    st = lib.rt_host_radiance_accumulate(width, height, ctypes.byref(p), _vp(cur), _vp(mo), _vp(gc), _vp(rp), _vp(mp),
+                                         _vp(gp), _vp(rad), _vp(mom))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_radiance_accumulate")
+    return rad, mom
+
+
+def host_radiance_atrous(width: int, height: int, rad_in, moments, guide, iterations: int = 3,
+                         depth_tol: float = 0.02, normal_cos: float = 0.9, sigma_l: float = 4.0):
+    """rt_host_radiance_atrous: the radiance filter's variance-guided a-trous blur on the host (no GPU). rad_in,
+    moments, guide: (width * height, 4); only moments[:, 3], the variance, is read. Returns (rad_out (width * height,
+    4), var_out width * height) float32."""
+    n = width * height
+    a, m, g = _f32(rad_in, 4 * n), _f32(moments, 4 * n), _f32(guide, 4 * n)
+    p = rt_radiance_atrous_params(iterations, depth_tol, normal_cos, sigma_l)
+    out, tmp = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+    var, vtmp = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    st = lib.rt_host_radiance_atrous(width, height, ctypes.byref(p), _vp(a), _vp(m), _vp(g), _vp(out), _vp(var),
+                                     _vp(tmp), _vp(vtmp))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_radiance_atrous")
+    return out, var
 
 
 def _upscale_params(jitter_cur, jitter_prev, max_history, depth_tol) -> rt_upscale_params:
@@ -1717,6 +1775,37 @@ class Context:
         self._check(self._lib.rt_ao_atrous(self._h, width, height, ctypes.byref(p), self._plane(m, "ao_in", ao_in, n),
                                            self._plane(m, "guide", guide, 4 * n), self._plane(m, "ao_out", ao_out, n),
                                            self._plane(m, "tmp", tmp, n), stream), "rt_ao_atrous")
+
+    def radiance_accumulate(self, width: int, height: int, rad_cur, motion, guide_cur, rad_out, moments_out,
+                            rad_prev=None, moments_prev=None, guide_prev=None, max_history: int = 32,
+                            depth_tol: float = 0.02, normal_cos: float = 0.9, stream: Optional[int] = None):
+        """rt_radiance_accumulate: ao_accumulate for a plane of 4-float entries (dispatch_reflection's radiance), all
+        four channels blended alike, with the luminance moments (m1, m2, hist, var) in moments_out: the variance
+        radiance_atrous reads. Every plane is width * height x 4 floats. rad_prev, moments_prev, guide_prev all None:
+        the first frame. No output may be an input (rad_cur's neighbours are read)."""
+        n, m = 4 * width * height, "radiance_accumulate"
+        p = rt_radiance_temporal_params(max_history, depth_tol, normal_cos)
+        self._check(self._lib.rt_radiance_accumulate(
+            self._h, width, height, ctypes.byref(p), self._plane(m, "rad_cur", rad_cur, n),
+            self._plane(m, "motion", motion, n), self._plane(m, "guide_cur", guide_cur, n),
+            self._plane(m, "rad_prev", rad_prev, n), self._plane(m, "moments_prev", moments_prev, n),
+            self._plane(m, "guide_prev", guide_prev, n), self._plane(m, "rad_out", rad_out, n),
+            self._plane(m, "moments_out", moments_out, n), stream), "rt_radiance_accumulate")
+
+    def radiance_atrous(self, width: int, height: int, rad_in, moments, guide, rad_out, var_out, tmp=None,
+                        var_tmp=None, iterations: int = 3, depth_tol: float = 0.02, normal_cos: float = 0.9,
+                        sigma_l: float = 4.0, stream: Optional[int] = None):
+        """rt_radiance_atrous: `iterations` (1..5) passes of the a-trous filter over a plane of 4-float entries, the
+        luminance weight scaled by the variance (moments' .w, filtered along with the colour); the result lands in
+        rad_out / var_out, rad_in and moments are not written; tmp (width * height x 4 floats) and var_tmp (width *
+        height floats) are needed from two iterations on."""
+        n, m = width * height, "radiance_atrous"
+        p = rt_radiance_atrous_params(iterations, depth_tol, normal_cos, sigma_l)
+        self._check(self._lib.rt_radiance_atrous(
+            self._h, width, height, ctypes.byref(p), self._plane(m, "rad_in", rad_in, 4 * n),
+            self._plane(m, "moments", moments, 4 * n), self._plane(m, "guide", guide, 4 * n),
+            self._plane(m, "rad_out", rad_out, 4 * n), self._plane(m, "var_out", var_out, n),
+            self._plane(m, "tmp", tmp, 4 * n), self._plane(m, "var_tmp", var_tmp, n), stream), "rt_radiance_atrous")
 
     def upscale(self, render_width: int, render_height: int, width: int, height: int, color_cur, motion_cur, color_out,
                 hist_out, motion_prev=None, color_prev=None, hist_prev=None, rgba8_out=None, jitter_cur=(0.0, 0.0),

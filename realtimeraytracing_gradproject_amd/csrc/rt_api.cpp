@@ -2424,6 +2424,135 @@ rt_status rt_ao_atrous(rt_ctx_t c, uint32_t W, uint32_t H, const rt_ao_atrous_pa
   return RT_OK;
 }
 
+// ---- Radiance filter: the argument checks shared by the device entry points and their host twins
+// (align as above), and the iterations' planes ------------------------------------------------------------------
+namespace {
+
+const char* radiance_accumulate_args_error(uint32_t W, uint32_t H, const rt_radiance_temporal_params* p,
+                                           const float* rad_cur, const float* motion, const float* guide_cur,
+                                           const float* rad_prev, const float* moments_prev, const float* guide_prev,
+                                           const float* rad_out, const float* moments_out, bool align,
+                                           rt_status* st) {
+  if (const char* why = denoise_frame_error(W, H, st)) return why;
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (p->max_history < 1 || p->max_history > 1024) return "max_history outside 1..1024";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!(p->normal_cos >= -1.0f && p->normal_cos < 1.0f)) return "normal_cos outside [-1, 1)";
+  if (!rad_cur) return "null rad_cur";
+  if (!motion) return "null motion plane";
+  if (!guide_cur) return "null guide_cur";
+  if (!rad_out) return "null rad_out";
+  if (!moments_out) return "null moments_out";
+  const int nprev = (rad_prev != nullptr) + (moments_prev != nullptr) + (guide_prev != nullptr);
+  if (nprev != 0 && nprev != 3) return "rad_prev, moments_prev and guide_prev must be all given or all NULL";
+  const size_t a4 = align ? 16 : 4;
+  for (const float* q : {rad_cur, motion, guide_cur, rad_prev, moments_prev, guide_prev, rad_out, moments_out})
+    if (misaligned(q, a4)) return "a plane is misaligned";
+  if (rad_out == moments_out) return "rad_out is moments_out";
+  for (const float* o : {rad_out, moments_out}) {
+    if (nprev && (o == rad_prev || o == moments_prev || o == guide_prev)) return "an output is a previous-frame plane";
+    // rad_cur too: the spatial variance estimate reads a pixel's neighbours there
+    if (o == rad_cur || o == motion || o == guide_cur) return "an output is rad_cur, the motion plane or guide_cur";
+  }
+  return nullptr;
+}
+
+const char* radiance_atrous_args_error(uint32_t W, uint32_t H, const rt_radiance_atrous_params* p,
+                                       const float* rad_in, const float* moments, const float* guide,
+                                       const float* rad_out, const float* var_out, const float* tmp,
+                                       const float* var_tmp, bool align, rt_status* st) {
+  if (const char* why = denoise_frame_error(W, H, st)) return why;
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (p->iterations < 1 || p->iterations > 5) return "iterations outside 1..5";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!(p->normal_cos >= -1.0f && p->normal_cos < 1.0f)) return "normal_cos outside [-1, 1)";
+  if (!std::isfinite(p->sigma_l) || !(p->sigma_l > 0.0f)) return "sigma_l not finite and > 0";
+  if (!rad_in) return "null rad_in";
+  if (!moments) return "null moments";
+  if (!guide) return "null guide";
+  if (!rad_out) return "null rad_out";
+  if (!var_out) return "null var_out";
+  if ((!tmp || !var_tmp) && p->iterations > 1) return "null tmp or var_tmp with more than one iteration";
+  const size_t a4 = align ? 16 : 4;
+  for (const float* q : {rad_in, moments, guide, rad_out, tmp})
+    if (misaligned(q, a4)) return "a 4-float plane is misaligned";
+  if (misaligned(var_out, 4) || misaligned(var_tmp, 4)) return "a variance plane is not aligned to 4 bytes";
+  const float* all[] = {rad_in, moments, guide, rad_out, var_out, tmp, var_tmp};
+  for (size_t i = 0; i < 7; ++i)
+    for (size_t j = i + 1; j < 7; ++j)
+      if (all[i] && all[i] == all[j]) return "two planes are the same";
+  return nullptr;
+}
+
+rt::RadTemporal radiance_temporal_of(uint32_t W, uint32_t H, const rt_radiance_temporal_params* p,
+                                     const float* rad_cur, const float* motion, const float* guide_cur,
+                                     const float* rad_prev, const float* moments_prev, const float* guide_prev,
+                                     float* rad_out, float* moments_out) {
+  rt::RadTemporal a = {};
+  a.W = W, a.H = H;
+  a.max_history = (float)p->max_history;
+  a.depth_tol = p->depth_tol, a.normal_cos = p->normal_cos;
+  a.rad_cur = rad_cur, a.motion = motion, a.guide_cur = guide_cur;
+  a.rad_prev = rad_prev, a.moments_prev = moments_prev, a.guide_prev = guide_prev;
+  a.rad_out = rad_out, a.moments_out = moments_out;
+  return a;
+}
+
+// Iteration k of rt_radiance_atrous: atrous_planes' ping-pong for the colour and the variance alike; iteration 0 reads
+// the variance from the moments plane's .w.
+rt::RadAtrous radiance_iteration(uint32_t k, uint32_t W, uint32_t H, const rt_radiance_atrous_params* p,
+                                 const float* rad_in, const float* moments, const float* guide, float* rad_out,
+                                 float* var_out, float* tmp, float* var_tmp) {
+  rt::RadAtrous a = {};
+  a.W = W, a.H = H, a.s = 1u << k;
+  a.depth_tol = p->depth_tol, a.normal_cos = p->normal_cos, a.sigma_l = p->sigma_l;
+  a.guide = guide;
+  atrous_planes(k, p->iterations, rad_in, rad_out, tmp, &a.in, &a.out);
+  atrous_planes(k, p->iterations, moments + 3, var_out, var_tmp, &a.var, &a.var_out);
+  a.var_stride = k == 0 ? 4u : 1u;
+  return a;
+}
+
+}  // namespace
+
+rt_status rt_radiance_accumulate(rt_ctx_t c, uint32_t W, uint32_t H, const rt_radiance_temporal_params* params,
+                                 const float* rad_cur, const float* motion, const float* guide_cur,
+                                 const float* rad_prev, const float* moments_prev, const float* guide_prev,
+                                 float* rad_out, float* moments_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = radiance_accumulate_args_error(W, H, params, rad_cur, motion, guide_cur, rad_prev,
+                                                       moments_prev, guide_prev, rad_out, moments_out, true, &st))
+    return fail(c, st, std::string("rt_radiance_accumulate: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_radiance_accumulate(
+      radiance_temporal_of(W, H, params, rad_cur, motion, guide_cur, rad_prev, moments_prev, guide_prev, rad_out,
+                           moments_out),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "radiance accumulate launch");
+  return RT_OK;
+}
+
+rt_status rt_radiance_atrous(rt_ctx_t c, uint32_t W, uint32_t H, const rt_radiance_atrous_params* params,
+                             const float* rad_in, const float* moments, const float* guide, float* rad_out,
+                             float* var_out, float* tmp, float* var_tmp, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why =
+          radiance_atrous_args_error(W, H, params, rad_in, moments, guide, rad_out, var_out, tmp, var_tmp, true, &st))
+    return fail(c, st, std::string("rt_radiance_atrous: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipStream_t s = pick_stream(c, stream);
+  for (uint32_t k = 0; k < params->iterations; ++k) {
+    const hipError_t e = rt::launch_radiance_atrous(
+        radiance_iteration(k, W, H, params, rad_in, moments, guide, rad_out, var_out, tmp, var_tmp), c->atrous_form, s);
+    if (e != hipSuccess) return hip_fail(c, e, "radiance a-trous launch");
+  }
+  return RT_OK;
+}
+
 // ---- Temporal upscaler: the argument check shared by rt_upscale and rt_host_upscale (align as above) --
 namespace {
 
@@ -3136,6 +3265,78 @@ rt_status rt_host_ao_atrous(uint32_t W, uint32_t H, const rt_ao_atrous_params* p
         dst[i] = g[3] == 0.0f ? src[i]
                               : rt::atrous_pixel(g, s, params->depth_tol, params->normal_cos,
                                                  HostTap{guide, src, (int)x, (int)y, (int)s, (int)W, (int)H});
+      }
+  }
+  return RT_OK;
+}
+
+// Host services: the radiance filter's two passes on host arrays, as the AO filter's above.
+rt_status rt_host_radiance_accumulate(uint32_t W, uint32_t H, const rt_radiance_temporal_params* params,
+                                      const float* rad_cur, const float* motion, const float* guide_cur,
+                                      const float* rad_prev, const float* moments_prev, const float* guide_prev,
+                                      float* rad_out, float* moments_out) {
+  rt_status st = RT_OK;
+  if (radiance_accumulate_args_error(W, H, params, rad_cur, motion, guide_cur, rad_prev, moments_prev, guide_prev,
+                                     rad_out, moments_out, false, &st))
+    return st;
+  const rt::RadTemporal a = radiance_temporal_of(W, H, params, rad_cur, motion, guide_cur, rad_prev, moments_prev,
+                                                 guide_prev, rad_out, moments_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::radiance_accumulate_pixel(a, x, y);
+  return RT_OK;
+}
+
+namespace {
+struct HostRadTap {  // rt_denoise.hip's RadGlobalTap on host arrays
+  const rt::RadAtrous& a;
+  int x, y;
+  bool at(int dx, int dy, size_t& t) const {
+    const int xx = x + dx * (int)a.s, yy = y + dy * (int)a.s;
+    if (xx < 0 || yy < 0 || xx >= (int)a.W || yy >= (int)a.H) return false;
+    t = (size_t)yy * (size_t)a.W + (size_t)xx;
+    return true;
+  }
+  bool var_at(int dx, int dy, float& v) const {
+    size_t t;
+    if (!at(dx, dy, t)) return false;
+    v = a.var[t * a.var_stride];
+    return true;
+  }
+  bool operator()(int dx, int dy, float q[4], float c[4], float& v) const {
+    size_t t;
+    if (!at(dx, dy, t)) return false;
+    rt::ld4(a.guide + 4 * t, q);
+    rt::ld4(a.in + 4 * t, c);
+    v = a.var[t * a.var_stride];
+    return true;
+  }
+};
+}  // namespace
+
+rt_status rt_host_radiance_atrous(uint32_t W, uint32_t H, const rt_radiance_atrous_params* params,
+                                  const float* rad_in, const float* moments, const float* guide, float* rad_out,
+                                  float* var_out, float* tmp, float* var_tmp) {
+  rt_status st = RT_OK;
+  if (radiance_atrous_args_error(W, H, params, rad_in, moments, guide, rad_out, var_out, tmp, var_tmp, false, &st))
+    return st;
+  for (uint32_t k = 0; k < params->iterations; ++k) {
+    const rt::RadAtrous a =
+        radiance_iteration(k, W, H, params, rad_in, moments, guide, rad_out, var_out, tmp, var_tmp);
+    for (uint32_t y = 0; y < H; ++y)
+      for (uint32_t x = 0; x < W; ++x) {
+        const size_t i = (size_t)y * W + x;
+        float g[4], c[4], o[4], vo;
+        rt::ld4(guide + 4 * i, g);
+        rt::ld4(a.in + 4 * i, c);
+        if (g[3] == 0.0f) {
+          rt::st4(a.out + 4 * i, c);
+          a.var_out[i] = a.var[i * a.var_stride];
+          continue;
+        }
+        rt::radiance_atrous_pixel(g, c, a.s, a.depth_tol, a.normal_cos, a.sigma_l, HostRadTap{a, (int)x, (int)y}, o,
+                                  vo);
+        rt::st4(a.out + 4 * i, o);
+        a.var_out[i] = vo;
       }
   }
   return RT_OK;

@@ -24,9 +24,18 @@
 //                       planes, the reflection pass's radiance and an instance -> material map -> the colour frame of
 //                       the RT_SHADE_REF hit programs. The lights, the camera and the material table (32 entries of
 //                       60 B) ride in the kernel argument.
+//   k_radiance_accumulate   the radiance filter's temporal pass (rt_radiance_accumulate), one pixel per
+//                       lane over 32 x 8 tiles: k_ao_accumulate's reprojection over 4-float radiance entries and the
+//                       luminance moments (a tap costs two 16-byte loads plus the guide's); the 25-tap spatial variance
+//                       estimate runs only on lanes whose history is shorter than 4.
+//   k_radiance_atrous_direct / k_radiance_atrous_lds  one iteration of rt_radiance_atrous in the two AO forms. The
+//                       staged form takes the same 36 x 12 lattice tile in three arrays (guide float4, colour float4,
+//                       variance float: 15,552 B); every row read is 32 consecutive entries as in k_ao_atrous_lds, and
+//                       the halo of 2 covers the 3 x 3 variance prefilter, which sits on the same lattice.
 //
-// The arithmetic of all seven is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
-// resolve_pixel, reflection_composite_pixel, resolve_pbr_pixel), which the host twins in rt_api.cpp call too: the
+// The arithmetic of all of them is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
+// resolve_pixel, reflection_composite_pixel, resolve_pbr_pixel, radiance_accumulate_pixel, radiance_atrous_pixel),
+// which the host twins in rt_api.cpp call too: the
 // kernels differ from them in where a value is read, never in how it is used.
 // Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
 #include "rt_internal.hpp"
@@ -167,6 +176,138 @@ __global__ __launch_bounds__(256) void k_shade_resolve_pbr(ResolvePbr r) {
   resolve_pbr_pixel(r, i % r.W, i / r.W);
 }
 
+__global__ __launch_bounds__(256) void k_radiance_accumulate(RadTemporal a, uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= a.W || y >= a.H) return;
+  radiance_accumulate_pixel(a, x, y);
+}
+
+struct RadGlobalTap {  // a tap read from the planes, bounds-checked; var is read every var_stride floats
+  const float* guide;
+  const float* in;
+  const float* var;
+  uint32_t var_stride;
+  int x, y, s, W, H;
+  __device__ __forceinline__ bool at(int dx, int dy, size_t& t) const {
+    const int xx = x + dx * s, yy = y + dy * s;
+    if (xx < 0 || yy < 0 || xx >= W || yy >= H) return false;
+    t = (size_t)yy * (size_t)W + (size_t)xx;
+    return true;
+  }
+  __device__ __forceinline__ bool var_at(int dx, int dy, float& v) const {
+    size_t t;
+    if (!at(dx, dy, t)) return false;
+    v = var[t * var_stride];
+    return true;
+  }
+  __device__ __forceinline__ bool operator()(int dx, int dy, float q[4], float c[4], float& v) const {
+    size_t t;
+    if (!at(dx, dy, t)) return false;
+    ld4(guide + 4 * t, q);
+    ld4(in + 4 * t, c);
+    v = var[t * var_stride];
+    return true;
+  }
+};
+
+// var: the variance read every var_stride floats (iteration 0 reads the moments plane's .w at stride 4).
+__global__ __launch_bounds__(256) void k_radiance_atrous_direct(
+    uint32_t W, uint32_t H, uint32_t s, float depth_tol,
+    float normal_cos, float sigma_l, const float* __restrict__ in,
+    const float* __restrict__ var, uint32_t var_stride,
+    const float* __restrict__ guide, float* __restrict__ out,
+    float* __restrict__ var_out, uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= W || y >= H) return;
+  const size_t i = (size_t)y * W + x;
+  float g[4], c[4], o[4], vo;
+  ld4(guide + 4 * i, g);
+  ld4(in + 4 * i, c);
+  if (g[3] == 0.0f) {
+    st4(out + 4 * i, c);
+    var_out[i] = var[i * var_stride];
+    return;
+  }
+  radiance_atrous_pixel(g, c, s, depth_tol, normal_cos, sigma_l,
+                        RadGlobalTap{guide, in, var, var_stride, (int)x, (int)y, (int)s, (int)W, (int)H}, o, vo);
+  st4(out + 4 * i, o);
+  var_out[i] = vo;
+}
+
+struct RadLdsTap {  // a tap read from the staged tile: an entry outside the frame was staged as "no surface"
+  const float4* g;
+  const float4* c;
+  const float* v;
+  int at;  // the pixel's own entry
+  int x, y, s, W, H;  // the prefilter alone asks whether a tap lies in the frame
+  __device__ __forceinline__ bool var_at(int dx, int dy, float& val) const {
+    const int xx = x + dx * s, yy = y + dy * s;
+    if (xx < 0 || yy < 0 || xx >= W || yy >= H) return false;
+    val = v[at + dy * (int)kStageW + dx];
+    return true;
+  }
+  __device__ __forceinline__ bool operator()(int dx, int dy, float q[4], float col[4], float& val) const {
+    const int e = at + dy * (int)kStageW + dx;
+    const float4 t = g[e], u = c[e];
+    q[0] = t.x, q[1] = t.y, q[2] = t.z, q[3] = t.w;
+    col[0] = u.x, col[1] = u.y, col[2] = u.z, col[3] = u.w;
+    val = v[e];
+    return true;
+  }
+};
+
+// k_ao_atrous_lds's block order and staging (shift = log2(s), nbx = lattice tiles per row * s) with a colour array.
+__global__ __launch_bounds__(256) void k_radiance_atrous_lds(
+    uint32_t W, uint32_t H, uint32_t shift, float depth_tol,
+    float normal_cos, float sigma_l, const float* __restrict__ in,
+    const float* __restrict__ var, uint32_t var_stride,
+    const float* __restrict__ guide, float* __restrict__ out,
+    float* __restrict__ var_out, uint32_t nbx) {
+  __shared__ float4 sg[kStageH * kStageW];
+  __shared__ float4 sc[kStageH * kStageW];
+  __shared__ float sv[kStageH * kStageW];
+  const uint32_t s = 1u << shift;
+  const uint32_t bx = blockIdx.x % nbx, by = blockIdx.x / nbx;
+  const uint32_t rx = bx & (s - 1u), ry = by & (s - 1u);
+  const int lx0 = (int)((bx >> shift) * kTileW), ly0 = (int)((by >> shift) * kTileH);  // the tile's lattice origin
+  if ((uint32_t)lx0 * s + rx >= W || (uint32_t)ly0 * s + ry >= H) return;  // block-uniform: an empty tile
+  for (uint32_t e = threadIdx.x; e < kStageH * kStageW; e += 256u) {
+    const int li = lx0 + (int)(e % kStageW) - (int)kHalo, lj = ly0 + (int)(e / kStageW) - (int)kHalo;
+    const long long X = (long long)li * s + rx, Y = (long long)lj * s + ry;
+    float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f), col = q;
+    float v = 0.0f;
+    if (li >= 0 && lj >= 0 && X < (long long)W && Y < (long long)H) {
+      const size_t t = (size_t)Y * W + (size_t)X;
+      q = *reinterpret_cast<const float4*>(guide + 4 * t);
+      col = *reinterpret_cast<const float4*>(in + 4 * t);
+      v = var[t * var_stride];
+    }
+    sg[e] = q;
+    sc[e] = col;
+    sv[e] = v;
+  }
+  __syncthreads();
+  const uint32_t tx = threadIdx.x & 31u, ty = threadIdx.x >> 5;
+  const uint32_t x = ((uint32_t)lx0 + tx) * s + rx, y = ((uint32_t)ly0 + ty) * s + ry;
+  if (x >= W || y >= H) return;
+  const int at = (int)((ty + kHalo) * kStageW + tx + kHalo);
+  const size_t i = (size_t)y * W + x;
+  const float4 gq = sg[at], cq = sc[at];
+  if (gq.w == 0.0f) {
+    *reinterpret_cast<float4*>(out + 4 * i) = cq;
+    var_out[i] = sv[at];
+    return;
+  }
+  const float g[4] = {gq.x, gq.y, gq.z, gq.w}, c[4] = {cq.x, cq.y, cq.z, cq.w};
+  float o[4], vo;
+  radiance_atrous_pixel(g, c, s, depth_tol, normal_cos, sigma_l,
+                        RadLdsTap{sg, sc, sv, at, (int)x, (int)y, (int)s, (int)W, (int)H}, o, vo);
+  st4(out + 4 * i, o);
+  var_out[i] = vo;
+}
+
 uint32_t tiles(uint32_t n, uint32_t t) { return (n + t - 1u) / t; }
 
 }  // namespace
@@ -219,6 +360,35 @@ hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol,
   if (nbx * nby > 0x7fffffffull) return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(k_ao_atrous_lds, dim3((uint32_t)(nbx * nby)), dim3(256), 0, stream, W, H, shift, depth_tol,
                      normal_cos, in, guide, out, (uint32_t)nbx);
+  return hipGetLastError();
+}
+
+hipError_t launch_radiance_accumulate(const RadTemporal& a, hipStream_t stream) {
+  const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
+  hipLaunchKernelGGL(k_radiance_accumulate, dim3(tx * ty), dim3(256), 0, stream, a, tx);
+  return hipGetLastError();
+}
+
+hipError_t launch_radiance_atrous(const RadAtrous& a, int form, hipStream_t stream) {
+  // Measured per step on C2F at 1080p (tools/radiance_filter_study.py), not launch_ao_atrous's rule: the
+  // staged form takes 0.58 x, 0.88 x and 0.91 x the direct form's time at steps 1, 2 and 4, beyond both p10 - p90
+  // spreads; from step 8 on its staging loads (36 B per entry against the AO filter's 20 B, a cache line apart) cost
+  // more than the taps they save and it takes 1.30 x and 1.75 x.
+  if (form == kAtrousAuto) form = a.s <= 4u ? kAtrousLds : kAtrousDirect;
+  if (form == kAtrousDirect) {
+    const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
+    hipLaunchKernelGGL(k_radiance_atrous_direct, dim3(tx * ty), dim3(256), 0, stream, a.W, a.H, a.s, a.depth_tol,
+                       a.normal_cos, a.sigma_l, a.in, a.var, a.var_stride, a.guide, a.out, a.var_out, tx);
+    return hipGetLastError();
+  }
+  uint32_t shift = 0;
+  while ((1u << shift) < a.s) ++shift;
+  const uint64_t nbx = (uint64_t)tiles(tiles(a.W, a.s), kTileW) * a.s,
+                 nby = (uint64_t)tiles(tiles(a.H, a.s), kTileH) * a.s;  // as launch_ao_atrous
+  if (nbx * nby > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(k_radiance_atrous_lds, dim3((uint32_t)(nbx * nby)), dim3(256), 0, stream, a.W, a.H, shift,
+                     a.depth_tol, a.normal_cos, a.sigma_l, a.in, a.var, a.var_stride, a.guide, a.out, a.var_out,
+                     (uint32_t)nbx);
   return hipGetLastError();
 }
 

@@ -1181,6 +1181,180 @@ RT_HD float atrous_pixel(const float g[4], uint32_t s, float depth_tol, float no
   return sa / sw;
 }
 
+// ------------------------------------------------------------------------------------------
+// Radiance filter (rt_radiance_accumulate, rt_radiance_atrous): the AO filter's pair for planes of
+// 4-float entries (a reflection plane: mean colour and mean distance), with luminance moments kept by the temporal
+// pass and a luminance weight scaled by their variance in the blur. The AO section's arithmetic rule holds;
+// tests/radiance_reference.py restates it in numpy.
+// ------------------------------------------------------------------------------------------
+RT_HD float radiance_lum(const float c[4]) { return (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2]; }
+
+// The normal weight both passes share with atrous_pixel.
+RT_HD float radiance_wn(V3 gn, const float q[4], float normal_cos, float nden) {
+  return minf(1.0f, maxf(0.0f, (dot(gn, v3(q[0], q[1], q[2])) - normal_cos) / nden));
+}
+
+struct RadTemporal {  // rt_radiance_accumulate's launch (prev planes all null or none)
+  uint32_t W, H;
+  float max_history, depth_tol, normal_cos;
+  const float *rad_cur, *motion, *guide_cur, *rad_prev, *moments_prev, *guide_prev;
+  float *rad_out, *moments_out;
+};
+
+// Pixel (x, y) of rt_radiance_accumulate: ao_accumulate_pixel's reprojection (the same conditions, taps, weights and
+// rejection tests) over the radiance entry and the moments (m1, m2, hist), then the variance: temporal from a history
+// of 4 or more, else from the 5 x 5 neighbourhood of rad_cur under the guide's depth and normal weights.
+RT_HD void radiance_accumulate_pixel(const RadTemporal& a, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * a.W + x;
+  float c[4], g[4], m[4];
+  ld4(a.rad_cur + 4 * i, c);
+  ld4(a.guide_cur + 4 * i, g);
+  if (g[3] == 0.0f) {
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    st4(a.rad_out + 4 * i, c);
+    st4(a.moments_out + 4 * i, zero);
+    return;
+  }
+  ld4(a.motion + 4 * i, m);
+  const float big = 3.402823466e+38f;
+  const float l = radiance_lum(c);
+  const V3 gn = v3(g[0], g[1], g[2]);
+  float sw = 0.0f, s1 = 0.0f, s2 = 0.0f, sh = 0.0f;
+  float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (a.rad_prev && fabsf(m[0]) <= big && fabsf(m[1]) <= big && m[2] > 0.0f) {
+    const float fx = (float)x + m[0], fy = (float)y + m[1];
+    if (fx > -1.0f && fx < (float)a.W && fy > -1.0f && fy < (float)a.H) {  // before any conversion to integer
+      const float xf = floorf(fx), yf = floorf(fy);
+      const float tx = fx - xf, ty = fy - yf;
+      const int x0 = (int)xf, y0 = (int)yf;
+      const float lim = a.depth_tol * m[2];
+      for (int k = 0; k < 4; ++k) {
+        const int dx = k & 1, dy = k >> 1;
+        const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
+        const int xx = x0 + dx, yy = y0 + dy;
+        if (w == 0.0f || xx < 0 || yy < 0 || xx >= (int)a.W || yy >= (int)a.H) continue;
+        const size_t t = (size_t)yy * a.W + (size_t)xx;
+        float q[4], rp[4], mp[4];
+        ld4(a.guide_prev + 4 * t, q);
+        if (q[3] == 0.0f || fabsf(q[3] - m[2]) > lim || dot(gn, v3(q[0], q[1], q[2])) < a.normal_cos) continue;
+        ld4(a.rad_prev + 4 * t, rp);
+        ld4(a.moments_prev + 4 * t, mp);
+        sw += w;
+        for (int k4 = 0; k4 < 4; ++k4) sc[k4] += w * rp[k4];
+        s1 += w * mp[0];
+        s2 += w * mp[1];
+        sh += w * mp[2];
+      }
+    }
+  }
+  float out[4], mo[4];
+  if (sw >= 0.01f) {
+    const float n = minf(sh / sw + 1.0f, a.max_history);
+    const float al = 1.0f / n;
+    const float p1 = s1 / sw, p2 = s2 / sw, l2 = l * l;
+    for (int k = 0; k < 4; ++k) {
+      const float p = sc[k] / sw;
+      out[k] = n == 1.0f ? c[k] : p + al * (c[k] - p);  // n == 1: the current value itself (ao_accumulate_pixel)
+    }
+    mo[0] = n == 1.0f ? l : p1 + al * (l - p1);
+    mo[1] = n == 1.0f ? l2 : p2 + al * (l2 - p2);
+    mo[2] = n;
+  } else {
+    for (int k = 0; k < 4; ++k) out[k] = c[k];
+    mo[0] = l, mo[1] = l * l, mo[2] = 1.0f;
+  }
+  if (mo[2] >= 4.0f) {
+    mo[3] = maxf(0.0f, mo[1] - mo[0] * mo[0]);
+  } else {  // a short history: the spatial estimate, scaled up by how short it is
+    const float zden = a.depth_tol * g[3];
+    const float nden = 1.0f - a.normal_cos;
+    float tw = 0.0f, t1 = 0.0f, t2 = 0.0f;
+    for (int dy = -2; dy <= 2; ++dy) {
+      for (int dx = -2; dx <= 2; ++dx) {
+        const int xx = (int)x + dx, yy = (int)y + dy;
+        if (xx < 0 || yy < 0 || xx >= (int)a.W || yy >= (int)a.H) continue;
+        const size_t t = (size_t)yy * a.W + (size_t)xx;
+        float q[4], ct[4];
+        float w = 1.0f;
+        if (dx != 0 || dy != 0) {
+          ld4(a.guide_cur + 4 * t, q);
+          if (q[3] == 0.0f) continue;
+          const float wz = maxf(0.0f, 1.0f - fabsf(q[3] - g[3]) / zden);
+          w = wz * radiance_wn(gn, q, a.normal_cos, nden);
+        }
+        ld4(a.rad_cur + 4 * t, ct);
+        const float lt = radiance_lum(ct);
+        tw += w;
+        t1 += w * lt;
+        t2 += w * (lt * lt);
+      }
+    }
+    const float M1 = t1 / tw, M2 = t2 / tw;
+    mo[3] = maxf(0.0f, M2 - M1 * M1) * (4.0f / mo[2]);
+  }
+  st4(a.rad_out + 4 * i, out);
+  st4(a.moments_out + 4 * i, mo);
+}
+
+// One iteration's colour and variance for a pixel with guide g (g[3] != 0) and input colour c0. s: the step;
+// tap(dx, dy, q, c, v) gives the guide entry, the input colour and the input variance of the tap at (x + dx s,
+// y + dy s) and returns false where that lies outside the frame; tap.var_at(dx, dy, v) gives the variance alone, for the
+// 3 x 3 prefilter on the step's lattice (in-frame taps only, a tap without a surface included). dy outer, dx inner,
+// ascending, in both loops.
+template <typename Tap>
+RT_HD void radiance_atrous_pixel(const float g[4], const float c0[4], uint32_t s, float depth_tol, float normal_cos,
+                                 float sigma_l, Tap tap, float out[4], float& var_out) {
+  const V3 gn = v3(g[0], g[1], g[2]);
+  const float zden = (depth_tol * g[3]) * (float)s;
+  const float nden = 1.0f - normal_cos;
+  float pw = 0.0f, pv = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int dy = -1; dy <= 1; ++dy) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dx = -1; dx <= 1; ++dx) {
+      float v;
+      if (!tap.var_at(dx, dy, v)) continue;
+      const float w = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
+      pw += w;
+      pv += w * v;
+    }
+  }
+  const float lden = sigma_l * sqrtf(pv / pw) + 1e-4f;
+  const float lc = radiance_lum(c0);
+  float sw = 0.0f, sv = 0.0f;
+  float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int dy = -2; dy <= 2; ++dy) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dx = -2; dx <= 2; ++dx) {
+      float q[4], c[4], v;
+      if (!tap(dx, dy, q, c, v)) continue;
+      float w = atrous_h(dy) * atrous_h(dx);
+      if (dx != 0 || dy != 0) {
+        if (q[3] == 0.0f) continue;
+        const float wz = maxf(0.0f, 1.0f - fabsf(q[3] - g[3]) / zden);
+        const float wn = radiance_wn(gn, q, normal_cos, nden);
+        const float wl = maxf(0.0f, 1.0f - fabsf(radiance_lum(c) - lc) / lden);
+        const float e = (wz * wn) * wl;
+        w = w * (e * e);
+      }
+      sw += w;
+      for (int k = 0; k < 4; ++k) sc[k] += w * c[k];
+      sv += (w * w) * v;
+    }
+  }
+  for (int k = 0; k < 4; ++k) out[k] = sc[k] / sw;
+  var_out = sv / (sw * sw);
+}
+
 // The resolve of the soft-shadow section above (rt_shade_resolve); here for ld4 / st4.
 // rt_shade_resolve's launch: the camera, the lights, the frame's size and the planes (vis, ao, rgba8_out may be null).
 struct Resolve {

@@ -234,6 +234,21 @@ enum { kAtrousAuto = 0, kAtrousDirect = 1, kAtrousLds = 2 };
 hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol, float normal_cos, const float* in,
                             const float* guide, float* out, int form, hipStream_t stream);
 
+// --- Radiance filter (rt_denoise.hip) -----------------------------------------
+// The AO filter's pair for planes of 4-float entries; per-pixel arithmetic in rt_device.hpp, shared with the host twins.
+hipError_t launch_radiance_accumulate(const RadTemporal& a, hipStream_t stream);
+// One a-trous iteration of step s: colour `in` and variance `var` (read every var_stride floats) to out / var_out.
+struct RadAtrous {
+  uint32_t W, H, s;
+  float depth_tol, normal_cos, sigma_l;
+  const float *in, *var;
+  uint32_t var_stride;
+  const float* guide;
+  float *out, *var_out;
+};
+// form: launch_ao_atrous's constants; kAtrousAuto picks per step by this filter's own measurement.
+hipError_t launch_radiance_atrous(const RadAtrous& a, int form, hipStream_t stream);
+
 // --- Temporal upscaler (rt_upscale.hip) ---------------------------------------
 // One launch; no scene, no scratch. form: kUpscaleDirect (each lane loads its 9 + 9 taps) or kUpscaleLds (a workgroup
 // stages its tile's render-resolution footprint in LDS); kUpscaleAuto picks.
