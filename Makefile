@@ -178,8 +178,11 @@ $(ASAN)/obj_ingest_fuzz: tools/obj_ingest_fuzz.cpp $(ASAN)/rt_host.o | $(ASAN)
 #   asan-radiance        the radiance filter's host twins (rt_host_radiance_accumulate, rt_host_radiance_atrous: the
 #                        5 x 5 and 3 x 3 stencils with edge handling and the stride-4 variance read, on exact-size heap
 #                        blocks)
+#   asan-indirect        the indirect pass's host twins (rt_host_indirect_rays against rt_host_ao_rays' directions,
+#                        rt_host_shade_resolve_gi with every subset of the optional planes and its anchors against
+#                        rt_host_shade_resolve_pbr, on exact-size heap blocks)
 ASAN_CHECKS := asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials asan-reflection-pbr \
-               asan-radiance
+               asan-radiance asan-indirect
 asan-ao: $(ASAN)/ao_rays_check
 asan-denoise: $(ASAN)/denoise_check
 asan-upscale: $(ASAN)/upscale_check
@@ -188,6 +191,7 @@ asan-reflection: $(ASAN)/reflection_check
 asan-materials: $(ASAN)/materials_check
 asan-reflection-pbr: $(ASAN)/reflection_pbr_check
 asan-radiance: $(ASAN)/radiance_check
+asan-indirect: $(ASAN)/indirect_check
 
 $(ASAN)/rt_api.o: $(SRC)/rt_api.cpp $(HDRS) | $(ASAN)
 	$(HIPCC) $(HIPFLAGS) -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -c $< -o $@

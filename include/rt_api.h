@@ -41,7 +41,9 @@ extern "C" {
  * rt_resolve_pbr_inputs and RT_MAX_MATERIALS, and rt_dispatch_reflection_pbr, its host twins
  * rt_host_reflection_rays_flags and rt_host_reflection_radiance_pbr, rt_reflection_pbr_params and the RT_REFLECT_*
  * flags, and rt_radiance_accumulate, rt_radiance_atrous, their host twins rt_host_radiance_accumulate and
- * rt_host_radiance_atrous, rt_radiance_temporal_params and rt_radiance_atrous_params. */
+ * rt_host_radiance_atrous, rt_radiance_temporal_params and rt_radiance_atrous_params, and rt_dispatch_indirect,
+ * rt_shade_resolve_gi, their host twins rt_host_indirect_rays and rt_host_shade_resolve_gi, rt_indirect_params and
+ * rt_resolve_gi_inputs. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -962,6 +964,80 @@ rt_status rt_dispatch_reflection_pbr(rt_ctx_t ctx, uint32_t W, uint32_t H, const
                                      const rt_reflection_pbr_params* params, const rt_material_table* table,
                                      const rt_reflection_planes* out, void* hip_stream);
 
+/* Parameters of the diffuse indirect pass: samples 1..64; seed; tmax finite and > 0.001; shadow_tmin finite and >= 0;
+ * flags: RT_REFLECT_SHADOW_MODELS or 0 (there is no mirror direction here, so RT_REFLECT_FRAME_RAY is refused). */
+typedef struct { uint32_t samples; uint32_t seed; float tmax; float shadow_tmin; uint32_t flags; } rt_indirect_params;
+
+/* The diffuse indirect pass: one bounce of light that reaches a surface by way of another surface. Per
+ * pixel `samples` cosine-weighted closest-hit rays about the facing normal, each shaded as rt_dispatch_reflection_pbr
+ * shades a reflection ray, reduced to that pass's planes: radiance (mean colour, mean distance in .w: the plane
+ * rt_radiance_accumulate / rt_radiance_atrous take) and, optionally, hits (ray 0's record). Everything
+ * rt_dispatch_reflection_pbr documents about W, H, rows, nrows and the compact row order, the schedule rule and the
+ * per-lane fall-back, rt_set_triangle_test, streams, slot rings, the TLAS double buffer, rt_forget_stream and
+ * refit-before-rebuild, the table (materials a host array copied by value, the map a device array keyed by instance
+ * index, no index reads outside either array), `out` (radiance required, hits optional) and the zero entries on a
+ * primary miss or an invalid normal holds unchanged. Needs a camera, a current TLAS and the context's lights.
+ * Pixel (px, py), py the GLOBAL row, camera ray (O, D), primary hit at t, G-buffer normal N:
+ *   a primary miss, or N not valid by rt_dispatch_ao's rule: four zeros, four zero words, no ray traced;
+ *   otherwise P = O + D t, nf = rt_dispatch_ao's facing normal of the pixel (bit for bit),
+ *   base = ao_base(px, py, seed ^ hash(0x200)) (the AO pass's base under a seed of this pass's own: the reflection
+ *   passes use 0x100, the shadow pass l + 1 <= 16), d_k = ao_direction(nf, ao_sphere(base, k)): for every k the
+ *   direction rt_host_ao_rays returns for seed `seed ^ hash(0x200)`, to the bit; sample k does not depend on samples.
+ * Ray k is (P + d_k * 0.001f, 0.001f, d_k, tmax), the reflection passes' origin rule, searched closest-hit under
+ * RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES. Its colour L_k and distance t_k follow rt_dispatch_reflection_pbr's "Colour
+ * of ray k", rule for rule: a miss is the miss colour at the pixel's row with t_k = tmax; a plane hit PlaneClosestHit
+ * with its one shadow ray to light 0; a model hit ClosestHit's surface colour under the hit instance's material with
+ * cam = the ray's origin and, with RT_REFLECT_SHADOW_MODELS, one shadow ray per faced light (without it an occluded
+ * light still lights the bounce: the flag is what a caller wants unless it measures). The reduction, radiance.w and
+ * hits are that pass's.
+ * Hence the anchor: the radiance plane equals rt_host_reflection_radiance_pbr (params {samples, seed, roughness 0,
+ * tmax, shadow_tmin, flags}) fed rt_host_indirect_rays' rays and what they hit. No new arithmetic: every expected
+ * value comes from functions that existed before the pass.
+ * Schedule: set by rt_set_schedule as for every grid pass; nothing switches by itself. Recommendation, from the
+ * measurement in DESIGN §3.18 (C2F at 1080p, REFLO at 720p): keep RT_SCHED_PACKET, the default. At samples 1, the
+ * real-time case, the packet kernel was 1.08 - 1.24 x faster than the per-lane kernel in all four cases measured, and
+ * at samples 4 with RT_REFLECT_SHADOW_MODELS it was ahead or level (1.08 x, 0.99 x within the spread). Only the
+ * unshadowed pass at samples 4 favoured RT_SCHED_LANE, by 8 - 13 %: a caller who runs exactly that may switch.
+ * rt_set_stats: as rt_dispatch_reflection_pbr; RT_STAT_REFLECTION_RAYS grows by (valid pixels) x samples.
+ * Errors (RT_E_INVALID, nothing written, rt_last_error naming the cause): every case of rt_dispatch_reflection_pbr
+ * that applies (NULL params, table, table->materials, out or radiance; samples, tmax or shadow_tmin out of range; a
+ * misaligned plane or map; nmaterials of 0 or above RT_MAX_MATERIALS; instance_material with ninstances 0; W or H of
+ * 0; a bad row list; no scene, camera or shading), and any flag bit other than RT_REFLECT_SHADOW_MODELS.
+ * No reference counterpart: the reference stands in for this light with a constant (Hit.hlsl:165). */
+rt_status rt_dispatch_indirect(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                               const rt_indirect_params* params, const rt_material_table* table,
+                               const rt_reflection_planes* out, void* hip_stream);
+
+/* Inputs of rt_shade_resolve_gi: rt_resolve_pbr_inputs' seven fields, exactly, and two more. */
+typedef struct {
+  const uint32_t* hits;   /* W*H x 4, rt_gbuffer.hits */
+  const float*    normal; /* W*H x 4, rt_gbuffer.normal */
+  const uint32_t* object; /* W*H x 2, rt_gbuffer.object */
+  const float*    vis;    /* nlights planes of W*H floats, or NULL: every light fully visible */
+  uint64_t        vis_stride; /* floats between planes; 0 = W*H */
+  const float*    ao;     /* W*H floats, or NULL: 1 */
+  const float*    refl;   /* W*H x 4 floats, rt_reflection_planes.radiance, 16-byte aligned, or NULL */
+  const float*    indirect;       /* W*H x 4 floats, rt_dispatch_indirect's radiance (filtered or not), 16-byte aligned,
+                                     or NULL */
+  float           indirect_scale; /* finite, >= 0 */
+} rt_resolve_gi_inputs;
+
+/* The PBR resolve with a diffuse indirect term: rt_shade_resolve_pbr's contract and arithmetic with one
+ * more term, added before the lerp towards refl, where `indirect` is given (ind = indirect[4i..4i+2]; .w is not read):
+ *   a model pixel: per channel colour = colour + ((km * albedo) * ind) * indirect_scale, km = 1.0f - metallic of the
+ *     pixel's material (a cosine-weighted estimator of the Lambert term is albedo x the mean incoming radiance; a metal
+ *     has no diffuse term);
+ *   a plane pixel: colour = c + ind * indirect_scale per channel (the plane program has no material: albedo 1);
+ *   a miss: unchanged.
+ * The 0.3f * a ambient share of s_l stays as it is. float32, no contraction, in the order written.
+ * The anchors: with indirect NULL, color_out and rgba8_out are rt_shade_resolve_pbr's bit for bit; so they are for a
+ * plane of zeros, and for indirect_scale == 0 with a finite plane (the surface sums start from +0, so no -0 arises).
+ * rt_host_shade_resolve_gi agrees to the bit.
+ * Errors, nothing written: rt_shade_resolve_pbr's cases, and RT_E_INVALID for a misaligned indirect (16 bytes), an
+ * indirect_scale that is not finite or is negative, an output equal to indirect. */
+rt_status rt_shade_resolve_gi(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_resolve_gi_inputs* in,
+                              const rt_material_table* table, float* color_out, void* rgba8_out, void* hip_stream);
+
 /* The weights of rt_reflection_composite: both finite, in [0, 1]. strength: the share of the reflection at F = 1;
  * f0: the Fresnel reflectance at normal incidence. */
 typedef struct { float strength; float f0; } rt_reflection_composite_params;
@@ -1343,6 +1419,22 @@ rt_status rt_host_reflection_radiance_pbr(const float* rays, const uint32_t* hit
                                           const rt_light* lights, uint32_t nlights,
                                           const rt_reflection_pbr_params* params, const rt_material_table* table,
                                           float* radiance_out, uint8_t* lit_out);
+
+/* The rays rt_dispatch_indirect traces for n pixels, on the host: rt_host_reflection_rays' arguments, results and
+ * conventions (rays_out n x samples x 8 floats, (P + d * 0.001f, 0.001f, d, tmax); valid_out n bytes or NULL; an
+ * invalid normal gets zero-filled rays; the caller leaves a primary miss out) with the pass's directions: those of
+ * rt_host_ao_rays for seed `seed ^ hash(0x200)`, bit for bit. It calls the functions the indirect kernels call. The
+ * pass's radiance twin is rt_host_reflection_radiance_pbr, unchanged, at roughness 0. Null arrays with n > 0 or bad
+ * params (rt_dispatch_indirect's ranges and flag rule): RT_E_INVALID, nothing written. */
+rt_status rt_host_indirect_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
+                                const uint32_t* py, uint32_t n, const rt_indirect_params* params, float* rays_out,
+                                uint8_t* valid_out);
+
+/* rt_shade_resolve_gi on host arrays: as rt_host_shade_resolve_pbr (every plane and table->instance_material a HOST
+ * array, no stream, the same checks less the 16-byte alignment), the same per-pixel function, so the same bits. */
+rt_status rt_host_shade_resolve_gi(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights, uint32_t nlights,
+                                   const rt_resolve_gi_inputs* in, const rt_material_table* table, float* color_out,
+                                   void* rgba8_out);
 
 /* rt_reflection_composite on host arrays: cb in place of the context's camera (rt_set_camera's layout; the origin and
  * the inverses are derived from it as rt_set_camera's are), no stream; the same checks less the 16-byte alignment

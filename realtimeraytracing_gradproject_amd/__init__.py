@@ -138,6 +138,21 @@ class rt_reflection_pbr_params(ctypes.Structure):
                 ("tmax", ctypes.c_float), ("shadow_tmin", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
+class rt_indirect_params(ctypes.Structure):
+    """include/rt_api.h rt_indirect_params: samples (1..64), seed, tmax, shadow_tmin and the flags
+    (RT_REFLECT_SHADOW_MODELS only) of rt_dispatch_indirect."""
+    _fields_ = [("samples", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("tmax", ctypes.c_float),
+                ("shadow_tmin", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
+class rt_resolve_gi_inputs(ctypes.Structure):
+    """include/rt_api.h rt_resolve_gi_inputs: rt_resolve_pbr_inputs' fields, the indirect pass's radiance plane and its
+    scale."""
+    _fields_ = [("hits", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("object", ctypes.c_void_p),
+                ("vis", ctypes.c_void_p), ("vis_stride", ctypes.c_uint64), ("ao", ctypes.c_void_p),
+                ("refl", ctypes.c_void_p), ("indirect", ctypes.c_void_p), ("indirect_scale", ctypes.c_float)]
+
+
 class rt_reflection_planes(ctypes.Structure):
     """include/rt_api.h rt_reflection_planes: the planes rt_dispatch_reflection writes (hits may be None)."""
     _fields_ = [("radiance", ctypes.c_void_p), ("hits", ctypes.c_void_p)]
@@ -240,6 +255,10 @@ SIGNATURES = [
                                     ctypes.POINTER(rt_reflection_planes), _P]),
     ("rt_dispatch_reflection_pbr", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_reflection_pbr_params),
                                         ctypes.POINTER(rt_material_table), ctypes.POINTER(rt_reflection_planes), _P]),
+    ("rt_dispatch_indirect", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_indirect_params),
+                                  ctypes.POINTER(rt_material_table), ctypes.POINTER(rt_reflection_planes), _P]),
+    ("rt_shade_resolve_gi", _I, [_P, _U32, _U32, ctypes.POINTER(rt_resolve_gi_inputs),
+                                 ctypes.POINTER(rt_material_table), _P, _P, _P]),
     ("rt_reflection_composite", _I, [_P, _U32, _U32, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P, _P,
                                      _P, _P, _P]),
     ("rt_denoise_guide", _I, [_P, _U32, _P, _P, _U32, _P, _P]),
@@ -313,6 +332,10 @@ SIGNATURES = [
                                              ctypes.POINTER(rt_material_table), _P, _P]),
     ("rt_host_reflection_composite", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P,
                                           _P, _P, _P]),
+    ("rt_host_indirect_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_indirect_params), _P, _P]),
+    ("rt_host_shade_resolve_gi", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_light), _U32,
+                                      ctypes.POINTER(rt_resolve_gi_inputs), ctypes.POINTER(rt_material_table), _P,
+                                      _P]),
     ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
     ("rt_host_ao_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rt_host_ao_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P]),
@@ -831,6 +854,64 @@ def host_reflection_radiance_pbr(rays, hits, hit_normal, hit_group, hit_inst, oc
     if st != RT_OK:
         raise RtError(st, "rt_host_reflection_radiance_pbr")
     return (out, lit) if want_lit else out
+
+
+def host_indirect_rays(cam_rays, t, normal, px, py, samples: int = 1, tmax: float = 1000.0, shadow_tmin: float = 0.01,
+                       seed: int = 0, flags: int = RT_REFLECT_SHADOW_MODELS):
+    """rt_host_indirect_rays: the rays rt_dispatch_indirect traces, on the host (no GPU): host_reflection_rays'
+    arguments and results with the pass's directions, cosine-weighted about the facing normal (host_ao_rays'
+    directions for seed `seed ^ hash(0x200)`, bit for bit). The pass's radiance twin is host_reflection_radiance_pbr
+    at roughness 0 with the same samples, seed, tmax, shadow_tmin and flags."""
+    cr = np.ascontiguousarray(cam_rays, dtype=np.float32).reshape(-1, 8)
+    n = cr.shape[0]
+    tt = _f32(t, n)
+    nr = _f32(normal, 4 * n)
+    x = np.ascontiguousarray(px, dtype=np.uint32).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if x.size != n or y.size != n:
+        raise ValueError(f"expected {n} pixel coordinates, got {x.size} and {y.size}")
+    if not 1 <= int(samples) <= 64:  # the function's own limit, checked before the output is sized by it
+        raise RtError(RT_E_INVALID, f"rt_host_indirect_rays: samples {samples} outside 1..64")
+    p = rt_indirect_params(samples, seed, tmax, shadow_tmin, flags)
+    rays = np.zeros((n, int(samples), 8), np.float32)
+    valid = np.zeros(n, np.uint8)
+    st = lib.rt_host_indirect_rays(_vp(cr), _vp(tt), _vp(nr), _vp(x), _vp(y), n, ctypes.byref(p), _vp(rays),
+                                   _vp(valid))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_indirect_rays")
+    return rays, valid
+
+
+def host_shade_resolve_gi(width: int, height: int, camera, lights, hits, normal, object, materials,  # noqa: A002
+                          instance_material=None, vis=None, ao=None, refl=None, indirect=None,
+                          indirect_scale: float = 1.0, want_rgba8: bool = False):
+    """rt_host_shade_resolve_gi: the PBR resolve with the indirect term on the host (no GPU). host_shade_resolve_pbr's
+    arguments, and indirect: (n, 4) float32, the indirect pass's radiance plane (filtered or not), or None;
+    indirect_scale: finite, >= 0. With indirect None the results are host_shade_resolve_pbr's bit for bit."""
+    n = width * height
+    cb = _f32(camera, 64)
+    arr = _lights_array(lights)
+    nl = len(arr)
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    oo = np.ascontiguousarray(object).view(np.uint32).reshape(-1)
+    if hh.size != 4 * n or oo.size != 2 * n:
+        raise ValueError(f"expected {4 * n} hit words and {2 * n} object words, got {hh.size} and {oo.size}")
+    nn = _f32(normal, 4 * n)
+    vv = None if vis is None else _f32(vis, nl * n)
+    aa = None if ao is None else _f32(ao, n)
+    rr = None if refl is None else _f32(refl, 4 * n)
+    ii = None if indirect is None else _f32(indirect, 4 * n)
+    mats, nm = _materials_array(materials)
+    im = None if instance_material is None else np.ascontiguousarray(instance_material, dtype=np.uint32).ravel()
+    inp = rt_resolve_gi_inputs(_vp(hh), _vp(nn), _vp(oo), _vp(vv), 0, _vp(aa), _vp(rr), _vp(ii), indirect_scale)
+    table = rt_material_table(mats, nm, _vp(im), 0 if im is None else im.size)
+    out = np.zeros((n, 4), np.float32)
+    out8 = np.zeros((n, 4), np.uint8) if want_rgba8 else None
+    st = lib.rt_host_shade_resolve_gi(width, height, _fptr(cb), arr, nl, ctypes.byref(inp), ctypes.byref(table),
+                                      _vp(out), _vp(out8))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_shade_resolve_gi")
+    return (out, out8) if want_rgba8 else out
 
 
 def host_reflection_composite(width: int, height: int, camera, color_in, radiance, hits, normal,
@@ -1714,6 +1795,64 @@ class Context:
         self._check(self._lib.rt_dispatch_reflection_pbr(self._h, width, height, rp, nr, ctypes.byref(p),
                                                          ctypes.byref(table), ctypes.byref(g), stream),
                     "rt_dispatch_reflection_pbr")
+
+    def _material_table(self, m: str, materials, instance_material):
+        """The rt_material_table of a call from set_shading-format materials and a device map (or None); the returned
+        array must outlive the call."""
+        mats, nm = _materials_array(materials)
+        ninst = 0
+        if instance_material is not None:
+            if isinstance(instance_material, int):
+                raise ValueError(f"{m}: instance_material must be a tensor (its length is the map's size)")
+            if instance_material.element_size() != 4 or not instance_material.is_contiguous():
+                raise ValueError(f"{m}: instance_material must be a contiguous tensor of 32-bit elements")
+            ninst = instance_material.numel()
+        return rt_material_table(mats, nm, _ptr(instance_material), ninst), mats
+
+    def dispatch_indirect(self, width: int, height: int, radiance, materials, instance_material=None,
+                          samples: int = 1, tmax: float = 1000.0, shadow_tmin: float = 0.01, seed: int = 0,
+                          flags: int = RT_REFLECT_SHADOW_MODELS, hits=None, rows: Optional[np.ndarray] = None,
+                          stream: Optional[int] = None):
+        """rt_dispatch_indirect: one bounce of diffuse indirect light for the frame dispatch_gbuffer describes, 4 floats
+        per pixel (nrows * width entries in dispatch()'s compact row order): the mean colour of `samples` (1..64)
+        cosine-weighted rays about the facing normal, each shaded as dispatch_reflection_pbr shades a reflection ray
+        (the hit instance's material; the miss colour where it hits nothing), and in .w their mean distance; four zeros
+        on a primary miss. materials, instance_material, hits: as for dispatch_reflection_pbr. flags:
+        RT_REFLECT_SHADOW_MODELS (the default: an unshadowed bounce leaks light) or 0. The plane feeds
+        radiance_accumulate / radiance_atrous and then shade_resolve_gi(indirect=...). host_indirect_rays gives the rays,
+        host_reflection_radiance_pbr (roughness 0) the plane."""
+        m = "dispatch_indirect"
+        rp, nr, _keep = self._rows_arg(rows, height)
+        g = rt_reflection_planes()
+        self._set_planes(g, m, nr * width, (("radiance", radiance, 4), ("hits", hits, 4)))
+        table, _mats = self._material_table(m, materials, instance_material)
+        p = rt_indirect_params(samples, seed, tmax, shadow_tmin, flags)
+        self._check(self._lib.rt_dispatch_indirect(self._h, width, height, rp, nr, ctypes.byref(p),
+                                                   ctypes.byref(table), ctypes.byref(g), stream),
+                    "rt_dispatch_indirect")
+
+    def shade_resolve_gi(self, width: int, height: int, hits, normal, object, color_out, materials,  # noqa: A002
+                         instance_material=None, vis=None, ao=None, refl=None, rgba8_out=None, vis_stride: int = 0,
+                         stream: Optional[int] = None, nlights: Optional[int] = None, indirect=None,
+                         indirect_scale: float = 1.0):
+        """rt_shade_resolve_gi: shade_resolve_pbr with a diffuse indirect term. indirect: dispatch_indirect's radiance
+        plane (width * height x 4 floats, filtered or not) or None; where given, a model pixel gains
+        ((1 - metallic) * albedo) * indirect * indirect_scale per channel before the lerp towards refl, a plane pixel
+        indirect * indirect_scale, a miss nothing. indirect_scale: finite, >= 0. With indirect None, a plane of zeros
+        or scale 0 the frame is shade_resolve_pbr's bit for bit."""
+        n, m = width * height, "shade_resolve_gi"
+        self._vis_planes(m, vis, n, vis_stride, nlights)
+        inp = rt_resolve_gi_inputs(self._plane(m, "hits", hits, 4 * n), self._plane(m, "normal", normal, 4 * n),
+                                   self._plane(m, "object", object, 2 * n), _ptr(vis), vis_stride,
+                                   self._plane(m, "ao", ao, n), self._plane(m, "refl", refl, 4 * n),
+                                   self._plane(m, "indirect", indirect, 4 * n), indirect_scale)
+        table, _mats = self._material_table(m, materials, instance_material)
+        out8 = rgba8_out.view(torch.int32) if isinstance(rgba8_out, torch.Tensor) and rgba8_out.dtype == torch.uint8 \
+            else rgba8_out
+        self._check(self._lib.rt_shade_resolve_gi(self._h, width, height, ctypes.byref(inp), ctypes.byref(table),
+                                                  self._plane(m, "color_out", color_out, 4 * n),
+                                                  self._plane(m, "rgba8_out", out8, n), stream),
+                    "rt_shade_resolve_gi")
 
     def reflection_composite(self, width: int, height: int, color_in, radiance, hits, normal, color_out,
                              strength: float = 1.0, f0: float = 0.04, rgba8_out=None, stream: Optional[int] = None):

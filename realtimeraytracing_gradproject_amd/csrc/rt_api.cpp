@@ -2767,6 +2767,57 @@ rt_status rt_shade_resolve_pbr(rt_ctx_t c, uint32_t W, uint32_t H, const rt_reso
   return RT_OK;
 }
 
+// ---- PBR resolve with the indirect term: the PBR resolve's check on the seven fields the two input
+// structures share, then the indirect plane and its scale; shared by rt_shade_resolve_gi and rt_host_shade_resolve_gi
+namespace {
+
+rt_resolve_pbr_inputs resolve_gi_base(const rt_resolve_gi_inputs* in) {
+  return {in->hits, in->normal, in->object, in->vis, in->vis_stride, in->ao, in->refl};
+}
+
+const char* resolve_gi_args_error(uint32_t W, uint32_t H, const rt_resolve_gi_inputs* in,
+                                  const rt_material_table* table, const float* color_out, const void* rgba8_out,
+                                  bool align, rt_status* st) {
+  rt_resolve_pbr_inputs base = {};
+  if (in) base = resolve_gi_base(in);
+  if (const char* why = resolve_pbr_args_error(W, H, in ? &base : nullptr, table, color_out, rgba8_out, align, st))
+    return why;
+  if (misaligned(in->indirect, align ? 16 : 4)) return "indirect plane misaligned";
+  if (!std::isfinite(in->indirect_scale) || !(in->indirect_scale >= 0.0f)) return "indirect_scale not finite and >= 0";
+  for (const void* o : {(const void*)color_out, rgba8_out})
+    if (o && o == in->indirect) return "an output is an input plane";
+  return nullptr;
+}
+
+rt::ResolveGi resolve_gi_of(uint32_t W, uint32_t H, const float cb[64], const rt::LightRec* lights, uint32_t nlights,
+                            const rt_resolve_gi_inputs* in, const rt_material_table* table, float* color_out,
+                            void* rgba8_out) {
+  const rt_resolve_pbr_inputs base = resolve_gi_base(in);
+  rt::ResolveGi g = {};
+  g.r = resolve_pbr_of(W, H, cb, lights, nlights, &base, table, color_out, rgba8_out);
+  g.indirect = in->indirect;
+  g.indirect_scale = in->indirect_scale;
+  return g;
+}
+
+}  // namespace
+
+rt_status rt_shade_resolve_gi(rt_ctx_t c, uint32_t W, uint32_t H, const rt_resolve_gi_inputs* in,
+                              const rt_material_table* table, float* color_out, void* rgba8_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = resolve_gi_args_error(W, H, in, table, color_out, rgba8_out, true, &st))
+    return fail(c, st, std::string("rt_shade_resolve_gi: ") + why);
+  if (!c->have_camera) return fail(c, RT_E_INVALID, "rt_shade_resolve_gi: camera not set");
+  if (!c->have_shading) return fail(c, RT_E_INVALID, "rt_shade_resolve_gi: shading not set");
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_shade_resolve_gi(
+      resolve_gi_of(W, H, c->cam_cb, c->fp.lights, c->fp.nlights, in, table, color_out, rgba8_out),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "GI resolve launch");
+  return RT_OK;
+}
+
 // ---- PBR reflection pass: rt_dispatch_reflection's checks and launch sequence around the PBR
 // reflection kernels, with the PBR resolve's table rules. The checks of the parameters and of the table are shared
 // with the host twins ------------------------------------------------------------------------------------------
@@ -2831,6 +2882,43 @@ rt_status rt_dispatch_reflection_pbr(rt_ctx_t c, uint32_t W, uint32_t H, const u
   pp.rp.radiance = out->radiance;
   pp.rp.hits = out->hits;
   return grid_pass_launch(c, fn, W, H, rows, nrows, stream, pp, pp.rp.gb, "PBR reflection launch");
+}
+
+// ---- Diffuse indirect pass: rt_dispatch_reflection_pbr's checks and launch sequence around the
+// indirect kernels. The parameter check is shared with rt_host_indirect_rays; it leaves the PBR reflection pass's
+// parameters (roughness 0) in *pbr, which are the radiance twin's -----------------------------------------------
+namespace {
+
+const char* indirect_params_error(const rt_indirect_params* p, rt_reflection_pbr_params* pbr) {
+  if (!p) return "null params";
+  *pbr = {p->samples, p->seed, 0.0f, p->tmax, p->shadow_tmin, p->flags};
+  if (p->flags & ~(uint32_t)RT_REFLECT_SHADOW_MODELS) return "a flag other than RT_REFLECT_SHADOW_MODELS";
+  rt_reflection_params base;
+  return reflection_pbr_params_error(pbr, &base);
+}
+
+}  // namespace
+
+rt_status rt_dispatch_indirect(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                               const rt_indirect_params* params, const rt_material_table* table,
+                               const rt_reflection_planes* out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  const std::string fn = "rt_dispatch_indirect";
+  rt_reflection_pbr_params pbr;
+  if (const char* why = indirect_params_error(params, &pbr)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (const char* why = material_table_error(table)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (!out) return fail(c, RT_E_INVALID, fn + ": null output planes");
+  if (!out->radiance) return fail(c, RT_E_INVALID, fn + ": null radiance plane");
+  if ((uintptr_t)out->radiance % 16u) return fail(c, RT_E_INVALID, fn + ": radiance plane not aligned to 16 bytes");
+  if ((uintptr_t)out->hits % 16u) return fail(c, RT_E_INVALID, fn + ": hits plane not aligned to 16 bytes");
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  if (st != RT_OK) return st;
+  if (!c->have_shading) return fail(c, RT_E_INVALID, fn + ": shading not set");
+  rt::IndirectParams ip = {};
+  reflection_pbr_of(&pbr, table, c->fp.lights, c->fp.nlights, ip.pp);
+  ip.pp.rp.radiance = out->radiance;
+  ip.pp.rp.hits = out->hits;
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, ip, ip.pp.rp.gb, "indirect launch");
 }
 
 // ---- Fresnel composite: the argument check shared by rt_reflection_composite and
@@ -3599,6 +3687,57 @@ rt_status rt_host_reflection_radiance_pbr(const float* rays, const uint32_t* hit
     }
     rt::reflection_reduce(sum, S, out);
   }
+  return RT_OK;
+}
+
+// Host service: the rays rt_dispatch_indirect traces for n pixels: rt_host_ao_rays' facing normal and directions under
+// indirect_base, rt_host_reflection_rays' origin rule, from the functions the indirect kernels call and in their order
+// of operations. The pass's radiance twin is rt_host_reflection_radiance_pbr at roughness 0. No context, no GPU call.
+rt_status rt_host_indirect_rays(const float* cam_rays, const float* t, const float* normal, const uint32_t* px,
+                                const uint32_t* py, uint32_t n, const rt_indirect_params* params, float* rays_out,
+                                uint8_t* valid_out) {
+  rt_reflection_pbr_params pbr;
+  if (indirect_params_error(params, &pbr) || (n && (!cam_rays || !t || !normal || !px || !py || !rays_out)))
+    return RT_E_INVALID;
+  const uint32_t S = params->samples;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* cr = cam_rays + 8 * (size_t)i;
+    const float* nr = normal + 4 * (size_t)i;
+    float* out = rays_out + 8 * (size_t)i * S;
+    const rt::V3 O = rt::v3(cr[0], cr[1], cr[2]), D = rt::v3(cr[4], cr[5], cr[6]), nv = rt::v3(nr[0], nr[1], nr[2]);
+    const bool valid = rt::ao_normal_valid(nv);
+    if (valid_out) valid_out[i] = valid ? 1 : 0;
+    if (!valid) {
+      std::memset(out, 0, sizeof(float) * 8 * (size_t)S);
+      continue;
+    }
+    const rt::V3 nf = rt::ao_facing_normal(nv, D);
+    const rt::V3 P = rt::add(O, rt::muls(D, t[i]));
+    const uint32_t base = rt::indirect_base(px[i], py[i], params->seed);
+    for (uint32_t k = 0; k < S; ++k) {
+      const rt::V3 d = rt::ao_direction(nf, rt::ao_sphere(base, k));
+      const rt::V3 ro = rt::reflection_origin(P, d);
+      float* r = out + 8 * (size_t)k;
+      r[0] = ro.x, r[1] = ro.y, r[2] = ro.z, r[3] = 0.001f;
+      r[4] = d.x, r[5] = d.y, r[6] = d.z, r[7] = params->tmax;
+    }
+  }
+  return RT_OK;
+}
+
+// Host service: rt_shade_resolve_gi on host arrays through resolve_gi_pixel, the function k_shade_resolve_gi calls,
+// after the device entry point's argument checks (less the 16-byte alignment); maps and table as in
+// rt_host_shade_resolve_pbr. No context, no GPU call.
+rt_status rt_host_shade_resolve_gi(uint32_t W, uint32_t H, const float cb[64], const rt_light* lights, uint32_t nlights,
+                                   const rt_resolve_gi_inputs* in, const rt_material_table* table, float* color_out,
+                                   void* rgba8_out) {
+  rt_status st = RT_OK;
+  if (resolve_gi_args_error(W, H, in, table, color_out, rgba8_out, false, &st)) return st;
+  if (!cb || !lights || nlights < 1 || nlights > (uint32_t)rt::kMaxLights) return RT_E_INVALID;
+  const rt::ResolveGi g = resolve_gi_of(W, H, cb, reinterpret_cast<const rt::LightRec*>(lights), nlights, in, table,
+                                        color_out, rgba8_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::resolve_gi_pixel(g, x, y);
   return RT_OK;
 }
 

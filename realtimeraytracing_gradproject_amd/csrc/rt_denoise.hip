@@ -24,6 +24,8 @@
 //                       planes, the reflection pass's radiance and an instance -> material map -> the colour frame of
 //                       the RT_SHADE_REF hit programs. The lights, the camera and the material table (32 entries of
 //                       60 B) ride in the kernel argument.
+//   k_shade_resolve_gi  the same with the indirect pass's radiance plane (rt_shade_resolve_gi): one more
+//                       16-byte load per surface pixel, the diffuse term added before the lerp.
 //   k_radiance_accumulate   the radiance filter's temporal pass (rt_radiance_accumulate), one pixel per
 //                       lane over 32 x 8 tiles: k_ao_accumulate's reprojection over 4-float radiance entries and the
 //                       luminance moments (a tap costs two 16-byte loads plus the guide's); the 25-tap spatial variance
@@ -34,7 +36,8 @@
 //                       the halo of 2 covers the 3 x 3 variance prefilter, which sits on the same lattice.
 //
 // The arithmetic of all of them is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
-// resolve_pixel, reflection_composite_pixel, resolve_pbr_pixel, radiance_accumulate_pixel, radiance_atrous_pixel),
+// resolve_pixel, reflection_composite_pixel, resolve_pbr_pixel, resolve_gi_pixel, radiance_accumulate_pixel,
+// radiance_atrous_pixel),
 // which the host twins in rt_api.cpp call too: the
 // kernels differ from them in where a value is read, never in how it is used.
 // Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
@@ -176,6 +179,15 @@ __global__ __launch_bounds__(256) void k_shade_resolve_pbr(ResolvePbr r) {
   resolve_pbr_pixel(r, i % r.W, i / r.W);
 }
 
+// k_shade_resolve_pbr with the indirect term (rt_shade_resolve_gi): one more 16-byte load per surface
+// pixel where the plane is given (a wave-uniform test of the kernel argument), none on a miss.
+static_assert(sizeof(ResolveGi) <= 4096, "rt_shade_resolve_gi's launch must fit the 4 KB kernel-argument segment");
+__global__ __launch_bounds__(256) void k_shade_resolve_gi(ResolveGi g) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= g.r.W * g.r.H) return;
+  resolve_gi_pixel(g, i % g.r.W, i / g.r.W);
+}
+
 __global__ __launch_bounds__(256) void k_radiance_accumulate(RadTemporal a, uint32_t tiles_x) {
   const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
   const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
@@ -314,6 +326,11 @@ uint32_t tiles(uint32_t n, uint32_t t) { return (n + t - 1u) / t; }
 
 hipError_t launch_shade_resolve_pbr(const ResolvePbr& r, hipStream_t stream) {
   hipLaunchKernelGGL(k_shade_resolve_pbr, dim3(tiles(r.W * r.H, 256u)), dim3(256), 0, stream, r);
+  return hipGetLastError();
+}
+
+hipError_t launch_shade_resolve_gi(const ResolveGi& g, hipStream_t stream) {
+  hipLaunchKernelGGL(k_shade_resolve_gi, dim3(tiles(g.r.W * g.r.H, 256u)), dim3(256), 0, stream, g);
   return hipGetLastError();
 }
 

@@ -1553,7 +1553,14 @@ RT_HD V3 surface_pbr(const MaterialEntry& e, const LightRec* lights, uint32_t nl
 //   any other group: surface_pbr with the material of the pixel's instance (object[2i] through instance_material, 0
 //   where either index is out of range), then HLSL's lerp towards refl by the material's reflectivity where that is
 //   not 0 and the normal is valid (ao_normal_valid, rt_dispatch_reflection's rule).
-RT_HD void resolve_pbr_pixel(const ResolvePbr& r, uint32_t x, uint32_t y) {
+//
+// rt_shade_resolve_gi is the same pixel with one more term where `indirect` (the indirect pass's radiance
+// plane) is given, added before the lerp: a model pixel col + ((km * albedo) * ind) * scale per channel with
+// km = 1.0f - metallic (a cosine-weighted estimator of the Lambert term is albedo times the mean incoming radiance; a
+// metal has no diffuse term), a plane pixel c + ind * scale (the plane program has no material: albedo 1), a miss
+// nothing; the plane's entry is loaded for surface pixels only. resolve_pbr_pixel passes a constant null plane, so
+// its instructions are what they were before the term existed.
+RT_HD void resolve_pbr_body(const ResolvePbr& r, uint32_t x, uint32_t y, const float* indirect, float indirect_scale) {
   const size_t i = (size_t)y * r.W + x;
   float h[4];
   ld4(reinterpret_cast<const float*>(r.hits) + 4 * i, h);  // bits only: (t, instance id, primitive, hit flag)
@@ -1578,12 +1585,25 @@ RT_HD void resolve_pbr_pixel(const ResolvePbr& r, uint32_t x, uint32_t y) {
       const float li = maxf(0.0f, dot(n, ldir));
       const float c = (1.0f * li) * s;
       col = v3(c, c, c);
+      if (indirect) {
+        float q[4];
+        ld4(indirect + 4 * i, q);
+        col = v3(c + q[0] * indirect_scale, c + q[1] * indirect_scale, c + q[2] * indirect_scale);
+      }
     } else {  // ClosestHit, Hit.hlsl:183-204
       uint32_t m = 0u;
       if (r.instance_material && inst < r.ninstances) m = r.instance_material[inst];
       if (m >= r.nmaterials) m = 0u;
       const MaterialEntry& e = r.table[m];
       col = surface_pbr(e, r.lights, r.nlights, P, n, O, a, vis, r.vis_stride);
+      if (indirect) {
+        float q[4];
+        ld4(indirect + 4 * i, q);
+        const float km = 1.0f - e.m.metallic;
+        col = v3(col.x + ((km * e.m.albedo[0]) * q[0]) * indirect_scale,
+                 col.y + ((km * e.m.albedo[1]) * q[1]) * indirect_scale,
+                 col.z + ((km * e.m.albedo[2]) * q[2]) * indirect_scale);
+      }
       const float rf = e.m.reflectivity;
       if (r.refl && rf != 0.0f && ao_normal_valid(n)) {
         float q[4];
@@ -1598,6 +1618,17 @@ RT_HD void resolve_pbr_pixel(const ResolvePbr& r, uint32_t x, uint32_t y) {
   const float out[4] = {col.x, col.y, col.z, 1.0f};
   st4(r.color_out + 4 * i, out);
   if (r.rgba8_out) r.rgba8_out[i] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | (255u << 24);
+}
+RT_HD void resolve_pbr_pixel(const ResolvePbr& r, uint32_t x, uint32_t y) { resolve_pbr_body(r, x, y, nullptr, 0.0f); }
+
+// rt_shade_resolve_gi's launch: rt_shade_resolve_pbr's, the indirect plane (may be null) and its scale.
+struct ResolveGi {
+  ResolvePbr r;
+  const float* indirect;
+  float indirect_scale;
+};
+RT_HD void resolve_gi_pixel(const ResolveGi& g, uint32_t x, uint32_t y) {
+  resolve_pbr_body(g.r, x, y, g.indirect, g.indirect_scale);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1713,6 +1744,25 @@ RT_HD V3 surface_split_end(const SurfaceSplit& st) {
 // A model hit's factor of one light: the frame kernels' occl ? 0.3f : 1.0f where RT_REFLECT_SHADOW_MODELS traced a
 // shadow ray that found an occluder, 1.0f everywhere else (the reference's ClosestHit traces none).
 RT_HD float reflection_model_factor(bool occluded) { return occluded ? 0.3f : 1.0f; }
+
+// ------------------------------------------------------------------------------------------
+// The diffuse indirect pass (rt_dispatch_indirect): one bounce of cosine-weighted rays about the facing
+// normal, each shaded as a PBR reflection ray is. It has no arithmetic of its own: the directions are the AO pass's
+// (ao_facing_normal, ao_sphere, ao_direction) under a seed of this pass's own, the origin, the per-ray colour, the
+// reduction and the planes the PBR reflection pass's. Called by the indirect kernels per lane and by
+// rt_host_indirect_rays per pixel; the radiance twin is rt_host_reflection_radiance_pbr, unchanged;
+// tests/indirect_reference.py restates the ray rule in numpy.
+// ------------------------------------------------------------------------------------------
+
+// rt_dispatch_indirect's launch: the PBR reflection pass's (pp.rp.roughness is not read, pp.flags holds
+// RT_REFLECT_SHADOW_MODELS or nothing). A type of its own, which picks the indirect kernels.
+struct IndirectParams {
+  ReflectionPbrParams pp;
+};
+
+// The hash base of a pixel's indirect samples: the AO pass's base under a seed of the pass's own (the reflection
+// passes use 0x100, the shadow pass l + 1 <= 16).
+RT_HD uint32_t indirect_base(uint32_t px, uint32_t py, uint32_t seed) { return ao_base(px, py, seed ^ ao_hash(0x200u)); }
 
 // ------------------------------------------------------------------------------------------
 // Temporal upscaler (rt_upscale): the per-pixel arithmetic, called by the kernels of rt_upscale.hip per

@@ -202,7 +202,8 @@ bool gbuffer_packet(const SceneView& scene, int schedule);
 //   ShadowParams         rt_dispatch_shadow (§3.13): params.vis's planes are written
 //   ReflectionParams     rt_dispatch_reflection (§3.14): params.radiance and, when given, params.hits are written
 //   ReflectionPbrParams  rt_dispatch_reflection_pbr (§3.16): likewise; the material table rides in the kernel argument
-// The last four read the camera and the frame size of their params.gb and none of its planes.
+//   IndirectParams       rt_dispatch_indirect (§3.18): likewise, around the cosine-weighted rays of the indirect kernels
+// The last five read the camera and the frame size of their params.gb and none of its planes.
 template <typename P>
 hipError_t launch_grid_pass(const SceneView& scene, const P& params, const uint32_t* d_rows,
                             unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);
@@ -216,6 +217,9 @@ hipError_t launch_shade_resolve(const Resolve& r, hipStream_t stream);
 // One launch, one pixel per lane; no scene, no scratch. Its per-pixel arithmetic is rt_device.hpp's resolve_pbr_pixel,
 // shared with rt_host_shade_resolve_pbr; the material table rides in the kernel argument.
 hipError_t launch_shade_resolve_pbr(const ResolvePbr& r, hipStream_t stream);
+// The same with the indirect term (rt_shade_resolve_gi): resolve_gi_pixel, shared with
+// rt_host_shade_resolve_gi.
+hipError_t launch_shade_resolve_gi(const ResolveGi& g, hipStream_t stream);
 
 // --- Deferred reflections (rt_trace.hip, rt_denoise.hip) -----------------------
 // The reflection passes are launch_grid_pass's, above. The composite (rt_reflection_composite): one launch, one pixel

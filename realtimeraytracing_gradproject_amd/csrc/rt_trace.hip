@@ -1953,6 +1953,7 @@ __host__ __device__ __forceinline__ const GbufParams& gbuf(const AoParams& p) { 
 __host__ __device__ __forceinline__ const GbufParams& gbuf(const ShadowParams& p) { return p.gb; }
 __host__ __device__ __forceinline__ const GbufParams& gbuf(const ReflectionParams& p) { return p.gb; }
 __host__ __device__ __forceinline__ const GbufParams& gbuf(const ReflectionPbrParams& p) { return p.rp.gb; }
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const IndirectParams& p) { return p.pp.rp.gb; }
 
 // The opening of every kernel on the G-buffer's grid, once per schedule: the lane's pixel, its camera ray and the
 // primary closest-hit walk. x: the pixel's column, orow: its entry of the row list (and of the planes: entry
@@ -2558,6 +2559,175 @@ __global__ __launch_bounds__(kBlock) void k_trace_reflection_pbr(SceneView sc, R
         ReflectionSum sum = reflection_sum_zero();
         for (uint32_t k = 0; k < rp.samples; ++k) {
           const V3 d = reflection_direction(m, nf, rp.roughness, base, k);
+          const V3 ro = reflection_origin(P, d);
+          if (STATS) ++cnt.refl;
+          HitRec h;
+          const bool f = trace<false, STATS, true, TT>(sc, ro, d, 0.001f, rp.tmax, h, stk, cnt);
+          if (k == 0u) rec0 = reflection_record(f, h, rp.tmax);
+          if (!f) {
+            reflection_sum_add(sum, sky, rp.tmax);
+            continue;
+          }
+          bool plane;
+          const V3 n2 = hit_normal(sc, h, plane);
+          const V3 P2 = add(ro, muls(d, h.t));
+          if (plane) {
+            const LightRec& L0 = rp.lights[0];
+            const V3 lp = light_pos(L0);
+            const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+            if (STATS) ++cnt.shadow;
+            HitRec hs;
+            const bool occ = trace<true, STATS, false, TT>(sc, P2, sd, rp.shadow_tmin, 100000.0f, hs, stk, cnt);
+            const float c = reflection_plane_color(n2, lp, P2, occ);
+            reflection_sum_add(sum, v3(c, c, c), h.t);
+            continue;
+          }
+          const uint32_t mi = material_index(pp.instance_material, pp.ninstances, pp.nmaterials, h.inst);
+          SurfaceSplit st = surface_split_begin(pp.table[mi], P2, n2, ro);
+          for (uint32_t l = 0; l < rp.nlights; ++l) {
+            const LightRec& Lr = rp.lights[l];
+            const V3 lp = light_pos(Lr);
+            V3 L;
+            float nl;
+            bool occ = false;
+            if (shadow_models && shadow_lit(neg(n2), lp, P2, L, nl)) {
+              const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+              if (STATS) ++cnt.shadow;
+              HitRec hs;
+              occ = trace<true, STATS, false, TT>(sc, P2, sd, rp.shadow_tmin, 100000.0f, hs, stk, cnt);
+            }
+            surface_split_light(st, pp.table[mi], Lr, P2, n2, reflection_model_factor(occ));
+          }
+          reflection_sum_add(sum, surface_split_end(st), h.t);
+        }
+        reflection_reduce(sum, rp.samples, out);
+      }
+    }
+    reflection_store(rp, g.orow * gb.width + g.x, out, rec0);
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
+// ------------------------------------------------------------------------------------------
+// Diffuse indirect pass (rt_dispatch_indirect): the PBR reflection kernels' launch shapes, primary walk,
+// per-ray shading, reduction and planes around other rays: S cosine-weighted closest-hit rays about the facing normal
+// (the AO pass's generator under indirect_base), the widest rays any pass traces. Kernels of their own, so the PBR
+// reflection kernels keep their instructions; the pass has no mirror vector, no roughness and one flag
+// (RT_REFLECT_SHADOW_MODELS, a wave-uniform run-time value). Which schedule these rays favour is measured in DESIGN
+// §3.18; nothing switches by itself.
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(SceneView) + sizeof(IndirectParams) + 2 * sizeof(void*) <= 4096,
+              "rt_dispatch_indirect's launch must fit the 4 KB kernel-argument segment");
+
+// Packet schedule: k_trace_reflection_pbr_packet's with the AO packet kernel's ray generation.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_REFLECT_SGPR_ATTR
+void k_trace_indirect_packet(SceneView sc, IndirectParams ip, const uint32_t* __restrict__ rows,
+                             unsigned long long* __restrict__ stats) {
+  const ReflectionPbrParams& pp = ip.pp;
+  const ReflectionParams& rp = pp.rp;
+  const GbufParams& gb = rp.gb;
+  RT_GRID_PACKET_PRIMARY(gb);
+  bool need = false;
+  V3 nf = v3(0.0f, 0.0f, 1.0f), P = O;  // a dead lane's ray: finite, never traced
+  if (inimg && found) {
+    const V3 n = ao_normal(sc, hit);
+    if (ao_normal_valid(n)) {
+      need = true;
+      nf = ao_facing_normal(n, D);
+      P = add(O, muls(D, hit.t));  // GetWorldHitPoint, the frame's expression
+    }
+  }
+  const bool shadow_models = (pp.flags & kReflectShadowModels) != 0u;  // uniform
+  const uint32_t base = indirect_base(x, py, rp.seed);
+  const uint32_t ns = wave_ballot(need) ? rp.samples : 0u;  // uniform
+  const V3 sky = reflection_miss_color(py, gb.fheight);
+  ReflectionSum sum = reflection_sum_zero();
+  uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t k = 0; k < ns; ++k) {
+    V3 d = ao_direction(nf, ao_sphere(base, k));
+    V3 ro = reflection_origin(P, d);
+    if (STATS && need) ++cnt.refl;
+    HitRec h;
+    bool f;
+    trace_packet<false, STATS, 1, true, TT>(sc, &ro, &d, 0.001f, rp.tmax, &need, &f, &h, cnt);
+    const bool rh = need && f;
+    if (k == 0u && need) rec0 = reflection_record(f, h, rp.tmax);
+    V3 n2 = v3(0.0f, 0.0f, 1.0f), P2 = ro;  // a lane without a hit: finite, shades nothing
+    bool plane = false;
+    uint32_t mi = 0u;
+    if (rh) {
+      n2 = hit_normal(sc, h, plane);
+      P2 = add(ro, muls(d, h.t));
+      mi = material_index(pp.instance_material, pp.ninstances, pp.nmaterials, h.inst);
+    }
+    const bool model = rh && !plane, floor = rh && plane;
+    SurfaceSplit st{};
+    if (model) st = surface_split_begin(pp.table[mi], P2, n2, ro);
+    float cp = 0.0f;
+    for (uint32_t l = 0; l < rp.nlights; ++l) {
+      const LightRec& Lr = rp.lights[l];
+      const V3 lp = light_pos(Lr);
+      V3 L;
+      float nl;
+      const bool lit = shadow_models && model && shadow_lit(neg(n2), lp, P2, L, nl);
+      const bool tr = lit || (floor && l == 0u);
+      bool occ = false;
+      if (wave_ballot(tr)) {  // uniform
+        V3 sd = v3(0.0f, 0.0f, 1.0f);  // a dead lane's ray: finite, never traced
+        if (tr) sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+        if (STATS && tr) ++cnt.shadow;
+        HitRec hs;
+        bool o;
+        trace_packet<true, STATS, 1, false, TT>(sc, &P2, &sd, rp.shadow_tmin, 100000.0f, &tr, &o, &hs, cnt);
+        occ = tr && o;
+      }
+      if (floor && l == 0u) cp = reflection_plane_color(n2, lp, P2, occ);
+      if (model) surface_split_light(st, pp.table[mi], Lr, P2, n2, reflection_model_factor(occ));
+    }
+    V3 col = sky;
+    if (floor) col = v3(cp, cp, cp);
+    if (model) col = surface_split_end(st);
+    if (need) reflection_sum_add(sum, col, rh ? h.t : rp.tmax);
+  }
+  if (inimg) {
+    const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (need) reflection_reduce(sum, rp.samples, out);
+    reflection_store(rp, o, out, rec0);
+  }
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// Per-lane schedule: k_trace_reflection_pbr's with the AO per-lane kernel's ray generation.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_indirect(SceneView sc, IndirectParams ip,
+                                                           const uint32_t* __restrict__ rows,
+                                                           unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const ReflectionPbrParams& pp = ip.pp;
+  const ReflectionParams& rp = pp.rp;
+  const GbufParams& gb = rp.gb;
+  GridLane g;
+  Counters cnt;
+  if (grid_lane_pixel(gb, g)) {
+    LaneStack stk;
+    V3 O, D;
+    HitRec hit;
+    const bool found = grid_lane_primary<STATS, TT>(sc, gb, rows, s_stack, g, stk, O, D, hit, cnt);
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+    if (found) {
+      const V3 n = ao_normal(sc, hit);
+      if (ao_normal_valid(n)) {
+        const V3 nf = ao_facing_normal(n, D);
+        const V3 P = add(O, muls(D, hit.t));
+        const bool shadow_models = (pp.flags & kReflectShadowModels) != 0u;
+        const uint32_t base = indirect_base(g.x, g.py, rp.seed);
+        const V3 sky = reflection_miss_color(g.py, gb.fheight);
+        ReflectionSum sum = reflection_sum_zero();
+        for (uint32_t k = 0; k < rp.samples; ++k) {
+          const V3 d = ao_direction(nf, ao_sphere(base, k));
           const V3 ro = reflection_origin(P, d);
           if (STATS) ++cnt.refl;
           HitRec h;
@@ -3287,6 +3457,10 @@ template <bool S, int T>
 GridKernel<ReflectionPbrParams> grid_kernel(const ReflectionPbrParams&, bool packet) {
   return packet ? k_trace_reflection_pbr_packet<S, T> : k_trace_reflection_pbr<S, T>;
 }
+template <bool S, int T>
+GridKernel<IndirectParams> grid_kernel(const IndirectParams&, bool packet) {
+  return packet ? k_trace_indirect_packet<S, T> : k_trace_indirect<S, T>;
+}
 
 // The packet kernel's plain grid (a workgroup = RT_PACKET_WX x RT_PACKET_WY tiles of 8 x 8 pixels), or the per-lane
 // kernel's 16 x 16 pixel workgroups with their LDS stacks.
@@ -3317,6 +3491,8 @@ template hipError_t launch_grid_pass(const SceneView&, const ShadowParams&, cons
 template hipError_t launch_grid_pass(const SceneView&, const ReflectionParams&, const uint32_t*, unsigned long long*,
                                      bool, int, hipStream_t);
 template hipError_t launch_grid_pass(const SceneView&, const ReflectionPbrParams&, const uint32_t*, unsigned long long*,
+                                     bool, int, hipStream_t);
+template hipError_t launch_grid_pass(const SceneView&, const IndirectParams&, const uint32_t*, unsigned long long*,
                                      bool, int, hipStream_t);
 
 hipError_t launch_assemble_strips(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
