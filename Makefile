@@ -181,8 +181,11 @@ $(ASAN)/obj_ingest_fuzz: tools/obj_ingest_fuzz.cpp $(ASAN)/rt_host.o | $(ASAN)
 #   asan-indirect        the indirect pass's host twins (rt_host_indirect_rays against rt_host_ao_rays' directions,
 #                        rt_host_shade_resolve_gi with every subset of the optional planes and its anchors against
 #                        rt_host_shade_resolve_pbr, on exact-size heap blocks)
+#   asan-reflmotion      the reflection motion plane's host twin (rt_host_reflection_motion: the history taps at
+#                        virtual points in and far out of the frame, the stride-4 distance read and the class bytes, on
+#                        exact-size heap blocks)
 ASAN_CHECKS := asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials asan-reflection-pbr \
-               asan-radiance asan-indirect
+               asan-radiance asan-indirect asan-reflmotion
 asan-ao: $(ASAN)/ao_rays_check
 asan-denoise: $(ASAN)/denoise_check
 asan-upscale: $(ASAN)/upscale_check
@@ -192,6 +195,7 @@ asan-materials: $(ASAN)/materials_check
 asan-reflection-pbr: $(ASAN)/reflection_pbr_check
 asan-radiance: $(ASAN)/radiance_check
 asan-indirect: $(ASAN)/indirect_check
+asan-reflmotion: $(ASAN)/reflmotion_check
 
 $(ASAN)/rt_api.o: $(SRC)/rt_api.cpp $(HDRS) | $(ASAN)
 	$(HIPCC) $(HIPFLAGS) -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -c $< -o $@

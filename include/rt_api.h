@@ -43,7 +43,8 @@ extern "C" {
  * flags, and rt_radiance_accumulate, rt_radiance_atrous, their host twins rt_host_radiance_accumulate and
  * rt_host_radiance_atrous, rt_radiance_temporal_params and rt_radiance_atrous_params, and rt_dispatch_indirect,
  * rt_shade_resolve_gi, their host twins rt_host_indirect_rays and rt_host_shade_resolve_gi, rt_indirect_params and
- * rt_resolve_gi_inputs. */
+ * rt_resolve_gi_inputs, and rt_reflection_motion, rt_radiance_accumulate_reflection, the host twin
+ * rt_host_reflection_motion and rt_reflection_motion_params. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -695,9 +696,11 @@ rt_status rt_ao_atrous(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_atrous_
  * arithmetic rules (so the device and the rt_host_radiance_* twins agree to the bit). The guide planes are
  * rt_denoise_guide's.
  *   lum(c) = (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2].
- * Known limit: history is fetched by SURFACE motion, so a mirror reflection ghosts under camera parallax; reprojection
- * by the filtered .w (the mean reflection distance, which both passes carry like a colour channel) is what this
- * plane layout leaves room for. */
+ * History is fetched through whatever motion plane the caller passes. The G-buffer's is SURFACE motion, under which a
+ * mirror reflection ghosts when the camera moves; rt_reflection_motion (below) turns it into the motion of what is seen
+ * IN the reflector, from the .w both passes carry (the mean reflection distance), and is what a reflection plane's
+ * rt_radiance_accumulate should be given. What remains after it: reflected objects that move themselves, curved
+ * reflectors (no curvature correction) and rough lobes (one mean distance per pixel). */
 
 /* As rt_ao_temporal_params. The Python binding's defaults: 32, 0.02, 0.9. */
 typedef struct { uint32_t max_history; float depth_tol; float normal_cos; } rt_radiance_temporal_params;
@@ -751,6 +754,81 @@ typedef struct { uint32_t iterations; float depth_tol; float normal_cos; float s
 rt_status rt_radiance_atrous(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_radiance_atrous_params* params,
                              const float* rad_in, const float* moments, const float* guide, float* rad_out,
                              float* var_out, float* tmp, float* var_tmp, void* hip_stream);
+
+/* ---- Reflection motion: a reflection's history from where the reflection was -----------------------
+ * rt_reflection_motion writes a motion plane for what is seen IN a reflector: the reflected image of a mirror lies
+ * behind it, the reflection distance further along the camera ray, and that virtual point (not the reflector's
+ * surface) keeps its place in the world while the camera moves. The output has the motion plane's own layout (mx, my,
+ * w_prev, w_cur), so the unchanged rt_radiance_accumulate takes it in place of rt_gbuffer_motion.motion; w_prev is the
+ * previous view depth of the point of the REFLECTOR the previous eye saw the image through, so that pass's depth and
+ * normal tests check "same reflector, same place". The filters' preamble holds: whole row-major W x H planes, one
+ * kernel, asynchronous on hip_stream, a context only (no TLAS, no context camera: both cameras are arguments), no
+ * allocation, aliasing detected by pointer equality, nothing written on RT_E_INVALID, the same RT_E_UNSUPPORTED
+ * limits, the same arithmetic rules (the device and rt_host_reflection_motion agree to the bit).
+ *
+ * share: finite, in [0, 1]: the part of the reflection distance the virtual point lies behind the reflector (1: a
+ * mirror; less for a rough lobe, whose image sits nearer the surface). static_tol: finite, >= 0, in pixels: how far the
+ * surface motion may lie from the static point's before the reflector counts as moved. depth_tol, normal_cos: as
+ * rt_radiance_temporal_params', used by class 6 alone; pass the values the accumulation will use. The Python
+ * binding's defaults: 1, 2^-4 (16 x the largest |e_s - m| measured on static geometry, 0.00256 px on C2F at 1080p,
+ * rounded up to a power of two: DESIGN §3.19), 0.02, 0.9. */
+typedef struct { float share, static_tol, depth_tol, normal_cos; } rt_reflection_motion_params;
+
+/* hits: rt_gbuffer.hits (W*H x 4 words); guide_cur, motion, motion_out: W*H x 4 floats; all 16-byte aligned. dist: the
+ * reflection distance of pixel i at dist[i * dist_stride] (a reflection plane's .w: rad + 3 at stride 4), 4-byte
+ * aligned. guide_prev: the previous frame's guide or NULL. cb_cur, cb_prev: host pointers, rt_set_camera's 64 floats of
+ * this frame and of the previous one. class_out: W*H bytes or NULL (then nothing extra is stored).
+ * For pixel (x, y), i = y W + x, g = guide_cur[i], m = motion[i], h = hits[4i .. 4i+3], d = dist[i * dist_stride],
+ * the pixel PASSES THROUGH (motion_out[i] = m, bit for bit) in the first of these classes that applies:
+ *   1  g.w == 0 or h[3] == 0 (no surface, a primary miss).
+ *   2  d is not finite or d < 0.
+ *   3  The reflector moved. (O, D) = the camera ray of the pixel under cb_cur (rt_shade_resolve's), t = asfloat(h[0]),
+ *      P = O + D t, e_s = rt_host_motion_project's entry of (P, P) under (cb_cur, cb_prev). Applies unless
+ *      fabsf(e_s[0] - m.x) <= static_tol && fabsf(e_s[1] - m.y) <= static_tol (a non-finite m lands here).
+ *   4  tv = t + share * d, Pv = O + D tv, e_v = the entry of (Pv, Pv). Applies when e_v[2] <= 0 (behind the previous
+ *      camera). The test is this comparison alone: a NaN e_v (a finite but huge d can overflow the projection's sums
+ *      to inf - inf) is not caught by it. Such a pixel mostly ends in class 5 (s or wx is then not finite either) and,
+ *      with guide_prev, otherwise in class 6; without guide_prev it can be written as a class-0 entry whose (mx, my)
+ *      are not finite, which rt_radiance_accumulate's conditions on the entry reject (no history is fetched).
+ *   5  C' = mul(viewInverse', (0, 0, 0, 1)), the previous camera's origin (RayGen's expression on cb_prev[32..47]);
+ *      n = g.xyz, a = dot(P - C', n), b = dot(Pv - C', n), s = a / b. Applies unless s is finite and 0 < s <= 1: the
+ *      previous eye's line of sight to the image must cross the reflector's tangent plane between the eye and the
+ *      image. X = C' + (Pv - C') s; wx = the clip w of X under the previous camera. Applies also unless wx > 0.
+ *   6  Only when guide_prev is given: rt_ao_accumulate's reprojection (conditions, taps, weights, skips and the three
+ *      tests) of the entry (e_v[0], e_v[1], wx, .) with g, guide_prev, depth_tol and normal_cos. Applies unless the
+ *      accepted weights sum to sw >= 0.01f: the plane is never worse than surface motion at FINDING history.
+ * Otherwise motion_out[i] = (e_v[0], e_v[1], wx, m.w): class 0, "virtual". class_out[i] = the class, 0..6.
+ * By construction: with cb_cur == cb_prev (bitwise) a class-0 pixel has mx = my = 0 exactly, and w_prev equals w_cur
+ * to rounding only; share = 0 gives e_s's (mx, my) bit for bit; a reflection miss (d = tmax) is a distant point, no
+ * special case.
+ * Not corrected: a reflected object that moves itself, a curved reflector's magnification, a rough lobe's spread (d is
+ * its mean); and the history's own .w is not compared with d (a reflection that was hidden a frame ago takes the
+ * history of what hid it). The construction is a flat mirror's: measured under a camera orbit it cuts a
+ * flat reflector's error on reflected geometry to a tenth and RAISES a curved reflector's, whose history it finds in
+ * the wrong place; pass this plane for flat reflectors and keep the surface motion plane for curved ones.
+ * RT_E_INVALID: null or out-of-range params; dist_stride 0; a null plane (guide_prev and class_out may be NULL) or
+ * camera buffer; a misaligned plane; motion_out or class_out equal to an input or to each other; dist inside
+ * motion_out; W or H of 0. */
+rt_status rt_reflection_motion(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_reflection_motion_params* params,
+                               const uint32_t* hits, const float* guide_cur, const float* motion, const float* dist,
+                               uint32_t dist_stride, const float* guide_prev, const float cb_cur[64],
+                               const float cb_prev[64], float* motion_out, uint8_t* class_out, void* hip_stream);
+
+/* rt_reflection_motion and rt_radiance_accumulate in one launch for a reflection plane: the entry is computed in
+ * registers with dist = rad_cur's .w (stride 4) and guide_prev = this call's, and accumulated through; nothing is
+ * stored between the two (32 B per pixel less traffic, one launch less; DESIGN §3.19 has the measurement). The result
+ * is bit-equal to rt_reflection_motion(motion_params, ..., rad_cur + 3, 4, guide_prev, ...) followed by
+ * rt_radiance_accumulate(params, ...) on its plane; with rad_prev, moments_prev and guide_prev all NULL it is
+ * rt_radiance_accumulate itself, bit for bit (no entry is computed: the motion is never read). There is no class plane.
+ * RT_E_INVALID: rt_radiance_accumulate's cases and rt_reflection_motion's (motion_params, hits, the camera buffers; an
+ * output equal to hits). */
+rt_status rt_radiance_accumulate_reflection(rt_ctx_t ctx, uint32_t W, uint32_t H,
+                                            const rt_radiance_temporal_params* params,
+                                            const rt_reflection_motion_params* motion_params, const float* rad_cur,
+                                            const float* motion, const float* guide_cur, const uint32_t* hits,
+                                            const float cb_cur[64], const float cb_prev[64], const float* rad_prev,
+                                            const float* moments_prev, const float* guide_prev, float* rad_out,
+                                            float* moments_out, void* hip_stream);
 
 /* ---- Temporal upscaler of the colour frame --------------------------------------------------------
  * rt_upscale reconstructs a W x H display frame from a jittered w x h render (rt_dispatch_rays' rgba32f_dev under a
@@ -1342,6 +1420,13 @@ rt_status rt_host_radiance_accumulate(uint32_t W, uint32_t H, const rt_radiance_
 rt_status rt_host_radiance_atrous(uint32_t W, uint32_t H, const rt_radiance_atrous_params* params,
                                   const float* rad_in, const float* moments, const float* guide, float* rad_out,
                                   float* var_out, float* tmp, float* var_tmp);
+
+/* rt_reflection_motion on host arrays, likewise (hits too needs 4-byte alignment only). */
+rt_status rt_host_reflection_motion(uint32_t W, uint32_t H, const rt_reflection_motion_params* params,
+                                    const uint32_t* hits, const float* guide_cur, const float* motion,
+                                    const float* dist, uint32_t dist_stride, const float* guide_prev,
+                                    const float cb_cur[64], const float cb_prev[64], float* motion_out,
+                                    uint8_t* class_out);
 
 /* rt_upscale on host arrays, likewise: the same arguments less the context and the stream, the same checks less the
  * 16-byte alignment (4 bytes will do, rgba8_out included), the same per-pixel function, so the same bits. */

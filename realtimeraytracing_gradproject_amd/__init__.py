@@ -185,6 +185,19 @@ class rt_radiance_atrous_params(ctypes.Structure):
                 ("sigma_l", ctypes.c_float)]
 
 
+class rt_reflection_motion_params(ctypes.Structure):
+    """include/rt_api.h rt_reflection_motion_params: share (0..1), static_tol (pixels, >= 0), depth_tol, normal_cos of
+    rt_reflection_motion."""
+    _fields_ = [("share", ctypes.c_float), ("static_tol", ctypes.c_float), ("depth_tol", ctypes.c_float),
+                ("normal_cos", ctypes.c_float)]
+
+
+# rt_reflection_motion's static_tol default: 16 x the largest |e_s - m| measured on static geometry (0.00256 px on C2F
+# at 1080p, 0.00049 px on REFLO at 720p, under an eye move of (0.3, 0.15, -0.2); tools/reflection_motion_study.py,
+# DESIGN §3.19) = 0.041 px, rounded up to a power of two; the cap of 0.25 px is not reached.
+REFLECTION_MOTION_STATIC_TOL = 2.0 ** -4
+
+
 class rt_upscale_params(ctypes.Structure):
     """include/rt_api.h rt_upscale_params: the two frames' jitters (render pixels), max_history (1..1024), depth_tol."""
     _fields_ = [("jitter_cur", ctypes.c_float * 2), ("jitter_prev", ctypes.c_float * 2),
@@ -269,6 +282,11 @@ SIGNATURES = [
                                     _P, _P, _P, _P]),
     ("rt_radiance_atrous", _I, [_P, _U32, _U32, ctypes.POINTER(rt_radiance_atrous_params), _P, _P, _P, _P, _P, _P, _P,
                                 _P]),
+    ("rt_reflection_motion", _I, [_P, _U32, _U32, ctypes.POINTER(rt_reflection_motion_params), _P, _P, _P, _P, _U32,
+                                  _P, _P, _P, _P, _P, _P]),
+    ("rt_radiance_accumulate_reflection", _I, [_P, _U32, _U32, ctypes.POINTER(rt_radiance_temporal_params),
+                                               ctypes.POINTER(rt_reflection_motion_params), _P, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, _P, _P, _P]),
     ("rt_upscale", _I, [_P, _U32, _U32, _U32, _U32, ctypes.POINTER(rt_upscale_params), _P, _P, _P, _P, _P, _P, _P, _P,
                         _P]),
     ("rt_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _P]),
@@ -343,6 +361,8 @@ SIGNATURES = [
                                          _P, _P, _P]),
     ("rt_host_radiance_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_radiance_atrous_params), _P, _P, _P, _P, _P, _P,
                                      _P]),
+    ("rt_host_reflection_motion", _I, [_U32, _U32, ctypes.POINTER(rt_reflection_motion_params), _P, _P, _P, _P, _U32,
+                                       _P, _P, _P, _P, _P]),
     ("rt_host_upscale", _I, [_U32, _U32, _U32, _U32, ctypes.POINTER(rt_upscale_params), _P, _P, _P, _P, _P, _P, _P,
                              _P]),
     ("rt_camera_jitter", _I, [_FP, _U32, _U32, ctypes.c_float, ctypes.c_float, _FP]),
@@ -1022,6 +1042,39 @@ def host_radiance_atrous(width: int, height: int, rad_in, moments, guide, iterat
     if st != RT_OK:
         raise RtError(st, "rt_host_radiance_atrous")
     return out, var
+
+
+def host_reflection_motion(width: int, height: int, hits, guide_cur, motion, dist, camera, prev_camera,
+                           guide_prev=None, share: float = 1.0, static_tol: float = REFLECTION_MOTION_STATIC_TOL,
+                           depth_tol: float = 0.02, normal_cos: float = 0.9):
+    """rt_host_reflection_motion: the reflection motion plane on the host (no GPU). hits: (width * height, 4) 32-bit
+    words (dispatch_gbuffer's hits); guide_cur, motion: (width * height, 4) floats; dist: width * height floats, or any
+    strided view of a float32 array (rad[:, 3]: a reflection plane's distance); camera / prev_camera: the two frames'
+    64-float camera buffers; guide_prev: the previous frame's guide or None (class 6 is then not evaluated). Returns
+    (motion_out (width * height, 4) float32, classes width * height uint8: 0 virtual, 1..6 the pass-through classes of
+    include/rt_api.h). static_tol's default, 2^-4 px, is 16 x the largest distance measured between the static point's
+    entry and the motion plane's on static geometry (0.00256 px, C2F at 1080p), rounded up to a power of two (DESIGN
+    §3.19)."""
+    n = width * height
+    hw = np.ascontiguousarray(hits)
+    if hw.dtype.itemsize != 4 or hw.size != 4 * n:
+        raise ValueError(f"expected {4 * n} 32-bit hit words, got {hw.size} of {hw.dtype.itemsize} bytes")
+    gc, mo = _f32(guide_cur, 4 * n), _f32(motion, 4 * n)
+    d = np.asarray(dist)
+    if d.dtype != np.float32 or d.ndim != 1 or (n and (d.strides[0] <= 0 or d.strides[0] % 4)):
+        d = np.ascontiguousarray(dist, dtype=np.float32).ravel()
+    if d.size != n:
+        raise ValueError(f"expected {n} distances, got {d.size}")
+    gp = None if guide_prev is None else _f32(guide_prev, 4 * n)
+    cb = None if camera is None else _f32(camera, 64)
+    pcb = None if prev_camera is None else _f32(prev_camera, 64)
+    p = rt_reflection_motion_params(share, static_tol, depth_tol, normal_cos)
+    out, cls = np.zeros((n, 4), np.float32), np.zeros(n, np.uint8)
+    st = lib.rt_host_reflection_motion(width, height, ctypes.byref(p), _vp(hw), _vp(gc), _vp(mo), _vp(d),
+                                       d.strides[0] // 4 if n else 1, _vp(gp), _vp(cb), _vp(pcb), _vp(out), _vp(cls))
+    if st != RT_OK:
+        raise RtError(st, "rt_host_reflection_motion")
+    return out, cls
 
 
 def _upscale_params(jitter_cur, jitter_prev, max_history, depth_tol) -> rt_upscale_params:
@@ -1945,6 +1998,56 @@ class Context:
             self._plane(m, "moments", moments, 4 * n), self._plane(m, "guide", guide, 4 * n),
             self._plane(m, "rad_out", rad_out, 4 * n), self._plane(m, "var_out", var_out, n),
             self._plane(m, "tmp", tmp, 4 * n), self._plane(m, "var_tmp", var_tmp, n), stream), "rt_radiance_atrous")
+
+    def reflection_motion(self, width: int, height: int, hits, guide_cur, motion, dist, camera, prev_camera,
+                          motion_out, guide_prev=None, class_out=None, dist_stride: int = 4, share: float = 1.0,
+                          static_tol: float = REFLECTION_MOTION_STATIC_TOL, depth_tol: float = 0.02,
+                          normal_cos: float = 0.9, stream: Optional[int] = None):
+        """rt_reflection_motion: the motion plane of what is seen IN a reflector (the virtual reflected point's), to
+        pass to radiance_accumulate in place of the G-buffer's surface motion when the plane is a reflection. hits:
+        dispatch_gbuffer's hits plane; guide_cur, motion, motion_out: width * height x 4 floats; dist: a raw address, or
+        a tensor whose element 0 is the first distance (rad.view(-1)[3:] for a reflection plane's .w), read every
+        dist_stride floats; camera / prev_camera: the two frames' 64-float camera buffers (host arrays); guide_prev: the
+        previous frame's guide or None; class_out: width * height bytes (uint8) or None. A pixel whose reflector moved,
+        whose virtual point cannot be seen from the previous camera or at which no history would be found keeps its
+        surface motion bit for bit. static_tol's default, 2^-4 px, is 16 x the largest distance measured between
+        the static point's entry and the motion plane's on static geometry (0.00256 px, C2F at 1080p), rounded up to a
+        power of two."""
+        n, m = width * height, "reflection_motion"
+        d = dist if dist is None or isinstance(dist, int) else dist.data_ptr()
+        if class_out is not None and not isinstance(class_out, int):
+            if class_out.element_size() != 1 or class_out.numel() != n or not class_out.is_contiguous():
+                raise ValueError(f"{m}: class_out must be a contiguous tensor of {n} bytes")
+        cb = None if camera is None else _f32(camera, 64)
+        pcb = None if prev_camera is None else _f32(prev_camera, 64)
+        p = rt_reflection_motion_params(share, static_tol, depth_tol, normal_cos)
+        self._check(self._lib.rt_reflection_motion(
+            self._h, width, height, ctypes.byref(p), self._plane(m, "hits", hits, 4 * n),
+            self._plane(m, "guide_cur", guide_cur, 4 * n), self._plane(m, "motion", motion, 4 * n), d, dist_stride,
+            self._plane(m, "guide_prev", guide_prev, 4 * n), _vp(cb), _vp(pcb), self._plane(m, "motion_out", motion_out, 4 * n), _ptr(class_out),
+            stream), "rt_reflection_motion")
+
+    def radiance_accumulate_reflection(self, width: int, height: int, rad_cur, motion, guide_cur, hits, camera,
+                                       prev_camera, rad_out, moments_out, rad_prev=None, moments_prev=None,
+                                       guide_prev=None, max_history: int = 32, depth_tol: float = 0.02,
+                                       normal_cos: float = 0.9, share: float = 1.0,
+                                       static_tol: float = REFLECTION_MOTION_STATIC_TOL,
+                                       stream: Optional[int] = None):
+        """rt_radiance_accumulate_reflection: reflection_motion (with dist = rad_cur's .w and this call's guide_prev,
+        depth_tol and normal_cos) and radiance_accumulate in one launch, bit-equal to the two; the motion entry stays
+        in registers. Without the previous planes it is radiance_accumulate itself."""
+        n, m = 4 * width * height, "radiance_accumulate_reflection"
+        cb = None if camera is None else _f32(camera, 64)
+        pcb = None if prev_camera is None else _f32(prev_camera, 64)
+        p = rt_radiance_temporal_params(max_history, depth_tol, normal_cos)
+        q = rt_reflection_motion_params(share, static_tol, depth_tol, normal_cos)
+        self._check(self._lib.rt_radiance_accumulate_reflection(
+            self._h, width, height, ctypes.byref(p), ctypes.byref(q), self._plane(m, "rad_cur", rad_cur, n),
+            self._plane(m, "motion", motion, n), self._plane(m, "guide_cur", guide_cur, n),
+            self._plane(m, "hits", hits, n), _vp(cb), _vp(pcb), self._plane(m, "rad_prev", rad_prev, n),
+            self._plane(m, "moments_prev", moments_prev, n), self._plane(m, "guide_prev", guide_prev, n),
+            self._plane(m, "rad_out", rad_out, n), self._plane(m, "moments_out", moments_out, n), stream),
+            "rt_radiance_accumulate_reflection")
 
     def upscale(self, render_width: int, render_height: int, width: int, height: int, color_cur, motion_cur, color_out,
                 hist_out, motion_prev=None, color_prev=None, hist_prev=None, rgba8_out=None, jitter_cur=(0.0, 0.0),

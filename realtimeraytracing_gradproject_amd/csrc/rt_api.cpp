@@ -2553,6 +2553,116 @@ rt_status rt_radiance_atrous(rt_ctx_t c, uint32_t W, uint32_t H, const rt_radian
   return RT_OK;
 }
 
+// ---- Reflection motion: the argument check shared by rt_reflection_motion and its host twin (align as
+// above), and the launch's parameters ---------------------------------------------------------------------------
+namespace {
+
+const char* reflection_motion_args_error(uint32_t W, uint32_t H, const rt_reflection_motion_params* p,
+                                         const uint32_t* hits, const float* guide_cur, const float* motion,
+                                         const float* dist, uint32_t dist_stride, const float* guide_prev,
+                                         const float* cb_cur, const float* cb_prev, const float* motion_out,
+                                         const uint8_t* class_out, bool align, rt_status* st) {
+  if (const char* why = denoise_frame_error(W, H, st)) return why;
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (!std::isfinite(p->share) || !(p->share >= 0.0f && p->share <= 1.0f)) return "share not finite or outside [0, 1]";
+  if (!std::isfinite(p->static_tol) || !(p->static_tol >= 0.0f)) return "static_tol not finite and >= 0";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!(p->normal_cos >= -1.0f && p->normal_cos < 1.0f)) return "normal_cos outside [-1, 1)";
+  if (dist_stride < 1) return "dist_stride is 0";
+  if (!hits) return "null hits plane";
+  if (!guide_cur) return "null guide_cur";
+  if (!motion) return "null motion plane";
+  if (!dist) return "null dist plane";
+  if (!cb_cur) return "null cb_cur";
+  if (!cb_prev) return "null cb_prev";
+  if (!motion_out) return "null motion_out";
+  const size_t a4 = align ? 16 : 4;
+  if (misaligned(hits, a4)) return "hits plane misaligned";
+  if (misaligned(guide_cur, a4)) return "guide_cur misaligned";
+  if (misaligned(motion, a4)) return "motion plane misaligned";
+  if (misaligned(guide_prev, a4)) return "guide_prev misaligned";
+  if (misaligned(motion_out, a4)) return "motion_out misaligned";
+  if (misaligned(dist, 4)) return "dist plane misaligned";
+  for (const void* in : {(const void*)hits, (const void*)guide_cur, (const void*)motion, (const void*)guide_prev,
+                         (const void*)dist}) {
+    if (in == (const void*)motion_out) return "motion_out is an input plane";
+    if (class_out && in == (const void*)class_out) return "class_out is an input plane";
+  }
+  if ((const void*)class_out == (const void*)motion_out) return "class_out is motion_out";
+  const float* me = motion_out + 4 * ((size_t)W * H);
+  if (dist >= motion_out && dist < me) return "dist lies inside motion_out";
+  return nullptr;
+}
+
+rt::ReflMotion reflection_motion_of(uint32_t W, uint32_t H, const rt_reflection_motion_params* p, const uint32_t* hits,
+                                    const float* guide_cur, const float* motion, const float* dist,
+                                    uint32_t dist_stride, const float* guide_prev, const float* cb_cur,
+                                    const float* cb_prev, float* motion_out, uint8_t* class_out) {
+  rt::ReflMotion r = {};
+  r.W = W, r.H = H;
+  r.fwidth = (float)W, r.fheight = (float)H;
+  r.share = p->share, r.static_tol = p->static_tol, r.depth_tol = p->depth_tol, r.normal_cos = p->normal_cos;
+  rt::frame_cam(cb_cur, r.cam);
+  motion_cams(cb_cur, cb_prev, r.cams);
+  rt::FrameCam prev;
+  rt::frame_cam(cb_prev, prev);
+  std::memcpy(r.prev_origin, prev.origin, sizeof(r.prev_origin));
+  r.hits = hits, r.guide_cur = guide_cur, r.motion = motion, r.dist = dist, r.dist_stride = dist_stride;
+  r.guide_prev = guide_prev;
+  r.motion_out = motion_out, r.class_out = class_out;
+  return r;
+}
+
+}  // namespace
+
+rt_status rt_reflection_motion(rt_ctx_t c, uint32_t W, uint32_t H, const rt_reflection_motion_params* params,
+                               const uint32_t* hits, const float* guide_cur, const float* motion, const float* dist,
+                               uint32_t dist_stride, const float* guide_prev, const float cb_cur[64],
+                               const float cb_prev[64], float* motion_out, uint8_t* class_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  if (const char* why = reflection_motion_args_error(W, H, params, hits, guide_cur, motion, dist, dist_stride,
+                                                     guide_prev, cb_cur, cb_prev, motion_out, class_out, true, &st))
+    return fail(c, st, std::string("rt_reflection_motion: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_reflection_motion(
+      reflection_motion_of(W, H, params, hits, guide_cur, motion, dist, dist_stride, guide_prev, cb_cur, cb_prev,
+                           motion_out, class_out),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "reflection motion launch");
+  return RT_OK;
+}
+
+rt_status rt_radiance_accumulate_reflection(rt_ctx_t c, uint32_t W, uint32_t H,
+                                            const rt_radiance_temporal_params* params,
+                                            const rt_reflection_motion_params* motion_params, const float* rad_cur,
+                                            const float* motion, const float* guide_cur, const uint32_t* hits,
+                                            const float cb_cur[64], const float cb_prev[64], const float* rad_prev,
+                                            const float* moments_prev, const float* guide_prev, float* rad_out,
+                                            float* moments_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  const char* why = radiance_accumulate_args_error(W, H, params, rad_cur, motion, guide_cur, rad_prev, moments_prev,
+                                                   guide_prev, rad_out, moments_out, true, &st);
+  // the entry's own arguments: its distance plane is rad_cur's .w, its output the registers (rad_out stands in for
+  // the aliasing rules: no output may be the hits plane either)
+  if (!why)
+    why = reflection_motion_args_error(W, H, motion_params, hits, guide_cur, motion, rad_cur + 3, 4, guide_prev,
+                                       cb_cur, cb_prev, rad_out, nullptr, true, &st);
+  if (!why && (const void*)hits == (const void*)moments_out) why = "moments_out is the hits plane", st = RT_E_INVALID;
+  if (why) return fail(c, st, std::string("rt_radiance_accumulate_reflection: ") + why);
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_radiance_accumulate_reflection(
+      radiance_temporal_of(W, H, params, rad_cur, motion, guide_cur, rad_prev, moments_prev, guide_prev, rad_out,
+                           moments_out),
+      reflection_motion_of(W, H, motion_params, hits, guide_cur, motion, rad_cur + 3, 4, guide_prev, cb_cur, cb_prev,
+                           nullptr, nullptr),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "fused reflection accumulate launch");
+  return RT_OK;
+}
+
 // ---- Temporal upscaler: the argument check shared by rt_upscale and rt_host_upscale (align as above) --
 namespace {
 
@@ -3427,6 +3537,24 @@ rt_status rt_host_radiance_atrous(uint32_t W, uint32_t H, const rt_radiance_atro
         a.var_out[i] = vo;
       }
   }
+  return RT_OK;
+}
+
+// Host service: rt_reflection_motion on host arrays through reflection_motion_pixel, the function k_reflection_motion
+// calls, after the device entry point's argument checks (less the 16-byte alignment).
+rt_status rt_host_reflection_motion(uint32_t W, uint32_t H, const rt_reflection_motion_params* params,
+                                    const uint32_t* hits, const float* guide_cur, const float* motion,
+                                    const float* dist, uint32_t dist_stride, const float* guide_prev,
+                                    const float cb_cur[64], const float cb_prev[64], float* motion_out,
+                                    uint8_t* class_out) {
+  rt_status st = RT_OK;
+  if (reflection_motion_args_error(W, H, params, hits, guide_cur, motion, dist, dist_stride, guide_prev, cb_cur,
+                                   cb_prev, motion_out, class_out, false, &st))
+    return st;
+  const rt::ReflMotion r = reflection_motion_of(W, H, params, hits, guide_cur, motion, dist, dist_stride, guide_prev,
+                                                cb_cur, cb_prev, motion_out, class_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::reflection_motion_pixel(r, x, y);
   return RT_OK;
 }
 

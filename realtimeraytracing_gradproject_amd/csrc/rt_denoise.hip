@@ -34,10 +34,13 @@
 //                       staged form takes the same 36 x 12 lattice tile in three arrays (guide float4, colour float4,
 //                       variance float: 15,552 B); every row read is 32 consecutive entries as in k_ao_atrous_lds, and
 //                       the halo of 2 covers the 3 x 3 variance prefilter, which sits on the same lattice.
+//   k_reflection_motion the reflection motion plane (rt_reflection_motion), one pixel per lane over 32 x 8
+//                       tiles: the surface motion replaced by the virtual reflected point's where the reflector is
+//                       static and history would be found there; the previous guide's four taps only on those lanes.
 //
 // The arithmetic of all of them is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
 // resolve_pixel, reflection_composite_pixel, resolve_pbr_pixel, resolve_gi_pixel, radiance_accumulate_pixel,
-// radiance_atrous_pixel),
+// radiance_atrous_pixel, reflection_motion_pixel),
 // which the host twins in rt_api.cpp call too: the
 // kernels differ from them in where a value is read, never in how it is used.
 // Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
@@ -193,6 +196,28 @@ __global__ __launch_bounds__(256) void k_radiance_accumulate(RadTemporal a, uint
   const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
   if (x >= a.W || y >= a.H) return;
   radiance_accumulate_pixel(a, x, y);
+}
+
+// One pixel per lane over the filters' tiles. Both cameras (FrameCam, MotionCams, the previous origin: 416 B) ride in
+// the kernel argument and are read wave-uniformly; a lane's plane traffic is three 16-byte loads, the distance and one
+// 16-byte store, plus the class's byte when asked for; the guide_prev taps (one 16-byte load each) are issued only by
+// the lanes that reach the history test.
+static_assert(sizeof(ReflMotion) <= 4096, "rt_reflection_motion's launch must fit the 4 KB kernel-argument segment");
+__global__ __launch_bounds__(256) void k_reflection_motion(ReflMotion r, uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= r.W || y >= r.H) return;
+  reflection_motion_pixel(r, x, y);
+}
+
+// k_reflection_motion and k_radiance_accumulate in one launch: the entry stays in registers (32 B per pixel less than
+// the two launches write and read back).
+static_assert(sizeof(RadTemporal) + sizeof(ReflMotion) <= 4096, "the fused launch must fit the kernel-argument segment");
+__global__ __launch_bounds__(256) void k_radiance_accumulate_reflection(RadTemporal a, ReflMotion r, uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= a.W || y >= a.H) return;
+  radiance_accumulate_reflection_pixel(a, r, x, y);
 }
 
 struct RadGlobalTap {  // a tap read from the planes, bounds-checked; var is read every var_stride floats
@@ -383,6 +408,18 @@ hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol,
 hipError_t launch_radiance_accumulate(const RadTemporal& a, hipStream_t stream) {
   const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
   hipLaunchKernelGGL(k_radiance_accumulate, dim3(tx * ty), dim3(256), 0, stream, a, tx);
+  return hipGetLastError();
+}
+
+hipError_t launch_reflection_motion(const ReflMotion& r, hipStream_t stream) {
+  const uint32_t tx = tiles(r.W, kTileW), ty = tiles(r.H, kTileH);
+  hipLaunchKernelGGL(k_reflection_motion, dim3(tx * ty), dim3(256), 0, stream, r, tx);
+  return hipGetLastError();
+}
+
+hipError_t launch_radiance_accumulate_reflection(const RadTemporal& a, const ReflMotion& r, hipStream_t stream) {
+  const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
+  hipLaunchKernelGGL(k_radiance_accumulate_reflection, dim3(tx * ty), dim3(256), 0, stream, a, r, tx);
   return hipGetLastError();
 }
 

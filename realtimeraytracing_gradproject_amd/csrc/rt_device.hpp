@@ -1093,6 +1093,37 @@ struct AoTemporal {  // rt_ao_accumulate's launch: rt_ao_temporal_params and the
   float *ao_out, *hist_out;
 };
 
+// The temporal passes' reprojection of pixel (x, y) with guide g (g[3] != 0) through the motion entry m = (mx, my,
+// w_prev, .): the conditions on m and on the reprojected position, the four bilinear taps in their order with their
+// weights, the skips (a zero weight, outside the frame) and the three tests of a tap's previous guide entry (a surface,
+// the expected previous depth m[2] within depth_tol, this pixel's normal within normal_cos). accept(w, t) is called for
+// every accepted tap with its weight and its plane index, in tap order. ao_accumulate_pixel, radiance_accumulate_pixel
+// and reflection_motion_entry's history test all run this one loop.
+template <typename Accept>
+RT_HD void reproject_taps(uint32_t W, uint32_t H, uint32_t x, uint32_t y, const float g[4], const float m[4],
+                          float depth_tol, float normal_cos, const float* guide_prev, Accept accept) {
+  const float big = 3.402823466e+38f;
+  if (!(fabsf(m[0]) <= big && fabsf(m[1]) <= big && m[2] > 0.0f)) return;
+  const float fx = (float)x + m[0], fy = (float)y + m[1];
+  if (!(fx > -1.0f && fx < (float)W && fy > -1.0f && fy < (float)H)) return;  // before any conversion to integer
+  const float xf = floorf(fx), yf = floorf(fy);
+  const float tx = fx - xf, ty = fy - yf;
+  const int x0 = (int)xf, y0 = (int)yf;
+  const V3 gn = v3(g[0], g[1], g[2]);
+  const float lim = depth_tol * m[2];
+  for (int k = 0; k < 4; ++k) {
+    const int dx = k & 1, dy = k >> 1;
+    const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
+    const int xx = x0 + dx, yy = y0 + dy;
+    if (w == 0.0f || xx < 0 || yy < 0 || xx >= (int)W || yy >= (int)H) continue;
+    const size_t t = (size_t)yy * W + (size_t)xx;
+    float q[4];
+    ld4(guide_prev + 4 * t, q);
+    if (q[3] == 0.0f || fabsf(q[3] - m[2]) > lim || dot(gn, v3(q[0], q[1], q[2])) < normal_cos) continue;
+    accept(w, t);
+  }
+}
+
 // Pixel (x, y) of rt_ao_accumulate: the previous frame's AO and history length fetched bilinearly at the reprojected
 // position from the taps whose previous guide agrees with the expected previous depth (motion's w_prev) and with this
 // pixel's normal, then blended 1 / n into it. Reads its own ao_cur entry before it writes (ao_out may be ao_cur).
@@ -1107,31 +1138,13 @@ RT_HD void ao_accumulate_pixel(const AoTemporal& a, uint32_t x, uint32_t y) {
     return;
   }
   ld4(a.motion + 4 * i, m);
-  const float big = 3.402823466e+38f;
   float sw = 0.0f, sa = 0.0f, sh = 0.0f;
-  if (a.ao_prev && fabsf(m[0]) <= big && fabsf(m[1]) <= big && m[2] > 0.0f) {
-    const float fx = (float)x + m[0], fy = (float)y + m[1];
-    if (fx > -1.0f && fx < (float)a.W && fy > -1.0f && fy < (float)a.H) {  // before any conversion to integer
-      const float xf = floorf(fx), yf = floorf(fy);
-      const float tx = fx - xf, ty = fy - yf;
-      const int x0 = (int)xf, y0 = (int)yf;
-      const V3 gn = v3(g[0], g[1], g[2]);
-      const float lim = a.depth_tol * m[2];
-      for (int k = 0; k < 4; ++k) {
-        const int dx = k & 1, dy = k >> 1;
-        const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
-        const int xx = x0 + dx, yy = y0 + dy;
-        if (w == 0.0f || xx < 0 || yy < 0 || xx >= (int)a.W || yy >= (int)a.H) continue;
-        const size_t t = (size_t)yy * a.W + (size_t)xx;
-        float q[4];
-        ld4(a.guide_prev + 4 * t, q);
-        if (q[3] == 0.0f || fabsf(q[3] - m[2]) > lim || dot(gn, v3(q[0], q[1], q[2])) < a.normal_cos) continue;
-        sw += w;
-        sa += w * a.ao_prev[t];
-        sh += w * a.hist_prev[t];
-      }
-    }
-  }
+  if (a.ao_prev)
+    reproject_taps(a.W, a.H, x, y, g, m, a.depth_tol, a.normal_cos, a.guide_prev, [&](float w, size_t t) {
+      sw += w;
+      sa += w * a.ao_prev[t];
+      sh += w * a.hist_prev[t];
+    });
   if (sw >= 0.01f) {
     const float av = sa / sw;
     const float n = minf(sh / sw + 1.0f, a.max_history);
@@ -1201,52 +1214,29 @@ struct RadTemporal {  // rt_radiance_accumulate's launch (prev planes all null o
   float *rad_out, *moments_out;
 };
 
-// Pixel (x, y) of rt_radiance_accumulate: ao_accumulate_pixel's reprojection (the same conditions, taps, weights and
-// rejection tests) over the radiance entry and the moments (m1, m2, hist), then the variance: temporal from a history
-// of 4 or more, else from the 5 x 5 neighbourhood of rad_cur under the guide's depth and normal weights.
-RT_HD void radiance_accumulate_pixel(const RadTemporal& a, uint32_t x, uint32_t y) {
+// The arithmetic of a surface pixel (x, y) of rt_radiance_accumulate from its loaded entries (c = rad_cur[i], g =
+// guide_cur[i] with g[3] != 0) and a motion entry m that need not come from a.motion (the fused reflection form passes
+// the virtual point's, computed in registers): ao_accumulate_pixel's reprojection (the same conditions, taps, weights
+// and rejection tests) over the radiance entry and the moments (m1, m2, hist), then the variance: temporal from a
+// history of 4 or more, else from the 5 x 5 neighbourhood of rad_cur under the guide's depth and normal weights.
+RT_HD void radiance_accumulate_surface(const RadTemporal& a, uint32_t x, uint32_t y, const float c[4],
+                                       const float g[4], const float m[4]) {
   const size_t i = (size_t)y * a.W + x;
-  float c[4], g[4], m[4];
-  ld4(a.rad_cur + 4 * i, c);
-  ld4(a.guide_cur + 4 * i, g);
-  if (g[3] == 0.0f) {
-    const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    st4(a.rad_out + 4 * i, c);
-    st4(a.moments_out + 4 * i, zero);
-    return;
-  }
-  ld4(a.motion + 4 * i, m);
-  const float big = 3.402823466e+38f;
   const float l = radiance_lum(c);
   const V3 gn = v3(g[0], g[1], g[2]);
   float sw = 0.0f, s1 = 0.0f, s2 = 0.0f, sh = 0.0f;
   float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (a.rad_prev && fabsf(m[0]) <= big && fabsf(m[1]) <= big && m[2] > 0.0f) {
-    const float fx = (float)x + m[0], fy = (float)y + m[1];
-    if (fx > -1.0f && fx < (float)a.W && fy > -1.0f && fy < (float)a.H) {  // before any conversion to integer
-      const float xf = floorf(fx), yf = floorf(fy);
-      const float tx = fx - xf, ty = fy - yf;
-      const int x0 = (int)xf, y0 = (int)yf;
-      const float lim = a.depth_tol * m[2];
-      for (int k = 0; k < 4; ++k) {
-        const int dx = k & 1, dy = k >> 1;
-        const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
-        const int xx = x0 + dx, yy = y0 + dy;
-        if (w == 0.0f || xx < 0 || yy < 0 || xx >= (int)a.W || yy >= (int)a.H) continue;
-        const size_t t = (size_t)yy * a.W + (size_t)xx;
-        float q[4], rp[4], mp[4];
-        ld4(a.guide_prev + 4 * t, q);
-        if (q[3] == 0.0f || fabsf(q[3] - m[2]) > lim || dot(gn, v3(q[0], q[1], q[2])) < a.normal_cos) continue;
-        ld4(a.rad_prev + 4 * t, rp);
-        ld4(a.moments_prev + 4 * t, mp);
-        sw += w;
-        for (int k4 = 0; k4 < 4; ++k4) sc[k4] += w * rp[k4];
-        s1 += w * mp[0];
-        s2 += w * mp[1];
-        sh += w * mp[2];
-      }
-    }
-  }
+  if (a.rad_prev)
+    reproject_taps(a.W, a.H, x, y, g, m, a.depth_tol, a.normal_cos, a.guide_prev, [&](float w, size_t t) {
+      float rp[4], mp[4];
+      ld4(a.rad_prev + 4 * t, rp);
+      ld4(a.moments_prev + 4 * t, mp);
+      sw += w;
+      for (int k4 = 0; k4 < 4; ++k4) sc[k4] += w * rp[k4];
+      s1 += w * mp[0];
+      s2 += w * mp[1];
+      sh += w * mp[2];
+    });
   float out[4], mo[4];
   if (sw >= 0.01f) {
     const float n = minf(sh / sw + 1.0f, a.max_history);
@@ -1294,6 +1284,23 @@ RT_HD void radiance_accumulate_pixel(const RadTemporal& a, uint32_t x, uint32_t 
   }
   st4(a.rad_out + 4 * i, out);
   st4(a.moments_out + 4 * i, mo);
+}
+
+// Pixel (x, y) of rt_radiance_accumulate: its entries loaded, "no surface" passed through, the rest
+// radiance_accumulate_surface's.
+RT_HD void radiance_accumulate_pixel(const RadTemporal& a, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * a.W + x;
+  float c[4], g[4], m[4];
+  ld4(a.rad_cur + 4 * i, c);
+  ld4(a.guide_cur + 4 * i, g);
+  if (g[3] == 0.0f) {
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    st4(a.rad_out + 4 * i, c);
+    st4(a.moments_out + 4 * i, zero);
+    return;
+  }
+  ld4(a.motion + 4 * i, m);
+  radiance_accumulate_surface(a, x, y, c, g, m);
 }
 
 // One iteration's colour and variance for a pixel with guide g (g[3] != 0) and input colour c0. s: the step;
@@ -1353,6 +1360,126 @@ RT_HD void radiance_atrous_pixel(const float g[4], const float c0[4], uint32_t s
   }
   for (int k = 0; k < 4; ++k) out[k] = sc[k] / sw;
   var_out = sv / (sw * sw);
+}
+
+// ------------------------------------------------------------------------------------------
+// Reflection motion (rt_reflection_motion): a motion plane for what is SEEN IN a reflector, by
+// virtual-point reprojection: the reflected image of a mirror lies behind it, `d` further along the camera ray, and
+// that point, not the reflector's surface, is what keeps its place in the world between two frames. The entry has the
+// motion plane's layout (mx, my, w_prev, w_cur), so rt_radiance_accumulate consumes it unchanged; w_prev is the previous
+// view depth of the point of the REFLECTOR the previous eye saw the image through, so that pass's depth and normal
+// tests check "same reflector, same place". The AO section's arithmetic rule holds; tests/reflection_motion_reference.py
+// restates it in numpy.
+//   * Both camera buffers equal and a static scene: a virtual pixel has mx = my = 0 exactly (both projections of Pv are
+//     one expression); w_prev agrees with w_cur only to rounding (it comes from X, not from P).
+//   * share = 0 makes Pv = P, bit for bit: (mx, my) are the static surface reprojection. share = 1 is the mirror image.
+//   * A reflection miss carries d = tmax and needs no special case: a distant point.
+//   * Whole row-major planes only, for the filters' reason.
+//   * A flat mirror's construction: no curvature correction (a curved reflector's history is found, in the wrong place:
+//     DESIGN §3.19 measures it), and the history's own distance is not compared with d.
+// ------------------------------------------------------------------------------------------
+enum : uint32_t {
+  kReflMotionVirtual = 0,     // the entry is the virtual point's
+  kReflMotionNoSurface = 1,   // g.w == 0 or a primary miss
+  kReflMotionNoDistance = 2,  // d not finite or < 0
+  kReflMotionMoved = 3,       // the surface motion is not the static point's: a moved or deformed reflector
+  kReflMotionBehind = 4,      // the virtual point is behind the previous camera
+  kReflMotionNoCrossing = 5,  // the previous eye's line to the image does not cross the reflector's tangent plane
+  kReflMotionNoHistory = 6    // the accumulators would find no history there
+};
+
+struct ReflMotion {  // rt_reflection_motion's launch: rt_reflection_motion_params, both cameras and the planes
+  uint32_t W, H;
+  float fwidth, fheight;
+  float share, static_tol, depth_tol, normal_cos;
+  FrameCam cam;          // the current camera's ray constants (frame_cam of cb_cur)
+  MotionCams cams;       // both cameras' forward chains
+  float prev_origin[4];  // frame_cam's origin of cb_prev
+  const uint32_t* hits;
+  const float *guide_cur, *motion, *dist;
+  uint32_t dist_stride;
+  const float* guide_prev;  // null: class 6 is not evaluated
+  float* motion_out;
+  uint8_t* class_out;  // null: not stored
+};
+
+// The entry and the class of pixel (x, y) from its guide entry g, surface motion m, primary hit record h (bits) and
+// reflection distance d. The classes are tested in their order; every class but 0 passes m through, bit for bit.
+RT_HD uint32_t reflection_motion_entry(const ReflMotion& r, uint32_t x, uint32_t y, const float g[4], const float m[4],
+                                       const float h[4], float d, float out[4]) {
+  const float big = 3.402823466e+38f;
+  out[0] = m[0], out[1] = m[1], out[2] = m[2], out[3] = m[3];
+  if (g[3] == 0.0f || __builtin_bit_cast(uint32_t, h[3]) == 0u) return kReflMotionNoSurface;
+  if (!(fabsf(d) <= big) || d < 0.0f) return kReflMotionNoDistance;
+  V3 O, D;
+  pixel_ray(r.cam, r.fwidth, r.fheight, x, y, O, D);
+  const float t = h[0];
+  const V3 P = add(O, muls(D, t));
+  float es[4], ev[4];
+  motion_entry(r.cams, P, P, r.fwidth, r.fheight, es);
+  if (!(fabsf(es[0] - m[0]) <= r.static_tol && fabsf(es[1] - m[1]) <= r.static_tol)) return kReflMotionMoved;
+  const float tv = t + r.share * d;
+  const V3 Pv = add(O, muls(D, tv));
+  motion_entry(r.cams, Pv, Pv, r.fwidth, r.fheight, ev);
+  if (ev[2] <= 0.0f) return kReflMotionBehind;
+  const V3 Cp = v3(r.prev_origin[0], r.prev_origin[1], r.prev_origin[2]);
+  const V3 n = v3(g[0], g[1], g[2]);
+  const V3 toPv = sub(Pv, Cp);
+  const float a = dot(sub(P, Cp), n), b = dot(toPv, n);
+  const float s = a / b;
+  if (!(fabsf(s) <= big && s > 0.0f && s <= 1.0f)) return kReflMotionNoCrossing;
+  const V3 X = add(Cp, muls(toPv, s));
+  float sx, sy, wx;
+  motion_screen(r.cams.prev_view, r.cams.prev_proj, X, r.fwidth, r.fheight, sx, sy, wx);
+  if (!(wx > 0.0f)) return kReflMotionNoCrossing;
+  const float cand[4] = {ev[0], ev[1], wx, m[3]};
+  if (r.guide_prev) {
+    float sw = 0.0f;
+    reproject_taps(r.W, r.H, x, y, g, cand, r.depth_tol, r.normal_cos, r.guide_prev,
+                   [&](float w, size_t) { sw += w; });
+    if (!(sw >= 0.01f)) return kReflMotionNoHistory;
+  }
+  out[0] = cand[0], out[1] = cand[1], out[2] = cand[2], out[3] = cand[3];
+  return kReflMotionVirtual;
+}
+
+// Pixel (x, y) of rt_reflection_motion: three 16-byte loads and the distance in, one 16-byte store (and the class's
+// byte) out.
+RT_HD void reflection_motion_pixel(const ReflMotion& r, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * r.W + x;
+  float g[4], m[4], h[4], out[4];
+  ld4(r.guide_cur + 4 * i, g);
+  ld4(r.motion + 4 * i, m);
+  ld4(reinterpret_cast<const float*>(r.hits) + 4 * i, h);  // bits only: (t, instance id, primitive, hit flag)
+  const float d = r.dist[i * r.dist_stride];
+  const uint32_t cls = reflection_motion_entry(r, x, y, g, m, h, d, out);
+  st4(r.motion_out + 4 * i, out);
+  if (r.class_out) r.class_out[i] = (uint8_t)cls;
+}
+
+// Pixel (x, y) of rt_radiance_accumulate_reflection: reflection_motion_entry with d = rad_cur[i].w, kept in registers,
+// then radiance_accumulate_surface on it: the two passes' bits without the plane between them (r.guide_prev is
+// a.guide_prev; r.dist, r.motion_out and r.class_out are not used). Without previous planes the motion entry is never
+// read, so none is computed: rt_radiance_accumulate itself.
+RT_HD void radiance_accumulate_reflection_pixel(const RadTemporal& a, const ReflMotion& r, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * a.W + x;
+  float c[4], g[4], m[4], h[4], e[4];
+  ld4(a.rad_cur + 4 * i, c);
+  ld4(a.guide_cur + 4 * i, g);
+  if (g[3] == 0.0f) {
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    st4(a.rad_out + 4 * i, c);
+    st4(a.moments_out + 4 * i, zero);
+    return;
+  }
+  ld4(a.motion + 4 * i, m);
+  if (!a.rad_prev) {
+    radiance_accumulate_surface(a, x, y, c, g, m);
+    return;
+  }
+  ld4(reinterpret_cast<const float*>(r.hits) + 4 * i, h);
+  reflection_motion_entry(r, x, y, g, m, h, c[3], e);
+  radiance_accumulate_surface(a, x, y, c, g, e);
 }
 
 // The resolve of the soft-shadow section above (rt_shade_resolve); here for ld4 / st4.

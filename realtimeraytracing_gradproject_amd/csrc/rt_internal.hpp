@@ -241,6 +241,10 @@ hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol,
 // --- Radiance filter (rt_denoise.hip) -----------------------------------------
 // The AO filter's pair for planes of 4-float entries; per-pixel arithmetic in rt_device.hpp, shared with the host twins.
 hipError_t launch_radiance_accumulate(const RadTemporal& a, hipStream_t stream);
+// The reflection motion plane: one launch over the filters' tiles, reflection_motion_pixel per lane.
+hipError_t launch_reflection_motion(const ReflMotion& r, hipStream_t stream);
+// Both in one launch: the entry is computed in registers and accumulated through (r's output planes are not used).
+hipError_t launch_radiance_accumulate_reflection(const RadTemporal& a, const ReflMotion& r, hipStream_t stream);
 // One a-trous iteration of step s: colour `in` and variance `var` (read every var_stride floats) to out / var_out.
 struct RadAtrous {
   uint32_t W, H, s;
