@@ -184,8 +184,11 @@ $(ASAN)/obj_ingest_fuzz: tools/obj_ingest_fuzz.cpp $(ASAN)/rt_host.o | $(ASAN)
 #   asan-reflmotion      the reflection motion plane's host twin (rt_host_reflection_motion: the history taps at
 #                        virtual points in and far out of the frame, the stride-4 distance read and the class bytes, on
 #                        exact-size heap blocks)
+#   asan-reflection-chain  the chained reflection pass's host twins (rt_host_reflection_chain_rays,
+#                        rt_host_reflection_chain_radiance: level-major indexing at 1 and 18 levels, chains of every
+#                        length, the "levels too few" refusal, on exact-size heap blocks)
 ASAN_CHECKS := asan-ao asan-denoise asan-upscale asan-shadow asan-reflection asan-materials asan-reflection-pbr \
-               asan-radiance asan-indirect asan-reflmotion
+               asan-radiance asan-indirect asan-reflmotion asan-reflection-chain
 asan-ao: $(ASAN)/ao_rays_check
 asan-denoise: $(ASAN)/denoise_check
 asan-upscale: $(ASAN)/upscale_check
@@ -196,6 +199,7 @@ asan-reflection-pbr: $(ASAN)/reflection_pbr_check
 asan-radiance: $(ASAN)/radiance_check
 asan-indirect: $(ASAN)/indirect_check
 asan-reflmotion: $(ASAN)/reflmotion_check
+asan-reflection-chain: $(ASAN)/reflection_chain_check
 
 $(ASAN)/rt_api.o: $(SRC)/rt_api.cpp $(HDRS) | $(ASAN)
 	$(HIPCC) $(HIPFLAGS) -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -c $< -o $@

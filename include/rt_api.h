@@ -44,7 +44,9 @@ extern "C" {
  * rt_host_radiance_atrous, rt_radiance_temporal_params and rt_radiance_atrous_params, and rt_dispatch_indirect,
  * rt_shade_resolve_gi, their host twins rt_host_indirect_rays and rt_host_shade_resolve_gi, rt_indirect_params and
  * rt_resolve_gi_inputs, and rt_reflection_motion, rt_radiance_accumulate_reflection, the host twin
- * rt_host_reflection_motion and rt_reflection_motion_params. */
+ * rt_host_reflection_motion and rt_reflection_motion_params, and rt_dispatch_reflection_chain, its host twins
+ * rt_host_reflection_chain_rays and rt_host_reflection_chain_radiance with rt_host_last_error,
+ * rt_reflection_chain_params and RT_MAX_REFLECTION_BOUNCES. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -1042,6 +1044,57 @@ rt_status rt_dispatch_reflection_pbr(rt_ctx_t ctx, uint32_t W, uint32_t H, const
                                      const rt_reflection_pbr_params* params, const rt_material_table* table,
                                      const rt_reflection_planes* out, void* hip_stream);
 
+/* The longest mirror chain rt_dispatch_reflection_chain follows, in reflection rays: the frame kernels' own limit (an
+ * RT_SHADE_REF frame traces at most this many reflection rays per camera ray). */
+#define RT_MAX_REFLECTION_BOUNCES 18
+
+/* Parameters of the chained PBR reflection pass: rt_reflection_pbr_params' six values, with their ranges, and
+ * max_bounces in 1..RT_MAX_REFLECTION_BOUNCES: the most reflection rays one sample's chain may hold. */
+typedef struct { uint32_t samples; uint32_t seed; float roughness; float tmax; float shadow_tmin; uint32_t flags;
+                 uint32_t max_bounces; } rt_reflection_chain_params;
+
+/* The chained PBR reflection pass: rt_dispatch_reflection_pbr whose reflected model hits reflect in
+ * turn, as the nested TraceRay of the reference's ClosestHit does (Hit.hlsl:194-203), up to max_bounces rays per
+ * sample. Everything rt_dispatch_reflection_pbr documents about W, H, rows, nrows and the compact row order, the
+ * schedule rule and the per-lane fall-back, rt_set_triangle_test, streams, slot rings, the TLAS double buffer,
+ * rt_forget_stream and refit-before-rebuild, the table and its index rule, the two flags, `out` and the zero entries
+ * on a primary miss or an invalid normal holds unchanged.
+ * Colour of sample k. Ray 1 is rt_dispatch_reflection_pbr's ray k to the bit (the flags' mirror rule, the roughness
+ * lobe, the origin). For b = 1, 2, ... ray b = (o_b, d_b) is searched closest-hit over [0.001, tmax] with back faces
+ * culled:
+ *   a miss: C_b = the miss colour at the pixel's row;
+ *   a plane-group hit: C_b = PlaneClosestHit, with its one shadow ray to light 0, as in rt_dispatch_reflection_pbr;
+ *   any other hit, at P_b = o_b + d_b * t_b with stored-form normal N_b and material m_b (the table's index rule):
+ *     s_b = ClosestHit's surface colour exactly as rt_dispatch_reflection_pbr evaluates it (cam = o_b; per light the
+ *     factor of RT_REFLECT_SHADOW_MODELS). The hit CONTINUES iff table[m_b].reflectivity != 0.0f (the frame's test)
+ *     and b < max_bounces. If it continues, ray b + 1 is the frame kernels' reflection ray:
+ *     d_{b+1} = normalize(normalize(reflect(normalize(d_b), N_b))) on N_b as stored, o_{b+1} = P_b + d_{b+1} * 0.001f
+ *     (no roughness on a continuation ray, whatever the flags), and C_b = s_b + r_b * (C_{b+1} - s_b) per channel with
+ *     r_b that material's reflectivity: HLSL's lerp, evaluated innermost first in float32 without contraction (also at
+ *     r_b == 1). If it does not continue, C_b = s_b.
+ *   The sample's colour is C_1.
+ * The reduction, radiance.w (the mean distance of the FIRST rays, what rt_reflection_motion and the radiance filter
+ * read) and hits (ray 0's first record) are rt_dispatch_reflection_pbr's.
+ * Two anchors follow:
+ *   (a) with max_bounces == 1 both planes are rt_dispatch_reflection_pbr's, byte for byte;
+ *   (b) with max_bounces == RT_MAX_REFLECTION_BOUNCES, samples 1, roughness 0, tmax 1000, shadow_tmin 0.01 and
+ *       RT_REFLECT_FRAME_RAY, feeding rt_shade_resolve_pbr as rt_dispatch_reflection_pbr's anchor does (entry 0 the
+ *       frame's material for instance ids 0 and 1, entry 1 the same with reflectivity 0 for all others) reproduces
+ *       rt_dispatch_rays' reflective RT_SHADE_REF frame bit for bit at EVERY pixel.
+ * Cost (one MI355X, C2F at 1080p and REFLO at 720p, both schedules, rt_dispatch_reflection_pbr in the
+ * same rounds): the per-lane chain stack lives in scratch memory (288 bytes per lane); at max_bounces 1, where no chain
+ * exists, a launch measured 0.995 - 1.017 x that pass, inside both spreads, so a one-bounce caller has no reason to move
+ * either way; max_bounces 2 measured 1.24 - 1.29 x, 18 measured 1.43 - 1.96 x. Nothing switches by itself.
+ * rt_set_stats: RT_STAT_REFLECTION_RAYS grows by every reflection ray traced, first and continuation;
+ * RT_STAT_SHADOW_RAYS by the plane hits at any level and, with RT_REFLECT_SHADOW_MODELS, by the lit (model hit, light)
+ * pairs at any level; primary rays, pixels and dispatches as in rt_dispatch_reflection_pbr.
+ * Errors (RT_E_INVALID, nothing written, rt_last_error naming the cause): every case of rt_dispatch_reflection_pbr,
+ * and max_bounces outside 1..RT_MAX_REFLECTION_BOUNCES.
+ * Reference: ClosestHit's nested TraceRay (Hit.hlsl:194-203). */
+rt_status rt_dispatch_reflection_chain(rt_ctx_t ctx, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                       const rt_reflection_chain_params* params, const rt_material_table* table,
+                                       const rt_reflection_planes* out, void* hip_stream);
+
 /* Parameters of the diffuse indirect pass: samples 1..64; seed; tmax finite and > 0.001; shadow_tmin finite and >= 0;
  * flags: RT_REFLECT_SHADOW_MODELS or 0 (there is no mirror direction here, so RT_REFLECT_FRAME_RAY is refused). */
 typedef struct { uint32_t samples; uint32_t seed; float tmax; float shadow_tmin; uint32_t flags; } rt_indirect_params;
@@ -1504,6 +1557,42 @@ rt_status rt_host_reflection_radiance_pbr(const float* rays, const uint32_t* hit
                                           const rt_light* lights, uint32_t nlights,
                                           const rt_reflection_pbr_params* params, const rt_material_table* table,
                                           float* radiance_out, uint8_t* lit_out);
+
+/* The continuation rays of rt_dispatch_reflection_chain for m traced rays, flat, on the host: rays m x 8 floats
+ * (origin, tmin, direction, tmax), hits m x 4 words (rt_trace_rays' records of their closest-hit search), hit_normal
+ * m x 4 floats (stored-form normals of those hits), hit_group and hit_inst m words; table as in
+ * rt_host_reflection_radiance_pbr (instance_material a HOST array). continues_out (m bytes, or NULL) is 1 where the
+ * record is a hit of a group other than RT_HITGROUP_PLANE whose material's reflectivity != 0.0f; rays_out (m x 8
+ * floats) holds there (o, 0.001f, d, tmax) with d = normalize(normalize(reflect(normalize(ray direction), N))) and
+ * o = (ray origin + ray direction * t) + d * 0.001f: the bits of rt_host_reflection_rays_flags fed the ray as the
+ * camera ray (samples 1, roughness 0, RT_REFLECT_FRAME_RAY), and of the frame kernels' reflection ray. Entries that
+ * do not continue are zero-filled. The bounce cap is the caller's loop. It calls the functions the chain kernels
+ * call. Null arrays with m > 0, tmax not finite and > 0.001 or a bad table: RT_E_INVALID, nothing written. */
+rt_status rt_host_reflection_chain_rays(const float* rays, const uint32_t* hits, const float* hit_normal,
+                                        const uint32_t* hit_group, const uint32_t* hit_inst, uint32_t m, float tmax,
+                                        const rt_material_table* table, float* rays_out, uint8_t* continues_out);
+
+/* The radiance plane rt_dispatch_reflection_chain writes for n pixels, on the host, from what the traced rays of every
+ * level found: rt_host_reflection_radiance_pbr's arguments with a leading level dimension. rays, hits, hit_normal,
+ * hit_group, hit_inst and occluded are level-major: level b's block (n x S entries of that function's layout) follows
+ * level b - 1's, `levels` (1..RT_MAX_REFLECTION_BOUNCES) blocks in all; level 1 holds the pass's first rays, level
+ * b + 1 rt_host_reflection_chain_rays' rays of level b. An entry of level b is read only where the chain of its
+ * (pixel, sample) reaches level b. valid and py are n entries as before. lit_out (levels x n x S x nlights bytes, or
+ * NULL) is 1 exactly at the shadow rays the pass traces; nrays_out (n x S bytes, or NULL) holds the rays of each
+ * chain (0 for an invalid pixel). Errors: rt_host_reflection_radiance_pbr's, levels or params->max_bounces out of
+ * range, and a chain that wants to continue past the supplied `levels` while below max_bounces (a caller cannot
+ * truncate a chain by accident): RT_E_INVALID, nothing written, rt_host_last_error naming the pixel. */
+rt_status rt_host_reflection_chain_radiance(uint32_t levels, const float* rays, const uint32_t* hits,
+                                            const float* hit_normal, const uint32_t* hit_group,
+                                            const uint32_t* hit_inst, const uint8_t* occluded, const uint8_t* valid,
+                                            const uint32_t* py, uint32_t n, uint32_t H, const rt_light* lights,
+                                            uint32_t nlights, const rt_reflection_chain_params* params,
+                                            const rt_material_table* table, float* radiance_out, uint8_t* lit_out,
+                                            uint8_t* nrays_out);
+
+/* What the calling thread's last refused rt_host_reflection_chain_* call objected to ("" before the first): the host
+ * twins take no context, so rt_last_error cannot carry it. The string lives until the thread's next such call. */
+const char* rt_host_last_error(void);
 
 /* The rays rt_dispatch_indirect traces for n pixels, on the host: rt_host_reflection_rays' arguments, results and
  * conventions (rays_out n x samples x 8 floats, (P + d * 0.001f, 0.001f, d, tmax); valid_out n bytes or NULL; an

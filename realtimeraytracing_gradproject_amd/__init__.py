@@ -138,6 +138,17 @@ class rt_reflection_pbr_params(ctypes.Structure):
                 ("tmax", ctypes.c_float), ("shadow_tmin", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
+RT_MAX_REFLECTION_BOUNCES = 18
+
+
+class rt_reflection_chain_params(ctypes.Structure):
+    """include/rt_api.h rt_reflection_chain_params: rt_reflection_pbr_params' fields and max_bounces
+    (1..RT_MAX_REFLECTION_BOUNCES) of rt_dispatch_reflection_chain."""
+    _fields_ = [("samples", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("roughness", ctypes.c_float),
+                ("tmax", ctypes.c_float), ("shadow_tmin", ctypes.c_float), ("flags", ctypes.c_uint32),
+                ("max_bounces", ctypes.c_uint32)]
+
+
 class rt_indirect_params(ctypes.Structure):
     """include/rt_api.h rt_indirect_params: samples (1..64), seed, tmax, shadow_tmin and the flags
     (RT_REFLECT_SHADOW_MODELS only) of rt_dispatch_indirect."""
@@ -268,6 +279,9 @@ SIGNATURES = [
                                     ctypes.POINTER(rt_reflection_planes), _P]),
     ("rt_dispatch_reflection_pbr", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_reflection_pbr_params),
                                         ctypes.POINTER(rt_material_table), ctypes.POINTER(rt_reflection_planes), _P]),
+    ("rt_dispatch_reflection_chain", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_reflection_chain_params),
+                                          ctypes.POINTER(rt_material_table), ctypes.POINTER(rt_reflection_planes),
+                                          _P]),
     ("rt_dispatch_indirect", _I, [_P, _U32, _U32, _P, _U32, ctypes.POINTER(rt_indirect_params),
                                   ctypes.POINTER(rt_material_table), ctypes.POINTER(rt_reflection_planes), _P]),
     ("rt_shade_resolve_gi", _I, [_P, _U32, _U32, ctypes.POINTER(rt_resolve_gi_inputs),
@@ -348,6 +362,13 @@ SIGNATURES = [
     ("rt_host_reflection_radiance_pbr", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _U32, _U32, ctypes.POINTER(rt_light), _U32,
                                              ctypes.POINTER(rt_reflection_pbr_params),
                                              ctypes.POINTER(rt_material_table), _P, _P]),
+    ("rt_host_reflection_chain_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.c_float,
+                                           ctypes.POINTER(rt_material_table), _P, _P]),
+    ("rt_host_reflection_chain_radiance", _I, [_U32, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _U32,
+                                               ctypes.POINTER(rt_light), _U32,
+                                               ctypes.POINTER(rt_reflection_chain_params),
+                                               ctypes.POINTER(rt_material_table), _P, _P, _P]),
+    ("rt_host_last_error", ctypes.c_char_p, []),
     ("rt_host_reflection_composite", _I, [_U32, _U32, _FP, ctypes.POINTER(rt_reflection_composite_params), _P, _P, _P,
                                           _P, _P, _P]),
     ("rt_host_indirect_rays", _I, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(rt_indirect_params), _P, _P]),
@@ -874,6 +895,92 @@ def host_reflection_radiance_pbr(rays, hits, hit_normal, hit_group, hit_inst, oc
     if st != RT_OK:
         raise RtError(st, "rt_host_reflection_radiance_pbr")
     return (out, lit) if want_lit else out
+
+
+def _host_table(materials, instance_material):
+    """The rt_material_table of a host twin from set_shading-format materials and a host map (or None); the returned
+    arrays must outlive the call."""
+    mats, nm = _materials_array(materials)
+    im = None if instance_material is None else np.ascontiguousarray(instance_material, dtype=np.uint32).ravel()
+    return rt_material_table(mats, nm, _vp(im), 0 if im is None else im.size), (mats, im)
+
+
+def host_reflection_chain_rays(rays, hits, hit_normal, hit_group, hit_inst, materials, instance_material=None,
+                               tmax: float = 1000.0):
+    """rt_host_reflection_chain_rays: the continuation rays of rt_dispatch_reflection_chain, on the host (no GPU).
+    rays: (..., 8) traced rays; hits: (..., 4) uint32 records of their closest-hit search; hit_normal: (..., 4)
+    stored-form normals of those hits; hit_group, hit_inst: (...) hit groups and instance indices; materials,
+    instance_material: as for host_reflection_radiance_pbr. Returns rays (same shape; the frame kernels' reflection
+    ray where the hit is a model hit whose material reflects, zeros elsewhere) and the uint8 mask of those hits. The
+    bounce cap is the caller's loop."""
+    ry = np.ascontiguousarray(rays, dtype=np.float32)
+    if ry.ndim < 1 or ry.shape[-1] != 8:
+        raise ValueError(f"rays must be (..., 8), got {ry.shape}")
+    m = ry.size // 8
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    hn = _f32(hit_normal, 4 * m)
+    hg = np.ascontiguousarray(hit_group, dtype=np.uint32).ravel()
+    hi = np.ascontiguousarray(hit_inst, dtype=np.uint32).ravel()
+    if hh.size != 4 * m or hg.size != m or hi.size != m:
+        raise ValueError(f"expected {m} records, hit groups and instances, got {hh.size // 4}, {hg.size} and {hi.size}")
+    table, _keep = _host_table(materials, instance_material)
+    out = np.zeros(ry.shape, np.float32)
+    cont = np.zeros(ry.shape[:-1], np.uint8)
+    st = lib.rt_host_reflection_chain_rays(_vp(ry), _vp(hh), _vp(hn), _vp(hg), _vp(hi), m, tmax, ctypes.byref(table),
+                                           _vp(out), _vp(cont))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_host_last_error().decode() or "rt_host_reflection_chain_rays")
+    return out, cont
+
+
+def host_reflection_chain_radiance(rays, hits, hit_normal, hit_group, hit_inst, occluded, valid, py, height: int,
+                                   lights, materials, instance_material=None, max_bounces: int = 4,
+                                   roughness: float = 0.0, tmax: float = 1000.0, shadow_tmin: float = 0.01,
+                                   seed: int = 0, flags: int = 0, want_lit: bool = False, want_nrays: bool = False):
+    """rt_host_reflection_chain_radiance: rt_dispatch_reflection_chain's radiance plane from what the rays of every
+    level found, on the host (no GPU): host_reflection_radiance_pbr's arguments with a leading level axis. rays:
+    (levels, n, S, 8), level 0 the pass's first rays, level b + 1 host_reflection_chain_rays' rays of level b; hits,
+    hit_normal: (levels, n, S, 4); hit_group, hit_inst: (levels, n, S); occluded: (levels, n, S, nlights); valid, py:
+    (n,). An entry of a level is read only where its chain reaches that level. Returns (n, 4) float32 and, as asked,
+    the (levels, n, S, nlights) uint8 mask of the shadow rays traced and the (n, S) uint8 rays of each chain. A chain
+    that wants to go on past the supplied levels while below max_bounces raises RtError naming the pixel."""
+    ry = np.ascontiguousarray(rays, dtype=np.float32)
+    if ry.ndim != 4 or ry.shape[3] != 8:
+        raise ValueError(f"rays must be (levels, n, samples, 8), got {ry.shape}")
+    lv, n, S = ry.shape[0], ry.shape[1], ry.shape[2]
+    arr = _lights_array(lights)
+    nl = len(arr)
+    name = "rt_host_reflection_chain_radiance"
+    if not 1 <= S <= 64:
+        raise RtError(RT_E_INVALID, f"{name}: samples {S} outside 1..64")
+    if not 1 <= nl <= 16:
+        raise RtError(RT_E_INVALID, f"{name}: {nl} lights, outside 1..16")
+    if not 1 <= lv <= RT_MAX_REFLECTION_BOUNCES:
+        raise RtError(RT_E_INVALID, f"{name}: {lv} levels, outside 1..{RT_MAX_REFLECTION_BOUNCES}")
+    e = lv * n * S
+    hh = np.ascontiguousarray(hits).view(np.uint32).reshape(-1)
+    hn = _f32(hit_normal, 4 * e)
+    hg = np.ascontiguousarray(hit_group, dtype=np.uint32).ravel()
+    hi = np.ascontiguousarray(hit_inst, dtype=np.uint32).ravel()
+    oc = np.ascontiguousarray(occluded, dtype=np.uint8).ravel()
+    va = np.ascontiguousarray(valid, dtype=np.uint8).ravel()
+    y = np.ascontiguousarray(py, dtype=np.uint32).ravel()
+    if hh.size != 4 * e or hg.size != e or hi.size != e or oc.size != e * nl or va.size != n or y.size != n:
+        raise ValueError(f"expected {lv} x {n} x {S} records, hit groups and instances, {e * nl} occlusion bytes and "
+                         f"{n} valid bytes and rows, got {hh.size // 4}, {hg.size}, {hi.size}, {oc.size}, {va.size} "
+                         f"and {y.size}")
+    table, _keep = _host_table(materials, instance_material)
+    p = rt_reflection_chain_params(S, seed, roughness, tmax, shadow_tmin, flags, max_bounces)
+    out = np.zeros((n, 4), np.float32)
+    lit = np.zeros((lv, n, S, nl), np.uint8) if want_lit else None
+    nrays = np.zeros((n, S), np.uint8) if want_nrays else None
+    st = lib.rt_host_reflection_chain_radiance(lv, _vp(ry), _vp(hh), _vp(hn), _vp(hg), _vp(hi), _vp(oc), _vp(va),
+                                               _vp(y), n, height, arr, nl, ctypes.byref(p), ctypes.byref(table),
+                                               _vp(out), _vp(lit), _vp(nrays))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_host_last_error().decode() or name)
+    res = (out,) + ((lit,) if want_lit else ()) + ((nrays,) if want_nrays else ())
+    return res if len(res) > 1 else out
 
 
 def host_indirect_rays(cam_rays, t, normal, px, py, samples: int = 1, tmax: float = 1000.0, shadow_tmin: float = 0.01,
@@ -1861,6 +1968,28 @@ class Context:
                 raise ValueError(f"{m}: instance_material must be a contiguous tensor of 32-bit elements")
             ninst = instance_material.numel()
         return rt_material_table(mats, nm, _ptr(instance_material), ninst), mats
+
+    def dispatch_reflection_chain(self, width: int, height: int, radiance, materials, instance_material=None,
+                                  samples: int = 1, roughness: float = 0.0, tmax: float = 1000.0,
+                                  shadow_tmin: float = 0.01, seed: int = 0, flags: int = 0, max_bounces: int = 4,
+                                  hits=None, rows: Optional[np.ndarray] = None, stream: Optional[int] = None):
+        """rt_dispatch_reflection_chain: dispatch_reflection_pbr whose reflected model hits reflect in turn, up to
+        max_bounces (1..RT_MAX_REFLECTION_BOUNCES) rays per sample: a hit whose material's reflectivity is not 0 sends
+        the frame kernels' mirror ray and its colour is lerped towards what that ray returns, innermost first. Every
+        other argument is dispatch_reflection_pbr's. With max_bounces 1 the planes are that pass's bytes; with 18 and
+        RT_REFLECT_FRAME_RAY, shade_resolve_pbr(refl=...) equals dispatch()'s reflective RT_SHADE_REF frame at every
+        pixel. radiance's .w and hits describe the first rays. At max_bounces 1 a launch measures level with
+        dispatch_reflection_pbr; each further bounce costs its rays. host_reflection_chain_rays and
+        host_reflection_chain_radiance give the rays and the plane."""
+        m = "dispatch_reflection_chain"
+        rp, nr, _keep = self._rows_arg(rows, height)
+        g = rt_reflection_planes()
+        self._set_planes(g, m, nr * width, (("radiance", radiance, 4), ("hits", hits, 4)))
+        table, _mats = self._material_table(m, materials, instance_material)
+        p = rt_reflection_chain_params(samples, seed, roughness, tmax, shadow_tmin, flags, max_bounces)
+        self._check(self._lib.rt_dispatch_reflection_chain(self._h, width, height, rp, nr, ctypes.byref(p),
+                                                           ctypes.byref(table), ctypes.byref(g), stream),
+                    "rt_dispatch_reflection_chain")
 
     def dispatch_indirect(self, width: int, height: int, radiance, materials, instance_material=None,
                           samples: int = 1, tmax: float = 1000.0, shadow_tmin: float = 0.01, seed: int = 0,

@@ -2994,6 +2994,47 @@ rt_status rt_dispatch_reflection_pbr(rt_ctx_t c, uint32_t W, uint32_t H, const u
   return grid_pass_launch(c, fn, W, H, rows, nrows, stream, pp, pp.rp.gb, "PBR reflection launch");
 }
 
+// ---- Chained PBR reflection pass: rt_dispatch_reflection_pbr's checks and launch sequence around the
+// chain kernels. The parameter check is shared with rt_host_reflection_chain_radiance; it leaves the PBR pass's
+// parameters in *pbr ----------------------------------------------------------------------------------------------
+static_assert(RT_MAX_REFLECTION_BOUNCES == rt::kMaxReflectDepth && RT_MAX_REFLECTION_BOUNCES == rt::kMaxReflectionBounces,
+              "the chain pass follows as many reflection rays as the frame kernels");
+namespace {
+
+const char* reflection_chain_params_error(const rt_reflection_chain_params* p, rt_reflection_pbr_params* pbr) {
+  if (!p) return "null params";
+  *pbr = {p->samples, p->seed, p->roughness, p->tmax, p->shadow_tmin, p->flags};
+  rt_reflection_params base;
+  if (const char* why = reflection_pbr_params_error(pbr, &base)) return why;
+  if (p->max_bounces < 1 || p->max_bounces > (uint32_t)RT_MAX_REFLECTION_BOUNCES) return "max_bounces outside 1..18";
+  return nullptr;
+}
+
+}  // namespace
+
+rt_status rt_dispatch_reflection_chain(rt_ctx_t c, uint32_t W, uint32_t H, const uint32_t* rows, uint32_t nrows,
+                                       const rt_reflection_chain_params* params, const rt_material_table* table,
+                                       const rt_reflection_planes* out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  const std::string fn = "rt_dispatch_reflection_chain";
+  rt_reflection_pbr_params pbr;
+  if (const char* why = reflection_chain_params_error(params, &pbr)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (const char* why = material_table_error(table)) return fail(c, RT_E_INVALID, fn + ": " + why);
+  if (!out) return fail(c, RT_E_INVALID, fn + ": null output planes");
+  if (!out->radiance) return fail(c, RT_E_INVALID, fn + ": null radiance plane");
+  if ((uintptr_t)out->radiance % 16u) return fail(c, RT_E_INVALID, fn + ": radiance plane not aligned to 16 bytes");
+  if ((uintptr_t)out->hits % 16u) return fail(c, RT_E_INVALID, fn + ": hits plane not aligned to 16 bytes");
+  const rt_status st = grid_pass_check(c, fn, W, H, rows, &nrows);
+  if (st != RT_OK) return st;
+  if (!c->have_shading) return fail(c, RT_E_INVALID, fn + ": shading not set");
+  rt::ReflectionChainParams cp = {};
+  reflection_pbr_of(&pbr, table, c->fp.lights, c->fp.nlights, cp.pp);
+  cp.pp.rp.radiance = out->radiance;
+  cp.pp.rp.hits = out->hits;
+  cp.max_bounces = params->max_bounces;
+  return grid_pass_launch(c, fn, W, H, rows, nrows, stream, cp, cp.pp.rp.gb, "reflection chain launch");
+}
+
 // ---- Diffuse indirect pass: rt_dispatch_reflection_pbr's checks and launch sequence around the
 // indirect kernels. The parameter check is shared with rt_host_indirect_rays; it leaves the PBR reflection pass's
 // parameters (roughness 0) in *pbr, which are the radiance twin's -----------------------------------------------
@@ -3812,6 +3853,166 @@ rt_status rt_host_reflection_radiance_pbr(const float* rays, const uint32_t* hit
         rt::surface_split_light(st, pp.table[mi], Lr, P2, n2, rt::reflection_model_factor(occ));
       }
       rt::reflection_sum_add(sum, rt::surface_split_end(st), t2);
+    }
+    rt::reflection_reduce(sum, S, out);
+  }
+  return RT_OK;
+}
+
+// ---- The chain pass's host twins. They take no context, so what a refused call objected to is kept
+// per thread for rt_host_last_error ------------------------------------------------------------------------------
+namespace {
+
+thread_local std::string g_host_error;
+
+rt_status host_fail(const std::string& msg) {
+  g_host_error = msg;
+  return RT_E_INVALID;
+}
+
+// Does record j (a hit of hit_group[j], instance hit_inst[j]) send a continuation ray under this table? The chain
+// kernels' test less the bounce cap: a hit, not of the plane group, whose material reflects.
+bool chain_record_reflects(const rt::ReflectionPbrParams& pp, const uint32_t* hits, const uint32_t* hit_group,
+                           const uint32_t* hit_inst, size_t j) {
+  if (hits[4 * j + 3] == 0u || hit_group[j] == 2u) return false;
+  const uint32_t mi = rt::material_index(pp.instance_material, pp.ninstances, pp.nmaterials, hit_inst[j]);
+  return rt::reflection_chain_continues(pp.table[mi], 0u, 1u);
+}
+
+}  // namespace
+
+const char* rt_host_last_error(void) { return g_host_error.c_str(); }
+
+// Host service: rt_dispatch_reflection_chain's continuation rays for m traced rays, through the functions the chain
+// kernels call (material_index, reflection_chain_continues, reflection_chain_ray). No context, no GPU call.
+rt_status rt_host_reflection_chain_rays(const float* rays, const uint32_t* hits, const float* hit_normal,
+                                        const uint32_t* hit_group, const uint32_t* hit_inst, uint32_t m, float tmax,
+                                        const rt_material_table* table, float* rays_out, uint8_t* continues_out) {
+  const std::string fn = "rt_host_reflection_chain_rays: ";
+  if (!std::isfinite(tmax) || !(tmax > 0.001f)) return host_fail(fn + "tmax not finite and > 0.001");
+  if (const char* why = material_table_error(table)) return host_fail(fn + why);
+  if (m && (!rays || !hits || !hit_normal || !hit_group || !hit_inst || !rays_out)) return host_fail(fn + "null array");
+  rt::ReflectionPbrParams pp = {};
+  const rt_reflection_pbr_params none = {1, 0, 0.0f, tmax, 0.0f, 0};
+  const rt::LightRec no_light = {};
+  reflection_pbr_of(&none, table, &no_light, 0, pp);  // the table alone: this function shades nothing
+  for (uint32_t j = 0; j < m; ++j) {
+    float* out = rays_out + 8 * (size_t)j;
+    const bool cont = chain_record_reflects(pp, hits, hit_group, hit_inst, j);
+    if (continues_out) continues_out[j] = cont ? 1 : 0;
+    if (!cont) {
+      std::memset(out, 0, sizeof(float) * 8);
+      continue;
+    }
+    const float* r = rays + 8 * (size_t)j;
+    float t;
+    std::memcpy(&t, hits + 4 * (size_t)j, sizeof(t));
+    const rt::V3 ro = rt::v3(r[0], r[1], r[2]), d = rt::v3(r[4], r[5], r[6]);
+    const rt::V3 n = rt::v3(hit_normal[4 * (size_t)j], hit_normal[4 * (size_t)j + 1], hit_normal[4 * (size_t)j + 2]);
+    const rt::V3 P = rt::add(ro, rt::muls(d, t));
+    rt::V3 o2, d2;
+    rt::reflection_chain_ray(P, n, d, o2, d2);
+    out[0] = o2.x, out[1] = o2.y, out[2] = o2.z, out[3] = 0.001f;
+    out[4] = d2.x, out[5] = d2.y, out[6] = d2.z, out[7] = tmax;
+  }
+  return RT_OK;
+}
+
+// Host service: rt_dispatch_reflection_chain's radiance plane for n pixels from the records, normals, hit groups,
+// instances and occlusion of the traced rays of every level, through the functions the chain kernels call (the PBR
+// twin's per-ray colour, then reflection_chain_continues and reflection_chain_unwind), in the kernels' order of
+// operations. A first pass over the records finds every chain's length, so a refused call writes nothing. No context,
+// no GPU call.
+rt_status rt_host_reflection_chain_radiance(uint32_t levels, const float* rays, const uint32_t* hits,
+                                            const float* hit_normal, const uint32_t* hit_group,
+                                            const uint32_t* hit_inst, const uint8_t* occluded, const uint8_t* valid,
+                                            const uint32_t* py, uint32_t n, uint32_t H, const rt_light* lights,
+                                            uint32_t nlights, const rt_reflection_chain_params* params,
+                                            const rt_material_table* table, float* radiance_out, uint8_t* lit_out,
+                                            uint8_t* nrays_out) {
+  const std::string fn = "rt_host_reflection_chain_radiance: ";
+  rt_reflection_pbr_params pbr;
+  if (const char* why = reflection_chain_params_error(params, &pbr)) return host_fail(fn + why);
+  if (const char* why = material_table_error(table)) return host_fail(fn + why);
+  if (levels < 1 || levels > (uint32_t)RT_MAX_REFLECTION_BOUNCES) return host_fail(fn + "levels outside 1..18");
+  if (!lights || nlights < 1 || nlights > (uint32_t)rt::kMaxLights) return host_fail(fn + "lights null or not 1..16");
+  if (H == 0) return host_fail(fn + "H is 0");
+  if (n && (!rays || !hits || !hit_normal || !hit_group || !hit_inst || !occluded || !valid || !py || !radiance_out))
+    return host_fail(fn + "null array");
+  rt::ReflectionPbrParams pp = {};
+  reflection_pbr_of(&pbr, table, reinterpret_cast<const rt::LightRec*>(lights), nlights, pp);
+  const uint32_t S = params->samples, cap = params->max_bounces;
+  const size_t level_stride = (size_t)n * S;  // entries of one level's block
+  // every chain's length (rays), before anything is written
+  std::vector<uint8_t> len(level_stride, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!valid[i]) continue;
+    for (uint32_t k = 0; k < S; ++k) {
+      uint32_t b = 1;
+      for (;; ++b) {
+        const size_t j = (size_t)(b - 1) * level_stride + (size_t)i * S + k;
+        if (!(b < cap && chain_record_reflects(pp, hits, hit_group, hit_inst, j))) break;
+        if (b == levels)
+          return host_fail(fn + "pixel " + std::to_string(i) + ", sample " + std::to_string(k) + ": the chain continues " +
+                           "past the " + std::to_string(levels) + " supplied levels (max_bounces " + std::to_string(cap) + ")");
+      }
+      len[(size_t)i * S + k] = (uint8_t)b;
+    }
+  }
+  const bool shadow_models = (pp.flags & rt::kReflectShadowModels) != 0u;
+  const float fheight = (float)H;
+  if (lit_out) std::memset(lit_out, 0, (size_t)levels * level_stride * nlights);
+  if (nrays_out) std::memcpy(nrays_out, len.data(), level_stride);
+  for (uint32_t i = 0; i < n; ++i) {
+    float* out = radiance_out + 4 * (size_t)i;
+    if (!valid[i]) {
+      out[0] = out[1] = out[2] = out[3] = 0.0f;
+      continue;
+    }
+    const rt::V3 sky = rt::reflection_miss_color(py[i], fheight);
+    rt::ReflectionSum sum = rt::reflection_sum_zero();
+    for (uint32_t k = 0; k < S; ++k) {
+      rt::ChainLevel sk[rt::kMaxReflectionBounces - 1];
+      const uint32_t nb = len[(size_t)i * S + k];
+      float t1 = params->tmax;
+      rt::V3 col = sky;
+      for (uint32_t b = 1; b <= nb; ++b) {
+        const size_t j = (size_t)(b - 1) * level_stride + (size_t)i * S + k;
+        col = sky;
+        if (hits[4 * j + 3] == 0u) continue;  // a miss ends the chain: b == nb
+        const float* r = rays + 8 * j;
+        float t2;
+        std::memcpy(&t2, hits + 4 * j, sizeof(t2));
+        if (b == 1) t1 = t2;
+        const rt::V3 ro = rt::v3(r[0], r[1], r[2]), d = rt::v3(r[4], r[5], r[6]);
+        const rt::V3 n2 = rt::v3(hit_normal[4 * j], hit_normal[4 * j + 1], hit_normal[4 * j + 2]);
+        const rt::V3 P2 = rt::add(ro, rt::muls(d, t2));
+        if (hit_group[j] == 2u) {
+          const rt::LightRec& L0 = pp.rp.lights[0];
+          if (lit_out) lit_out[j * nlights] = 1;
+          const float c = rt::reflection_plane_color(n2, rt::v3(L0.position[0], L0.position[1], L0.position[2]), P2,
+                                                     occluded[j * nlights] != 0);
+          col = rt::v3(c, c, c);
+          continue;
+        }
+        const uint32_t mi = rt::material_index(pp.instance_material, pp.ninstances, pp.nmaterials, hit_inst[j]);
+        rt::SurfaceSplit st = rt::surface_split_begin(pp.table[mi], P2, n2, ro);
+        for (uint32_t l = 0; l < nlights; ++l) {
+          const rt::LightRec& Lr = pp.rp.lights[l];
+          rt::V3 L;
+          float nl;
+          bool occ = false;
+          if (shadow_models &&
+              rt::shadow_lit(rt::neg(n2), rt::v3(Lr.position[0], Lr.position[1], Lr.position[2]), P2, L, nl)) {
+            if (lit_out) lit_out[j * nlights + l] = 1;
+            occ = occluded[j * nlights + l] != 0;
+          }
+          rt::surface_split_light(st, pp.table[mi], Lr, P2, n2, rt::reflection_model_factor(occ));
+        }
+        col = rt::surface_split_end(st);
+        if (b < nb) sk[b - 1] = rt::ChainLevel{col, pp.table[mi].m.reflectivity};  // the level continues
+      }
+      rt::reflection_sum_add(sum, rt::reflection_chain_unwind(sk, nb - 1u, col), t1);
     }
     rt::reflection_reduce(sum, S, out);
   }

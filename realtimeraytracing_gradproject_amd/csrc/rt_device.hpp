@@ -1873,6 +1873,56 @@ RT_HD V3 surface_split_end(const SurfaceSplit& st) {
 RT_HD float reflection_model_factor(bool occluded) { return occluded ? 0.3f : 1.0f; }
 
 // ------------------------------------------------------------------------------------------
+// The chained PBR reflection pass (rt_dispatch_reflection_chain): the PBR reflection pass whose reflected
+// model hits reflect in turn, as ClosestHit's nested TraceRay does (Hit.hlsl:194-203). Each level is shaded by the
+// functions above; what is new is below: the continuation test, the continuation ray, the lerp and the unwind. Called
+// by the chain kernels per lane and by rt_host_reflection_chain_rays / rt_host_reflection_chain_radiance;
+// tests/reflection_chain_reference.py restates the fold in numpy and in float64.
+// ------------------------------------------------------------------------------------------
+
+constexpr int kMaxReflectionBounces = 18;  // RT_MAX_REFLECTION_BOUNCES
+static_assert(kMaxReflectionBounces == kMaxReflectDepth, "the chain pass follows what the frame kernels follow");
+
+// rt_dispatch_reflection_chain's launch: the PBR reflection pass's and the bounce cap (1..kMaxReflectionBounces).
+struct ReflectionChainParams {
+  ReflectionPbrParams pp;
+  uint32_t max_bounces;
+};
+
+// A level that continues: its own surface colour s_b and its material's reflectivity r_b. A chain of max_bounces rays
+// stores at most max_bounces - 1 of them.
+struct ChainLevel {
+  V3 s;
+  float r;
+};
+
+// Does the model hit of ray b (1-based) with table entry e send ray b + 1? The frame kernels' test on the material
+// (reflectivity != 0.0f) and the bounce cap.
+RT_HD bool reflection_chain_continues(const MaterialEntry& e, uint32_t b, uint32_t max_bounces) {
+  return e.m.reflectivity != 0.0f && b < max_bounces;
+}
+
+// The continuation ray of a hit at P with stored-form normal n, reached along d: rt_trace.hip's reflection_ray, which
+// is reflection_pbr_mirror under kReflectFrameRay (about n as stored; nn is not read) and reflection_origin.
+RT_HD void reflection_chain_ray(V3 P, V3 n, V3 d, V3& ro_next, V3& rd_next) {
+  const V3 m = reflection_pbr_mirror(d, n, n, kReflectFrameRay);
+  ro_next = reflection_origin(P, m);
+  rd_next = m;
+}
+
+// HLSL lerp(x, y, s) = x + s * (y - x), per channel (rt_trace.hip's lerp3; no special case at s == 1).
+RT_HD V3 reflection_chain_lerp(V3 x, V3 y, float s) {
+  return v3(x.x + s * (y.x - x.x), x.y + s * (y.y - x.y), x.z + s * (y.z - x.z));
+}
+
+// The colour of a chain whose innermost ray came back with c, through its n stored levels, innermost first: level k
+// sets lerp(s_k, <colour of level k + 1>, r_k) after its nested TraceRay returned.
+RT_HD V3 reflection_chain_unwind(const ChainLevel* sk, uint32_t n, V3 c) {
+  for (uint32_t k = n; k-- > 0u;) c = reflection_chain_lerp(sk[k].s, c, sk[k].r);
+  return c;
+}
+
+// ------------------------------------------------------------------------------------------
 // The diffuse indirect pass (rt_dispatch_indirect): one bounce of cosine-weighted rays about the facing
 // normal, each shaded as a PBR reflection ray is. It has no arithmetic of its own: the directions are the AO pass's
 // (ao_facing_normal, ao_sphere, ao_direction) under a seed of this pass's own, the origin, the per-ray colour, the

@@ -203,7 +203,8 @@ bool gbuffer_packet(const SceneView& scene, int schedule);
 //   ReflectionParams     rt_dispatch_reflection (§3.14): params.radiance and, when given, params.hits are written
 //   ReflectionPbrParams  rt_dispatch_reflection_pbr (§3.16): likewise; the material table rides in the kernel argument
 //   IndirectParams       rt_dispatch_indirect (§3.18): likewise, around the cosine-weighted rays of the indirect kernels
-// The last five read the camera and the frame size of their params.gb and none of its planes.
+//   ReflectionChainParams  rt_dispatch_reflection_chain (§3.20): likewise, with the level loop of the chain kernels
+// The last six read the camera and the frame size of their params.gb and none of its planes.
 template <typename P>
 hipError_t launch_grid_pass(const SceneView& scene, const P& params, const uint32_t* d_rows,
                             unsigned long long* d_stats, bool stats, int schedule, hipStream_t stream);

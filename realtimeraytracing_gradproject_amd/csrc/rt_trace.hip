@@ -1954,6 +1954,7 @@ __host__ __device__ __forceinline__ const GbufParams& gbuf(const ShadowParams& p
 __host__ __device__ __forceinline__ const GbufParams& gbuf(const ReflectionParams& p) { return p.gb; }
 __host__ __device__ __forceinline__ const GbufParams& gbuf(const ReflectionPbrParams& p) { return p.rp.gb; }
 __host__ __device__ __forceinline__ const GbufParams& gbuf(const IndirectParams& p) { return p.pp.rp.gb; }
+__host__ __device__ __forceinline__ const GbufParams& gbuf(const ReflectionChainParams& p) { return p.pp.rp.gb; }
 
 // The opening of every kernel on the G-buffer's grid, once per schedule: the lane's pixel, its camera ray and the
 // primary closest-hit walk. x: the pixel's column, orow: its entry of the row list (and of the planes: entry
@@ -2777,6 +2778,216 @@ __global__ __launch_bounds__(kBlock) void k_trace_indirect(SceneView sc, Indirec
   if (STATS) flush_stats<false>(cnt, stats);
 }
 
+// ------------------------------------------------------------------------------------------
+// Chained PBR reflection pass (rt_dispatch_reflection_chain): the PBR reflection kernels' launch shapes,
+// primary walk, first rays, per-level shading, reduction and planes, with a level loop per sample: a reflected model
+// hit whose material reflects sends the frame kernels' reflection ray (rt_device.hpp's reflection_chain_ray) and the
+// levels' colours are folded innermost first (reflection_chain_unwind), as ClosestHit's nested TraceRay returns them
+// (Hit.hlsl:194-203). Kernels of their own, so the PBR reflection kernels keep their instructions. The chain stack
+// (surface colour and reflectivity of up to 17 levels per lane) is indexed by the level, a run-time value, so it lives
+// in private (scratch) memory as the frame kernels' sk[] does; only lanes that continue touch it. A launch without
+// any chain measures level with the PBR pass (0.995 - 1.017 x), so no LDS stack was built.
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(SceneView) + sizeof(ReflectionChainParams) + 2 * sizeof(void*) <= 4096,
+              "rt_dispatch_reflection_chain's launch must fit the 4 KB kernel-argument segment");
+
+// Packet schedule: k_trace_reflection_pbr_packet's set-up, first rays and stores. Per sample a wave-uniform level
+// loop: one closest-hit packet for the lanes whose chain is still running, the PBR packet kernel's light loop on what
+// they hit (one any-hit packet per light that some lane needs), then the lanes that continue are marked; a lane that
+// ends at level b unwinds its own b - 1 stored levels and adds to its sum, and the loop leaves when no lane continues.
+// Lanes of one tile end at different levels; the level is uniform, so each unwind is a uniform loop under a lane mask.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(packet_block(1)) RT_REFLECT_SGPR_ATTR
+void k_trace_reflection_chain_packet(SceneView sc, ReflectionChainParams cp, const uint32_t* __restrict__ rows,
+                                     unsigned long long* __restrict__ stats) {
+  const ReflectionPbrParams& pp = cp.pp;
+  const ReflectionParams& rp = pp.rp;
+  const GbufParams& gb = rp.gb;
+  RT_GRID_PACKET_PRIMARY(gb);
+  bool need = false;
+  V3 m = v3(0.0f, 0.0f, 1.0f), nf = m, P = O;  // a dead lane's ray: finite, never traced
+  if (inimg && found) {
+    const V3 n = ao_normal(sc, hit);
+    if (ao_normal_valid(n)) {
+      need = true;
+      const V3 nn = normalize(n);
+      m = reflection_pbr_mirror(D, n, nn, pp.flags);
+      nf = ao_facing_normal(nn, D);
+      P = add(O, muls(D, hit.t));  // GetWorldHitPoint, the frame's expression
+    }
+  }
+  const bool shadow_models = (pp.flags & kReflectShadowModels) != 0u;  // uniform
+  const uint32_t base = reflection_base(x, py, rp.seed);
+  const uint32_t ns = wave_ballot(need) ? rp.samples : 0u;  // uniform
+  const V3 sky = reflection_miss_color(py, gb.fheight);
+  ReflectionSum sum = reflection_sum_zero();
+  uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+  ChainLevel sk[kMaxReflectionBounces - 1];  // private memory: written and read by continuing lanes only
+  for (uint32_t k = 0; k < ns; ++k) {
+    V3 d = reflection_direction(m, nf, rp.roughness, base, k);
+    V3 ro = reflection_origin(P, d);
+    bool live = need;  // the lane's chain is still running; a finished lane keeps its last ray: finite, never traced
+    float t1 = rp.tmax;
+    for (uint32_t b = 1u;; ++b) {  // uniform; b <= max_bounces <= kMaxReflectionBounces (rt_api.cpp)
+      if (STATS && live) ++cnt.refl;
+      HitRec h;
+      bool f;
+      trace_packet<false, STATS, 1, true, TT>(sc, &ro, &d, 0.001f, rp.tmax, &live, &f, &h, cnt);
+      const bool rh = live && f;
+      if (b == 1u) {
+        if (k == 0u && need) rec0 = reflection_record(f, h, rp.tmax);
+        if (rh) t1 = h.t;
+      }
+      V3 n2 = v3(0.0f, 0.0f, 1.0f), P2 = ro;  // a lane without a hit at this level: finite, shades nothing
+      bool plane = false;
+      uint32_t mi = 0u;
+      if (rh) {
+        n2 = hit_normal(sc, h, plane);
+        P2 = add(ro, muls(d, h.t));
+        mi = material_index(pp.instance_material, pp.ninstances, pp.nmaterials, h.inst);
+      }
+      const bool model = rh && !plane, floor = rh && plane;
+      SurfaceSplit st{};
+      if (model) st = surface_split_begin(pp.table[mi], P2, n2, ro);
+      float cpl = 0.0f;
+      for (uint32_t l = 0; l < rp.nlights; ++l) {
+        const LightRec& Lr = rp.lights[l];
+        const V3 lp = light_pos(Lr);
+        V3 L;
+        float nl;
+        const bool lit = shadow_models && model && shadow_lit(neg(n2), lp, P2, L, nl);
+        const bool tr = lit || (floor && l == 0u);
+        bool occ = false;
+        if (wave_ballot(tr)) {  // uniform
+          V3 sd = v3(0.0f, 0.0f, 1.0f);  // a dead lane's ray: finite, never traced
+          if (tr) sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+          if (STATS && tr) ++cnt.shadow;
+          HitRec hs;
+          bool o;
+          trace_packet<true, STATS, 1, false, TT>(sc, &P2, &sd, rp.shadow_tmin, 100000.0f, &tr, &o, &hs, cnt);
+          occ = tr && o;
+        }
+        if (floor && l == 0u) cpl = reflection_plane_color(n2, lp, P2, occ);
+        if (model) surface_split_light(st, pp.table[mi], Lr, P2, n2, reflection_model_factor(occ));
+      }
+      V3 col = sky;
+      if (floor) col = v3(cpl, cpl, cpl);
+      if (model) col = surface_split_end(st);
+      const bool cont = model && reflection_chain_continues(pp.table[mi], b, cp.max_bounces);
+      if (live && !cont) reflection_sum_add(sum, reflection_chain_unwind(sk, b - 1u, col), t1);
+      if (cont) {
+        sk[b - 1u] = ChainLevel{col, pp.table[mi].m.reflectivity};  // b < max_bounces: index <= 16
+        reflection_chain_ray(P2, n2, d, ro, d);
+      }
+      live = cont;
+      if (!wave_ballot(live)) break;  // uniform
+    }
+  }
+  if (inimg) {
+    const uint32_t o = orow * gb.width + x;  // < 2^32 pixels (rt_api.cpp)
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (need) reflection_reduce(sum, rp.samples, out);
+    reflection_store(rp, o, out, rec0);
+  }
+  if (STATS) flush_stats<true>(cnt, stats);
+}
+
+// Per-lane schedule: k_trace_reflection_pbr's, each lane running the level loop of its own samples.
+template <bool STATS, int TT>
+__global__ __launch_bounds__(kBlock) void k_trace_reflection_chain(SceneView sc, ReflectionChainParams cp,
+                                                                   const uint32_t* __restrict__ rows,
+                                                                   unsigned long long* __restrict__ stats) {
+  extern __shared__ int s_stack[];
+  const ReflectionPbrParams& pp = cp.pp;
+  const ReflectionParams& rp = pp.rp;
+  const GbufParams& gb = rp.gb;
+  GridLane g;
+  Counters cnt;
+  if (grid_lane_pixel(gb, g)) {
+    LaneStack stk;
+    V3 O, D;
+    HitRec hit;
+    const bool found = grid_lane_primary<STATS, TT>(sc, gb, rows, s_stack, g, stk, O, D, hit, cnt);
+    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);
+    if (found) {
+      const V3 n = ao_normal(sc, hit);
+      if (ao_normal_valid(n)) {
+        const V3 nn = normalize(n);
+        const V3 m = reflection_pbr_mirror(D, n, nn, pp.flags);
+        const V3 nf = ao_facing_normal(nn, D);
+        const V3 P = add(O, muls(D, hit.t));
+        const bool shadow_models = (pp.flags & kReflectShadowModels) != 0u;
+        const uint32_t base = reflection_base(g.x, g.py, rp.seed);
+        const V3 sky = reflection_miss_color(g.py, gb.fheight);
+        ReflectionSum sum = reflection_sum_zero();
+        ChainLevel sk[kMaxReflectionBounces - 1];  // private memory: touched by chains longer than one ray only
+        for (uint32_t k = 0; k < rp.samples; ++k) {
+          V3 d = reflection_direction(m, nf, rp.roughness, base, k);
+          V3 ro = reflection_origin(P, d);
+          float t1 = rp.tmax;
+          for (uint32_t b = 1u;; ++b) {  // b <= max_bounces <= kMaxReflectionBounces (rt_api.cpp)
+            if (STATS) ++cnt.refl;
+            HitRec h;
+            const bool f = trace<false, STATS, true, TT>(sc, ro, d, 0.001f, rp.tmax, h, stk, cnt);
+            if (b == 1u) {
+              if (k == 0u) rec0 = reflection_record(f, h, rp.tmax);
+              if (f) t1 = h.t;
+            }
+            V3 col = sky;
+            bool cont = false;
+            if (f) {
+              bool plane;
+              const V3 n2 = hit_normal(sc, h, plane);
+              const V3 P2 = add(ro, muls(d, h.t));
+              if (plane) {
+                const LightRec& L0 = rp.lights[0];
+                const V3 lp = light_pos(L0);
+                const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+                if (STATS) ++cnt.shadow;
+                HitRec hs;
+                const bool occ = trace<true, STATS, false, TT>(sc, P2, sd, rp.shadow_tmin, 100000.0f, hs, stk, cnt);
+                const float c = reflection_plane_color(n2, lp, P2, occ);
+                col = v3(c, c, c);
+              } else {
+                const uint32_t mi = material_index(pp.instance_material, pp.ninstances, pp.nmaterials, h.inst);
+                SurfaceSplit st = surface_split_begin(pp.table[mi], P2, n2, ro);
+                for (uint32_t l = 0; l < rp.nlights; ++l) {
+                  const LightRec& Lr = rp.lights[l];
+                  const V3 lp = light_pos(Lr);
+                  V3 L;
+                  float nl;
+                  bool occ = false;
+                  if (shadow_models && shadow_lit(neg(n2), lp, P2, L, nl)) {
+                    const V3 sd = shadow_direction(lp, 0.0f, 0u, 0u, P2);
+                    if (STATS) ++cnt.shadow;
+                    HitRec hs;
+                    occ = trace<true, STATS, false, TT>(sc, P2, sd, rp.shadow_tmin, 100000.0f, hs, stk, cnt);
+                  }
+                  surface_split_light(st, pp.table[mi], Lr, P2, n2, reflection_model_factor(occ));
+                }
+                col = surface_split_end(st);
+                if (reflection_chain_continues(pp.table[mi], b, cp.max_bounces)) {
+                  sk[b - 1u] = ChainLevel{col, pp.table[mi].m.reflectivity};  // b < max_bounces: index <= 16
+                  reflection_chain_ray(P2, n2, d, ro, d);
+                  cont = true;
+                }
+              }
+            }
+            if (!cont) {
+              reflection_sum_add(sum, reflection_chain_unwind(sk, b - 1u, col), t1);
+              break;
+            }
+          }
+        }
+        reflection_reduce(sum, rp.samples, out);
+      }
+    }
+    reflection_store(rp, g.orow * gb.width + g.x, out, rec0);
+  }
+  if (STATS) flush_stats<false>(cnt, stats);
+}
+
 // Un-interleaves the gathered strips (rank-major blocks; rank k holds strips s % nranks == k) into the RGBA8 frame.
 // in_bpp 3: the strips are RGB8 and the constant alpha 255 is restored here (RayGen.hlsl:42 writes float4(c, 1)).
 __global__ void k_assemble(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
@@ -3461,6 +3672,10 @@ template <bool S, int T>
 GridKernel<IndirectParams> grid_kernel(const IndirectParams&, bool packet) {
   return packet ? k_trace_indirect_packet<S, T> : k_trace_indirect<S, T>;
 }
+template <bool S, int T>
+GridKernel<ReflectionChainParams> grid_kernel(const ReflectionChainParams&, bool packet) {
+  return packet ? k_trace_reflection_chain_packet<S, T> : k_trace_reflection_chain<S, T>;
+}
 
 // The packet kernel's plain grid (a workgroup = RT_PACKET_WX x RT_PACKET_WY tiles of 8 x 8 pixels), or the per-lane
 // kernel's 16 x 16 pixel workgroups with their LDS stacks.
@@ -3494,6 +3709,8 @@ template hipError_t launch_grid_pass(const SceneView&, const ReflectionPbrParams
                                      bool, int, hipStream_t);
 template hipError_t launch_grid_pass(const SceneView&, const IndirectParams&, const uint32_t*, unsigned long long*,
                                      bool, int, hipStream_t);
+template hipError_t launch_grid_pass(const SceneView&, const ReflectionChainParams&, const uint32_t*,
+                                     unsigned long long*, bool, int, hipStream_t);
 
 hipError_t launch_assemble_strips(uint32_t W, uint32_t H, uint32_t nranks, uint32_t strip_rows,
                                   const void* gathered, void* out, hipStream_t s, uint32_t rank_stride_rows,
