@@ -46,7 +46,8 @@ extern "C" {
  * rt_resolve_gi_inputs, and rt_reflection_motion, rt_radiance_accumulate_reflection, the host twin
  * rt_host_reflection_motion and rt_reflection_motion_params, and rt_dispatch_reflection_chain, its host twins
  * rt_host_reflection_chain_rays and rt_host_reflection_chain_radiance with rt_host_last_error,
- * rt_reflection_chain_params and RT_MAX_REFLECTION_BOUNCES. */
+ * rt_reflection_chain_params and RT_MAX_REFLECTION_BOUNCES, and rt_ao_accumulate_planes, rt_ao_atrous_planes, their
+ * host twins rt_host_ao_accumulate_planes and rt_host_ao_atrous_planes and RT_MAX_FILTER_PLANES. */
 #define RT_API_VERSION 4
 
 typedef struct rt_ctx* rt_ctx_t;
@@ -689,6 +690,46 @@ typedef struct { uint32_t iterations; float depth_tol; float normal_cos; } rt_ao
  * or out-of-range params, W or H of 0. */
 rt_status rt_ao_atrous(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
                        const float* guide, float* ao_out, float* tmp, void* hip_stream);
+
+/* ---- The AO filter over several planes in one launch per pass --------------------------------------
+ * A deferred frame filters one visibility plane per light and the AO plane under the same motion and guide planes.
+ * What rt_ao_accumulate and rt_ao_atrous compute from those alone (the reprojection's accepted taps with their
+ * weights, sw and sh; the 25 edge-stopping weights and their sum) is computed once per pixel here, and only sa is
+ * per plane, over the same taps in the same order with the same expressions. The preamble of the AO filter holds
+ * unchanged: whole W x H planes, asynchronous on hip_stream, a context only, no allocation, no scratch memory.
+ * cur, prev, out, in, tmp: HOST arrays of nplanes DEVICE pointers, each to W*H floats, 4-byte aligned. The arrays are
+ * copied into the launch during the call and may be freed when it returns. The planes need not be contiguous with
+ * each other (the L rows of rt_dispatch_shadow's vis and an AO plane that lives elsewhere will do). */
+#define RT_MAX_FILTER_PLANES 17   /* rt_set_shading's 16 lights + the AO plane */
+
+/* rt_ao_accumulate for nplanes planes that share ONE history plane (hist_prev / hist_out): a caller who wants a
+ * history per plane keeps using rt_ao_accumulate. motion, guide_cur, guide_prev, hist_prev, hist_out: as
+ * rt_ao_accumulate's.
+ *   out[p] equals, bit for bit, what rt_ao_accumulate writes to ao_out when given ao_cur = cur[p], ao_prev = prev[p],
+ *   hist_prev and the same other arguments; hist_out is that call's hist_out, for any p (they are identical).
+ * A tap rt_ao_accumulate skips is skipped here too, in every plane: it is neither read nor multiplied by a zero.
+ * prev, hist_prev and guide_prev: all given or all NULL (the first frame). out[p] == cur[p] is allowed for the same p
+ * (the in-place form: a pixel reads only its own cur[p] entry).
+ * RT_E_INVALID, nothing written, rt_last_error naming the argument and the plane index: nplanes of 0 or above
+ * RT_MAX_FILTER_PLANES; a NULL table or a NULL entry; a misaligned plane; ANY two pointers equal among all tables and
+ * single planes (two inputs included) other than out[p] == cur[p]; only some of the prev arguments; and every case
+ * in which rt_ao_accumulate returns it. RT_E_UNSUPPORTED: rt_ao_accumulate's W, H limits. */
+rt_status rt_ao_accumulate_planes(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_temporal_params* params,
+                                  uint32_t nplanes, const float* const* cur, const float* motion,
+                                  const float* guide_cur, const float* const* prev, const float* hist_prev,
+                                  const float* guide_prev, float* const* out, float* hist_out, void* hip_stream);
+
+/* rt_ao_atrous for nplanes planes under one guide: one launch per iteration whatever nplanes is.
+ *   out[p] equals, bit for bit, the ao_out of rt_ao_atrous(in[p], guide, out[p], tmp[p]).
+ * Every in[p] is unwritten; every tmp[p] is unwritten when iterations == 1, and tmp may be NULL only then. A tap
+ * rt_ao_atrous skips (outside the frame, or no surface) is skipped here too: neither read nor multiplied by a zero.
+ * RT_E_INVALID, nothing written, rt_last_error naming the argument and the plane index: nplanes of 0 or above
+ * RT_MAX_FILTER_PLANES; a NULL table (tmp: only with iterations > 1) or a NULL entry; a misaligned plane; any two
+ * pointers equal among in, out, tmp and guide; and every case in which rt_ao_atrous returns it. RT_E_UNSUPPORTED:
+ * rt_ao_atrous's W, H limits. RT_ATROUS_FORM selects the kernel form as for rt_ao_atrous. */
+rt_status rt_ao_atrous_planes(rt_ctx_t ctx, uint32_t W, uint32_t H, const rt_ao_atrous_params* params,
+                              uint32_t nplanes, const float* const* in, const float* guide,
+                              float* const* out, float* const* tmp, void* hip_stream);
 
 /* ---- Radiance filter: the AO filter's pair for planes of 4-float entries ---------------------------
  * A variance-guided (SVGF-style) temporal accumulation and a-trous blur for any W*H x 4 float plane; today that is
@@ -1464,6 +1505,16 @@ rt_status rt_host_ao_accumulate(uint32_t W, uint32_t H, const rt_ao_temporal_par
                                 const float* hist_prev, const float* guide_prev, float* ao_out, float* hist_out);
 rt_status rt_host_ao_atrous(uint32_t W, uint32_t H, const rt_ao_atrous_params* params, const float* ao_in,
                             const float* guide, float* ao_out, float* tmp);
+
+/* rt_ao_accumulate_planes and rt_ao_atrous_planes on host arrays, likewise (tables of host planes), through the
+ * per-pixel functions their kernels call and not through a loop over the twins above, so the shared arithmetic is
+ * what runs. A refused call's reason (the argument, the plane index) is kept for rt_host_last_error. */
+rt_status rt_host_ao_accumulate_planes(uint32_t W, uint32_t H, const rt_ao_temporal_params* params, uint32_t nplanes,
+                                       const float* const* cur, const float* motion, const float* guide_cur,
+                                       const float* const* prev, const float* hist_prev, const float* guide_prev,
+                                       float* const* out, float* hist_out);
+rt_status rt_host_ao_atrous_planes(uint32_t W, uint32_t H, const rt_ao_atrous_params* params, uint32_t nplanes,
+                                   const float* const* in, const float* guide, float* const* out, float* const* tmp);
 
 /* rt_radiance_accumulate and rt_radiance_atrous on host arrays, likewise. */
 rt_status rt_host_radiance_accumulate(uint32_t W, uint32_t H, const rt_radiance_temporal_params* params,

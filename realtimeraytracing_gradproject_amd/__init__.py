@@ -292,6 +292,9 @@ SIGNATURES = [
     ("rt_ao_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P,
                               _P]),
     ("rt_ao_atrous", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P, _P]),
+    ("rt_ao_accumulate_planes", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _U32, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P]),
+    ("rt_ao_atrous_planes", _I, [_P, _U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _U32, _P, _P, _P, _P, _P]),
     ("rt_radiance_accumulate", _I, [_P, _U32, _U32, ctypes.POINTER(rt_radiance_temporal_params), _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P]),
     ("rt_radiance_atrous", _I, [_P, _U32, _U32, ctypes.POINTER(rt_radiance_atrous_params), _P, _P, _P, _P, _P, _P, _P,
@@ -378,6 +381,9 @@ SIGNATURES = [
     ("rt_host_denoise_guide", _I, [_U32, _P, _P, _U32, _P]),
     ("rt_host_ao_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rt_host_ao_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _P, _P, _P, _P]),
+    ("rt_host_ao_accumulate_planes", _I, [_U32, _U32, ctypes.POINTER(rt_ao_temporal_params), _U32, _P, _P, _P, _P, _P,
+                                          _P, _P, _P]),
+    ("rt_host_ao_atrous_planes", _I, [_U32, _U32, ctypes.POINTER(rt_ao_atrous_params), _U32, _P, _P, _P, _P]),
     ("rt_host_radiance_accumulate", _I, [_U32, _U32, ctypes.POINTER(rt_radiance_temporal_params), _P, _P, _P, _P, _P,
                                          _P, _P, _P]),
     ("rt_host_radiance_atrous", _I, [_U32, _U32, ctypes.POINTER(rt_radiance_atrous_params), _P, _P, _P, _P, _P, _P,
@@ -1110,6 +1116,61 @@ def host_ao_atrous(width: int, height: int, ao_in, guide, iterations: int = 3, d
     st = lib.rt_host_ao_atrous(width, height, ctypes.byref(p), _vp(a), _vp(g), _vp(out), _vp(tmp))
     if st != RT_OK:
         raise RtError(st, "rt_host_ao_atrous")
+    return out
+
+
+RT_MAX_FILTER_PLANES = 17
+
+
+def _host_planes(x, n: int) -> np.ndarray:
+    """A plane set on the host: a 2-D array whose rows are the planes, or a sequence of them -> an own (P, n) float32
+    array."""
+    rows = [_f32(r, n) for r in x]
+    return np.array(rows, dtype=np.float32).reshape(len(rows), n)
+
+
+def _plane_table(a: np.ndarray):
+    """The table of row addresses of a (P, n) array (the array must outlive the call)."""
+    return (ctypes.c_void_p * a.shape[0])(*[a.ctypes.data + r * a.strides[0] for r in range(a.shape[0])])
+
+
+def host_ao_accumulate_planes(width: int, height: int, cur, motion, guide_cur, prev=None, hist_prev=None,
+                              guide_prev=None, max_history: int = 32, depth_tol: float = 0.02,
+                              normal_cos: float = 0.9, in_place: bool = False):
+    """rt_host_ao_accumulate_planes: host_ao_accumulate for P planes that share the history plane (no GPU). cur, prev:
+    plane sets (a (P, width * height) array, or a sequence of planes); the other arguments as host_ao_accumulate's.
+    in_place: the library is handed out[p] == cur[p] (on a copy: the caller's arrays are not written). Returns (out,
+    hist_out): (P, width * height) and width * height float32."""
+    n = width * height
+    c, mo, gc = _host_planes(cur, n), _f32(motion, 4 * n), _f32(guide_cur, 4 * n)
+    pv = None if prev is None else _host_planes(prev, n)
+    if pv is not None and pv.shape[0] != c.shape[0]:
+        raise ValueError(f"expected {c.shape[0]} prev planes, got {pv.shape[0]}")
+    hp = None if hist_prev is None else _f32(hist_prev, n)
+    gp = None if guide_prev is None else _f32(guide_prev, 4 * n)
+    p = rt_ao_temporal_params(max_history, depth_tol, normal_cos)
+    out = c if in_place else np.zeros_like(c)
+    hist = np.zeros(n, np.float32)
+    st = lib.rt_host_ao_accumulate_planes(width, height, ctypes.byref(p), c.shape[0], _plane_table(c), _vp(mo), _vp(gc),
+                                          None if pv is None else _plane_table(pv), _vp(hp), _vp(gp), _plane_table(out),
+                                          _vp(hist))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_host_last_error().decode() or "rt_host_ao_accumulate_planes")
+    return out, hist
+
+
+def host_ao_atrous_planes(width: int, height: int, planes_in, guide, iterations: int = 3, depth_tol: float = 0.02,
+                          normal_cos: float = 0.9):
+    """rt_host_ao_atrous_planes: host_ao_atrous for P planes under one guide (no GPU). planes_in: a plane set, as
+    host_ao_accumulate_planes'. Returns (P, width * height) float32."""
+    n = width * height
+    a, g = _host_planes(planes_in, n), _f32(guide, 4 * n)
+    p = rt_ao_atrous_params(iterations, depth_tol, normal_cos)
+    out, tmp = np.zeros_like(a), np.zeros_like(a)
+    st = lib.rt_host_ao_atrous_planes(width, height, ctypes.byref(p), a.shape[0], _plane_table(a), _vp(g),
+                                      _plane_table(out), _plane_table(tmp))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_host_last_error().decode() or "rt_host_ao_atrous_planes")
     return out
 
 
@@ -2096,6 +2157,58 @@ class Context:
         self._check(self._lib.rt_ao_atrous(self._h, width, height, ctypes.byref(p), self._plane(m, "ao_in", ao_in, n),
                                            self._plane(m, "guide", guide, 4 * n), self._plane(m, "ao_out", ao_out, n),
                                            self._plane(m, "tmp", tmp, n), stream), "rt_ao_atrous")
+
+    @classmethod
+    def _plane_set(cls, method: str, name: str, planes, words: int):
+        """A set of filter planes -> (the host table of their addresses, their count). planes: a 2-D tensor whose rows
+        are the planes, or a sequence of 1-D tensors (raw addresses and None are passed through, for the library to
+        judge); every row is checked as _plane checks a plane. None -> (None, 0)."""
+        if planes is None:
+            return None, 0
+        if not isinstance(planes, (list, tuple)):
+            if planes.dim() != 2:
+                raise ValueError(f"{method}: {name} must be a 2-D tensor of planes or a sequence of planes")
+            planes = [planes[r] for r in range(planes.shape[0])]
+        ptrs = [cls._plane(method, f"{name}[{r}]", t, words) for r, t in enumerate(planes)]
+        return (ctypes.c_void_p * len(ptrs))(*ptrs), len(ptrs)
+
+    def ao_accumulate_planes(self, width: int, height: int, cur, motion, guide_cur, out, hist_out, prev=None,
+                             hist_prev=None, guide_prev=None, max_history: int = 32, depth_tol: float = 0.02,
+                             normal_cos: float = 0.9, stream: Optional[int] = None):
+        """rt_ao_accumulate_planes: ao_accumulate for up to 17 planes in one launch (a frame's visibility planes and
+        its AO plane), which share the motion plane, the guides and ONE history plane; every out plane equals
+        ao_accumulate's bit for bit. cur, out, prev: plane sets (a 2-D tensor whose rows are the planes, or a sequence
+        of 1-D tensors, which need not be neighbours in memory). prev, hist_prev, guide_prev all None: the first
+        frame. out[p] may be cur[p]; no other two planes of the call may be the same."""
+        n, m = width * height, "ao_accumulate_planes"
+        tc, count = self._plane_set(m, "cur", cur, n)
+        to, no = self._plane_set(m, "out", out, n)
+        tp, np_ = self._plane_set(m, "prev", prev, n)
+        if no != count or (prev is not None and np_ != count):
+            raise ValueError(f"{m}: cur has {count} planes, out {no}" + ("" if prev is None else f", prev {np_}"))
+        p = rt_ao_temporal_params(max_history, depth_tol, normal_cos)
+        self._check(self._lib.rt_ao_accumulate_planes(
+            self._h, width, height, ctypes.byref(p), count, tc, self._plane(m, "motion", motion, 4 * n),
+            self._plane(m, "guide_cur", guide_cur, 4 * n), tp, self._plane(m, "hist_prev", hist_prev, n),
+            self._plane(m, "guide_prev", guide_prev, 4 * n), to, self._plane(m, "hist_out", hist_out, n), stream),
+            "rt_ao_accumulate_planes")
+
+    def ao_atrous_planes(self, width: int, height: int, planes_in, guide, planes_out, tmp=None, iterations: int = 3,
+                         depth_tol: float = 0.02, normal_cos: float = 0.9, stream: Optional[int] = None):
+        """rt_ao_atrous_planes: ao_atrous for up to 17 planes under one guide, one launch per iteration; every
+        planes_out plane equals ao_atrous's bit for bit, planes_in is not written. planes_in, planes_out, tmp: plane
+        sets as ao_accumulate_planes'; tmp (one plane per input plane) is needed from two iterations on."""
+        n, m = width * height, "ao_atrous_planes"
+        ti, count = self._plane_set(m, "planes_in", planes_in, n)
+        to, no = self._plane_set(m, "planes_out", planes_out, n)
+        tt, nt = self._plane_set(m, "tmp", tmp, n)
+        if no != count or (tmp is not None and nt != count):
+            raise ValueError(f"{m}: planes_in has {count} planes, planes_out {no}" +
+                             ("" if tmp is None else f", tmp {nt}"))
+        p = rt_ao_atrous_params(iterations, depth_tol, normal_cos)
+        self._check(self._lib.rt_ao_atrous_planes(self._h, width, height, ctypes.byref(p), count, ti,
+                                                  self._plane(m, "guide", guide, 4 * n), to, tt, stream),
+                    "rt_ao_atrous_planes")
 
     def radiance_accumulate(self, width: int, height: int, rad_cur, motion, guide_cur, rad_out, moments_out,
                             rad_prev=None, moments_prev=None, guide_prev=None, max_history: int = 32,

@@ -2374,6 +2374,142 @@ void atrous_planes(uint32_t k, uint32_t n, const float* ao_in, float* ao_out, fl
   *dst = plane(k);
 }
 
+// ---- The filter over several planes: the checks of rt_ao_accumulate_planes / rt_ao_atrous_planes and
+// their host twins. A refusal names the argument and, for a table's entry, the plane index. -------------------------
+struct NamedPlane {  // a pointer argument: a single plane (index < 0) or entry `index` of a table
+  const void* p;
+  const char* name;
+  int index;
+  std::string text() const { return index < 0 ? std::string(name) : std::string(name) + "[" + std::to_string(index) + "]"; }
+};
+
+struct PlaneList {  // every pointer of a call, for the pairwise test: 3 tables of 17 and 5 single planes at most
+  NamedPlane v[3 * rt::kMaxFilterPlanes + 5];
+  int n = 0;
+  void add(const void* p, const char* name, int index = -1) {
+    if (p) v[n++] = NamedPlane{p, name, index};
+  }
+  // any two equal, other than `a`[p] and `b`[p] of the same p (accumulate's in-place form)
+  std::string alias(const char* a = nullptr, const char* b = nullptr) const {
+    for (int i = 0; i < n; ++i)
+      for (int j = i + 1; j < n; ++j) {
+        if (v[i].p != v[j].p) continue;
+        const bool pair = a && v[i].index >= 0 && v[i].index == v[j].index &&
+                          ((!std::strcmp(v[i].name, a) && !std::strcmp(v[j].name, b)) ||
+                           (!std::strcmp(v[i].name, b) && !std::strcmp(v[j].name, a)));
+        if (!pair) return v[j].text() + " is " + v[i].text();
+      }
+    return std::string();
+  }
+};
+
+extern "C++" {  // they return strings
+// A table of nplanes planes: given, every entry non-null and aligned to 4 bytes.
+std::string table_error(const float* const* t, uint32_t nplanes, const char* name) {
+  if (!t) return std::string("null ") + name + " table";
+  for (uint32_t p = 0; p < nplanes; ++p) {
+    if (!t[p]) return std::string(name) + "[" + std::to_string(p) + "] is null";
+    if (misaligned(t[p], 4)) return std::string(name) + "[" + std::to_string(p) + "] is not aligned to 4 bytes";
+  }
+  return std::string();
+}
+
+std::string nplanes_error(uint32_t nplanes) {
+  if (nplanes == 0) return "nplanes is 0";
+  if (nplanes > (uint32_t)rt::kMaxFilterPlanes)
+    return "nplanes " + std::to_string(nplanes) + " above RT_MAX_FILTER_PLANES (" +
+           std::to_string(rt::kMaxFilterPlanes) + ")";
+  return std::string();
+}
+
+std::string accumulate_planes_error(uint32_t W, uint32_t H, const rt_ao_temporal_params* p, uint32_t nplanes,
+                                    const float* const* cur, const float* motion, const float* guide_cur,
+                                    const float* const* prev, const float* hist_prev, const float* guide_prev,
+                                    float* const* out, const float* hist_out, bool align, rt_status* st) {
+  if (const char* why = denoise_frame_error(W, H, st)) return why;
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (p->max_history < 1 || p->max_history > 1024) return "max_history outside 1..1024";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!(p->normal_cos >= -1.0f && p->normal_cos < 1.0f)) return "normal_cos outside [-1, 1)";
+  std::string why = nplanes_error(nplanes);
+  if (!why.empty()) return why;
+  if (!motion) return "null motion plane";
+  if (!guide_cur) return "null guide_cur";
+  if (!hist_out) return "null hist_out";
+  const int nprev = (prev != nullptr) + (hist_prev != nullptr) + (guide_prev != nullptr);
+  if (nprev != 0 && nprev != 3) return "prev, hist_prev and guide_prev must be all given or all NULL";
+  if (!(why = table_error(cur, nplanes, "cur")).empty()) return why;
+  if (!(why = table_error(out, nplanes, "out")).empty()) return why;
+  if (prev && !(why = table_error(prev, nplanes, "prev")).empty()) return why;
+  const size_t a4 = align ? 16 : 4;
+  if (misaligned(motion, a4)) return "motion plane misaligned";
+  if (misaligned(guide_cur, a4)) return "guide_cur misaligned";
+  if (misaligned(guide_prev, a4)) return "guide_prev misaligned";
+  if (misaligned(hist_prev, 4)) return "hist_prev is not aligned to 4 bytes";
+  if (misaligned(hist_out, 4)) return "hist_out is not aligned to 4 bytes";
+  PlaneList l;
+  l.add(motion, "motion"), l.add(guide_cur, "guide_cur"), l.add(hist_prev, "hist_prev"), l.add(guide_prev, "guide_prev");
+  l.add(hist_out, "hist_out");
+  for (uint32_t i = 0; i < nplanes; ++i) l.add(cur[i], "cur", (int)i);
+  for (uint32_t i = 0; prev && i < nplanes; ++i) l.add(prev[i], "prev", (int)i);
+  for (uint32_t i = 0; i < nplanes; ++i) l.add(out[i], "out", (int)i);
+  return l.alias("cur", "out");
+}
+
+std::string atrous_planes_error(uint32_t W, uint32_t H, const rt_ao_atrous_params* p, uint32_t nplanes,
+                                const float* const* in, const float* guide, float* const* out, float* const* tmp,
+                                bool align, rt_status* st) {
+  if (const char* why = denoise_frame_error(W, H, st)) return why;
+  *st = RT_E_INVALID;
+  if (!p) return "null params";
+  if (p->iterations < 1 || p->iterations > 5) return "iterations outside 1..5";
+  if (!std::isfinite(p->depth_tol) || !(p->depth_tol > 0.0f)) return "depth_tol not finite and > 0";
+  if (!(p->normal_cos >= -1.0f && p->normal_cos < 1.0f)) return "normal_cos outside [-1, 1)";
+  std::string why = nplanes_error(nplanes);
+  if (!why.empty()) return why;
+  if (!guide) return "null guide";
+  if (!tmp && p->iterations > 1) return "null tmp table with more than one iteration";
+  if (!(why = table_error(in, nplanes, "in")).empty()) return why;
+  if (!(why = table_error(out, nplanes, "out")).empty()) return why;
+  if (tmp && !(why = table_error(tmp, nplanes, "tmp")).empty()) return why;
+  if (misaligned(guide, align ? 16 : 4)) return "guide misaligned";
+  PlaneList l;
+  l.add(guide, "guide");
+  for (uint32_t i = 0; i < nplanes; ++i) l.add(in[i], "in", (int)i);
+  for (uint32_t i = 0; i < nplanes; ++i) l.add(out[i], "out", (int)i);
+  for (uint32_t i = 0; tmp && i < nplanes; ++i) l.add(tmp[i], "tmp", (int)i);
+  return l.alias();
+}
+}  // extern "C++"
+
+rt::AoTemporalPlanes temporal_planes_of(uint32_t W, uint32_t H, const rt_ao_temporal_params* p, uint32_t nplanes,
+                                        const float* const* cur, const float* motion, const float* guide_cur,
+                                        const float* const* prev, const float* hist_prev, const float* guide_prev,
+                                        float* const* out, float* hist_out) {
+  rt::AoTemporalPlanes a = {};
+  a.W = W, a.H = H, a.nplanes = nplanes;
+  a.max_history = (float)p->max_history;
+  a.depth_tol = p->depth_tol, a.normal_cos = p->normal_cos;
+  a.motion = motion, a.guide_cur = guide_cur, a.hist_prev = hist_prev, a.guide_prev = guide_prev;
+  a.hist_out = hist_out;
+  for (uint32_t i = 0; i < nplanes; ++i) a.cur[i] = cur[i], a.prev[i] = prev ? prev[i] : nullptr, a.out[i] = out[i];
+  return a;
+}
+
+// Iteration k of rt_ao_atrous_planes: atrous_planes' ping-pong for every plane.
+rt::AtrousPlanes atrous_planes_iteration(uint32_t k, uint32_t W, uint32_t H, const rt_ao_atrous_params* p,
+                                         uint32_t nplanes, const float* const* in, const float* guide,
+                                         float* const* out, float* const* tmp) {
+  rt::AtrousPlanes a = {};
+  a.W = W, a.H = H, a.s = 1u << k, a.nplanes = nplanes;
+  a.depth_tol = p->depth_tol, a.normal_cos = p->normal_cos;
+  a.guide = guide;
+  for (uint32_t i = 0; i < nplanes; ++i)
+    atrous_planes(k, p->iterations, in[i], out[i], tmp ? tmp[i] : nullptr, &a.in[i], &a.out[i]);
+  return a;
+}
+
 }  // namespace
 
 rt_status rt_denoise_guide(rt_ctx_t c, uint32_t n, const float* normal, const float* depth, uint32_t depth_stride,
@@ -2420,6 +2556,40 @@ rt_status rt_ao_atrous(rt_ctx_t c, uint32_t W, uint32_t H, const rt_ao_atrous_pa
     const hipError_t e = rt::launch_ao_atrous(W, H, 1u << k, params->depth_tol, params->normal_cos, src, guide, dst,
                                               c->atrous_form, s);
     if (e != hipSuccess) return hip_fail(c, e, "a-trous launch");
+  }
+  return RT_OK;
+}
+
+rt_status rt_ao_accumulate_planes(rt_ctx_t c, uint32_t W, uint32_t H, const rt_ao_temporal_params* params,
+                                  uint32_t nplanes, const float* const* cur, const float* motion,
+                                  const float* guide_cur, const float* const* prev, const float* hist_prev,
+                                  const float* guide_prev, float* const* out, float* hist_out, void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  const std::string why = accumulate_planes_error(W, H, params, nplanes, cur, motion, guide_cur, prev, hist_prev,
+                                                  guide_prev, out, hist_out, true, &st);
+  if (!why.empty()) return fail(c, st, "rt_ao_accumulate_planes: " + why);
+  (void)hipSetDevice(c->device);
+  const hipError_t e = rt::launch_ao_accumulate_planes(
+      temporal_planes_of(W, H, params, nplanes, cur, motion, guide_cur, prev, hist_prev, guide_prev, out, hist_out),
+      pick_stream(c, stream));
+  if (e != hipSuccess) return hip_fail(c, e, "accumulate (planes) launch");
+  return RT_OK;
+}
+
+rt_status rt_ao_atrous_planes(rt_ctx_t c, uint32_t W, uint32_t H, const rt_ao_atrous_params* params, uint32_t nplanes,
+                              const float* const* in, const float* guide, float* const* out, float* const* tmp,
+                              void* stream) {
+  if (!c) return RT_E_INVALID;
+  rt_status st = RT_OK;
+  const std::string why = atrous_planes_error(W, H, params, nplanes, in, guide, out, tmp, true, &st);
+  if (!why.empty()) return fail(c, st, "rt_ao_atrous_planes: " + why);
+  (void)hipSetDevice(c->device);
+  const hipStream_t s = pick_stream(c, stream);
+  for (uint32_t k = 0; k < params->iterations; ++k) {
+    const hipError_t e = rt::launch_ao_atrous_planes(
+        atrous_planes_iteration(k, W, H, params, nplanes, in, guide, out, tmp), c->atrous_form, s);
+    if (e != hipSuccess) return hip_fail(c, e, "a-trous (planes) launch");
   }
   return RT_OK;
 }
@@ -3882,6 +4052,72 @@ bool chain_record_reflects(const rt::ReflectionPbrParams& pp, const uint32_t* hi
 }  // namespace
 
 const char* rt_host_last_error(void) { return g_host_error.c_str(); }
+
+// Host services: rt_ao_accumulate_planes and rt_ao_atrous_planes on host arrays, through the per-pixel functions their
+// kernels call (ao_accumulate_planes_pixel, atrous_planes_pixel), not through the per-plane twins: the shared
+// arithmetic itself runs here. A refused call leaves its reason (the argument, the plane index) for
+// rt_host_last_error.
+rt_status rt_host_ao_accumulate_planes(uint32_t W, uint32_t H, const rt_ao_temporal_params* params, uint32_t nplanes,
+                                       const float* const* cur, const float* motion, const float* guide_cur,
+                                       const float* const* prev, const float* hist_prev, const float* guide_prev,
+                                       float* const* out, float* hist_out) {
+  rt_status st = RT_OK;
+  const std::string why = accumulate_planes_error(W, H, params, nplanes, cur, motion, guide_cur, prev, hist_prev,
+                                                  guide_prev, out, hist_out, false, &st);
+  if (!why.empty()) {
+    g_host_error = "rt_host_ao_accumulate_planes: " + why;
+    return st;
+  }
+  const rt::AoTemporalPlanes a =
+      temporal_planes_of(W, H, params, nplanes, cur, motion, guide_cur, prev, hist_prev, guide_prev, out, hist_out);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) rt::ao_accumulate_planes_pixel(a, x, y);
+  return RT_OK;
+}
+
+namespace {
+struct HostGuideTap {  // rt_denoise.hip's GlobalGuideTap on a host array
+  const float* guide;
+  int x, y, s, W, H;
+  bool operator()(int dx, int dy, float q[4]) const {
+    const int xx = x + dx * s, yy = y + dy * s;
+    if (xx < 0 || yy < 0 || xx >= W || yy >= H) return false;
+    rt::ld4(guide + 4 * ((size_t)yy * (size_t)W + (size_t)xx), q);
+    return true;
+  }
+};
+}  // namespace
+
+rt_status rt_host_ao_atrous_planes(uint32_t W, uint32_t H, const rt_ao_atrous_params* params, uint32_t nplanes,
+                                   const float* const* in, const float* guide, float* const* out, float* const* tmp) {
+  rt_status st = RT_OK;
+  const std::string why = atrous_planes_error(W, H, params, nplanes, in, guide, out, tmp, false, &st);
+  if (!why.empty()) {
+    g_host_error = "rt_host_ao_atrous_planes: " + why;
+    return st;
+  }
+  for (uint32_t k = 0; k < params->iterations; ++k) {
+    const rt::AtrousPlanes a = atrous_planes_iteration(k, W, H, params, nplanes, in, guide, out, tmp);
+    const int s = (int)a.s;
+    for (uint32_t y = 0; y < H; ++y)
+      for (uint32_t x = 0; x < W; ++x) {
+        const size_t i = (size_t)y * W + x;
+        float g[4];
+        rt::ld4(guide + 4 * i, g);
+        if (g[3] == 0.0f) {
+          for (uint32_t p = 0; p < nplanes; ++p) a.out[p][i] = a.in[p][i];
+          continue;
+        }
+        rt::atrous_planes_pixel(
+            g, a.s, a.depth_tol, a.normal_cos, nplanes, HostGuideTap{guide, (int)x, (int)y, s, (int)W, (int)H},
+            [&](uint32_t p, int dx, int dy, bool on) {  // a skipped tap is not read
+              return on ? a.in[p][(size_t)((int)y + dy * s) * (size_t)W + (size_t)((int)x + dx * s)] : 0.0f;
+            },
+            [&](uint32_t p, float v) { a.out[p][i] = v; });
+      }
+  }
+  return RT_OK;
+}
 
 // Host service: rt_dispatch_reflection_chain's continuation rays for m traced rays, through the functions the chain
 // kernels call (material_index, reflection_chain_continues, reflection_chain_ray). No context, no GPU call.

@@ -14,6 +14,11 @@
 //                       and the values a [12][36] array of floats: a half-wave reads 32 consecutive entries of one row
 //                       (512 contiguous bytes by ds_read_b128, every 16-lane group of which covers the 64 banks once;
 //                       128 contiguous bytes by ds_read_b32), whatever the tap offset, so no read conflicts.
+//   k_ao_accumulate_planes / k_ao_atrous_planes_direct / k_ao_atrous_planes_lds  the three kernels above over up to 17
+//                       planes in one launch (rt_ao_accumulate_planes, rt_ao_atrous_planes): the motion
+//                       and guide entries are loaded, the reprojection taps tested and the 25 weights computed once per
+//                       pixel; a plane costs its own values only. The pointer tables ride in the kernel argument; the
+//                       staged form keeps the guide tile and 7 value tiles in LDS (19,008 B).
 //   k_shade_resolve     the deferred resolve (rt_shade_resolve), one pixel per lane: G-buffer planes,
 //                       the per-light visibility planes and the AO plane -> the colour frame (one 16-byte store, and
 //                       4 bytes of RGBA8 when asked for). The lights and the camera ride in the kernel argument.
@@ -40,7 +45,7 @@
 //
 // The arithmetic of all of them is rt_device.hpp's (denoise_guide_entry, ao_accumulate_pixel, atrous_pixel,
 // resolve_pixel, reflection_composite_pixel, resolve_pbr_pixel, resolve_gi_pixel, radiance_accumulate_pixel,
-// radiance_atrous_pixel, reflection_motion_pixel),
+// radiance_atrous_pixel, reflection_motion_pixel, ao_accumulate_planes_pixel, atrous_planes_pixel and its two halves),
 // which the host twins in rt_api.cpp call too: the
 // kernels differ from them in where a value is read, never in how it is used.
 // Grids are one-dimensional (tile index), so a frame's height is not bounded by the grid's y limit.
@@ -154,6 +159,143 @@ __global__ __launch_bounds__(256) void k_ao_atrous_lds(uint32_t W, uint32_t H, u
   }
   const float g[4] = {c.x, c.y, c.z, c.w};
   out[i] = atrous_pixel(g, s, depth_tol, normal_cos, LdsTap{sg, sv, at});
+}
+
+// ---- the same two passes over several planes in one launch ------------------------------------------
+// The tables of plane pointers are part of the kernel argument: a plane's pointer is a scalar load at a wave-uniform
+// index, and the plane loops are wave-uniform.
+static_assert(sizeof(AoTemporalPlanes) + sizeof(uint32_t) <= 4096,
+              "rt_ao_accumulate_planes' launch must fit the 4 KB kernel-argument segment");
+static_assert(sizeof(AtrousPlanes) + 2 * sizeof(uint32_t) <= 4096,
+              "rt_ao_atrous_planes' launch must fit the 4 KB kernel-argument segment");
+
+__global__ __launch_bounds__(256) void k_ao_accumulate_planes(AoTemporalPlanes a, uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= a.W || y >= a.H) return;
+  ao_accumulate_planes_pixel(a, x, y);
+}
+
+struct GlobalGuideTap {  // a tap's guide entry read from the plane, bounds-checked
+  const float* guide;
+  int x, y, s, W, H;
+  __device__ __forceinline__ bool operator()(int dx, int dy, float q[4]) const {
+    const int xx = x + dx * s, yy = y + dy * s;
+    if (xx < 0 || yy < 0 || xx >= W || yy >= H) return false;
+    ld4(guide + 4 * ((size_t)yy * (size_t)W + (size_t)xx), q);
+    return true;
+  }
+};
+
+// One pixel per lane over 32 x 8 tiles: the 25 guide entries loaded and weighed once, then 25 four-byte loads per plane
+// (a skipped tap, which may lie outside the frame, is not read: its load goes to the pixel's own entry and is dropped).
+__global__ __launch_bounds__(256) void k_ao_atrous_planes_direct(AtrousPlanes a, uint32_t tiles_x) {
+  const uint32_t x = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 31u);
+  const uint32_t y = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 5);
+  if (x >= a.W || y >= a.H) return;
+  const size_t i = (size_t)y * a.W + x;
+  float g[4];
+  ld4(a.guide + 4 * i, g);
+  if (g[3] == 0.0f) {
+    for (uint32_t p = 0; p < a.nplanes; ++p) a.out[p][i] = a.in[p][i];
+    return;
+  }
+  // A tap is (dy s W + dx s) entries from the pixel. In 32-bit modular arithmetic: a tap in the frame has an index
+  // below W H < 2^31, and only those are used.
+  const uint32_t s = a.s, row = a.s * a.W, i32 = (uint32_t)i;
+  atrous_planes_pixel(
+      g, s, a.depth_tol, a.normal_cos, a.nplanes, GlobalGuideTap{a.guide, (int)x, (int)y, (int)s, (int)a.W, (int)a.H},
+      [&](uint32_t p, int dx, int dy, bool on) {  // a skipped tap reads the pixel's own entry
+        return a.in[p][i32 + (on ? (uint32_t)dy * row + (uint32_t)dx * s : 0u)];
+      },
+      [&](uint32_t p, float v) { a.out[p][i] = v; });
+}
+
+struct LdsGuideTap {  // a tap's guide entry read from the staged tile: outside the frame it was staged as "no surface"
+  const float4* g;
+  int at;  // the pixel's own entry
+  __device__ __forceinline__ bool operator()(int dx, int dy, float q[4]) const {
+    const float4 t = g[at + dy * (int)kStageW + dx];
+    q[0] = t.x, q[1] = t.y, q[2] = t.z, q[3] = t.w;
+    return true;
+  }
+};
+
+// The staged form keeps kStagePlanes value tiles next to the guide tile: 6912 + 7 x 1728 = 19,008 B, of which eight
+// workgroups (a CU's 32 waves) fit the 160 KB of LDS, and the six lights plus the AO plane of the reference frame
+// loop go through in one round. More planes take further rounds under the same weights.
+constexpr uint32_t kStagePlanes = 7;
+
+// k_ao_atrous_lds's block order and lattice tile (shift = log2(s), nbx = lattice tiles per row * s). The guide tile is
+// staged once per workgroup and the 25 weights are computed once per pixel; the planes follow kStagePlanes at a time.
+// A thread stages the same one or two entries of every tile, so their plane indices are computed once.
+__global__ __launch_bounds__(256, 8) void k_ao_atrous_planes_lds(AtrousPlanes a, uint32_t shift, uint32_t nbx) {
+  __shared__ float4 sg[kStageH * kStageW];
+  __shared__ float sv[kStagePlanes][kStageH * kStageW];
+  const uint32_t s = 1u << shift, W = a.W, H = a.H, P = a.nplanes;
+  const uint32_t bx = blockIdx.x % nbx, by = blockIdx.x / nbx;
+  const uint32_t rx = bx & (s - 1u), ry = by & (s - 1u);
+  const int lx0 = (int)((bx >> shift) * kTileW), ly0 = (int)((by >> shift) * kTileH);  // the tile's lattice origin
+  if ((uint32_t)lx0 * s + rx >= W || (uint32_t)ly0 * s + ry >= H) return;  // block-uniform: an empty tile
+  // this thread's entries of a tile: e0 always, e1 for the first 176 threads; in the frame or staged as zeros
+  auto entry = [&](uint32_t e, size_t& t) __attribute__((always_inline)) {
+    const int li = lx0 + (int)(e % kStageW) - (int)kHalo, lj = ly0 + (int)(e / kStageW) - (int)kHalo;
+    const long long X = (long long)li * s + rx, Y = (long long)lj * s + ry;
+    if (!(li >= 0 && lj >= 0 && X < (long long)W && Y < (long long)H)) return false;
+    t = (size_t)Y * W + (size_t)X;
+    return true;
+  };
+  const uint32_t e0 = threadIdx.x, e1 = threadIdx.x + 256u;
+  const bool has1 = e1 < kStageH * kStageW;
+  size_t t0 = 0, t1 = 0;
+  const bool in0 = entry(e0, t0), in1 = has1 && entry(e1, t1);
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 q0 = zero, q1 = zero;
+  if (in0) q0 = *reinterpret_cast<const float4*>(a.guide + 4 * t0);
+  if (in1) q1 = *reinterpret_cast<const float4*>(a.guide + 4 * t1);
+  sg[e0] = q0;
+  if (has1) sg[e1] = q1;
+  auto stage = [&](uint32_t p0, uint32_t nc) __attribute__((always_inline)) {
+    for (uint32_t c = 0; c < nc; ++c) {
+      const float* in = a.in[p0 + c];
+      float v0 = 0.0f, v1 = 0.0f;
+      if (in0) v0 = in[t0];
+      if (in1) v1 = in[t1];
+      sv[c][e0] = v0;
+      if (has1) sv[c][e1] = v1;
+    }
+  };
+  uint32_t p0 = 0, nc = P < kStagePlanes ? P : kStagePlanes;
+  stage(p0, nc);
+  __syncthreads();
+  const uint32_t tx = threadIdx.x & 31u, ty = threadIdx.x >> 5;
+  const uint32_t x = ((uint32_t)lx0 + tx) * s + rx, y = ((uint32_t)ly0 + ty) * s + ry;
+  const bool active = x < W && y < H;  // no early return: further rounds have barriers
+  const int at = (int)((ty + kHalo) * kStageW + tx + kHalo);
+  const size_t i = (size_t)y * W + x;
+  const float4 cg = sg[at];
+  const bool surface = active && cg.w != 0.0f;
+  float w[25], sw = 1.0f;
+  uint32_t mask = 0u;
+  if (surface) {
+    const float g[4] = {cg.x, cg.y, cg.z, cg.w};
+    atrous_planes_weights(g, s, a.depth_tol, a.normal_cos, LdsGuideTap{sg, at}, w, mask, sw);
+  }
+  for (;;) {
+    if (active)
+      for (uint32_t c = 0; c < nc; ++c) {
+        const float* v = sv[c];
+        a.out[p0 + c][i] =
+            surface ? atrous_planes_value(w, mask, sw, [&](int dx, int dy, bool) { return v[at + dy * (int)kStageW + dx]; })
+                    : v[at];
+      }
+    p0 += nc;
+    if (p0 >= P) break;  // uniform
+    nc = P - p0 < kStagePlanes ? P - p0 : kStagePlanes;
+    __syncthreads();  // every lane has read the round's tiles
+    stage(p0, nc);
+    __syncthreads();
+  }
 }
 
 // One-dimensional over the pixels (W * H < 2^31, rt_api.cpp): a wave's 64 pixels are consecutive in every plane.
@@ -402,6 +544,35 @@ hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol,
   if (nbx * nby > 0x7fffffffull) return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(k_ao_atrous_lds, dim3((uint32_t)(nbx * nby)), dim3(256), 0, stream, W, H, shift, depth_tol,
                      normal_cos, in, guide, out, (uint32_t)nbx);
+  return hipGetLastError();
+}
+
+hipError_t launch_ao_accumulate_planes(const AoTemporalPlanes& a, hipStream_t stream) {
+  const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
+  hipLaunchKernelGGL(k_ao_accumulate_planes, dim3(tx * ty), dim3(256), 0, stream, a, tx);
+  return hipGetLastError();
+}
+
+hipError_t launch_ao_atrous_planes(const AtrousPlanes& a, int form, hipStream_t stream) {
+  // Measured per step for this filter (tools/filter_planes_study.py), not launch_ao_atrous's rule: the
+  // staged form takes 0.83 x and 0.87 x the direct form's time at steps 1 and 2 with 7 planes at 720p, 0.77 x and
+  // 0.75 x with 2 planes at 1080p and 0.71 x and 0.74 x with 1, and the direct form wins from step 8 on (the staged
+  // form 1.36 x .. 2.46 x with 2 and 7 planes; with 1 plane a tie at 8, 1.21 x at 16): beyond both p10 - p90 spreads
+  // but for the tie. Step 4 depends on the plane count: staged 0.89 x with 2 planes, 1.14 x with 7 (so three planes or
+  // more take it direct), within the spreads with 1.
+  if (form == kAtrousAuto) form = a.s <= 2u || (a.s == 4u && a.nplanes <= 2u) ? kAtrousLds : kAtrousDirect;
+  if (form == kAtrousDirect) {
+    const uint32_t tx = tiles(a.W, kTileW), ty = tiles(a.H, kTileH);
+    hipLaunchKernelGGL(k_ao_atrous_planes_direct, dim3(tx * ty), dim3(256), 0, stream, a, tx);
+    return hipGetLastError();
+  }
+  uint32_t shift = 0;
+  while ((1u << shift) < a.s) ++shift;
+  const uint64_t nbx = (uint64_t)tiles(tiles(a.W, a.s), kTileW) * a.s,
+                 nby = (uint64_t)tiles(tiles(a.H, a.s), kTileH) * a.s;  // as launch_ao_atrous
+  if (nbx * nby > 0x7fffffffull) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(k_ao_atrous_planes_lds, dim3((uint32_t)(nbx * nby)), dim3(256), 0, stream, a, shift,
+                     (uint32_t)nbx);
   return hipGetLastError();
 }
 

@@ -1195,6 +1195,158 @@ RT_HD float atrous_pixel(const float g[4], uint32_t s, float depth_tol, float no
 }
 
 // ------------------------------------------------------------------------------------------
+// The AO filter over several planes at once (rt_ao_accumulate_planes, rt_ao_atrous_planes): what
+// ao_accumulate_pixel and atrous_pixel compute that does not depend on the plane's values (the accepted reprojection
+// taps, the 25 edge-stopping weights, sw, sh) is computed once per pixel; only sa is per plane, summed over the same
+// taps in the same order with the same expressions, so every plane's bits are the per-plane function's.
+// ------------------------------------------------------------------------------------------
+constexpr int kMaxFilterPlanes = 17;  // RT_MAX_FILTER_PLANES
+
+struct AoTemporalPlanes {  // rt_ao_accumulate_planes' launch: AoTemporal with tables of planes (prev: all null or none)
+  uint32_t W, H, nplanes;
+  float max_history, depth_tol, normal_cos;
+  const float *motion, *guide_cur, *hist_prev, *guide_prev;
+  float* hist_out;
+  const float* cur[kMaxFilterPlanes];
+  const float* prev[kMaxFilterPlanes];
+  float* out[kMaxFilterPlanes];
+};
+
+// Pixel (x, y) of rt_ao_accumulate_planes: reproject_taps once, the at most four accepted (weight, index) pairs kept in
+// tap order in four named slots (nothing here is indexed by a run-time value but the tables), then
+// ao_accumulate_pixel's sa and blend per plane. Reads its own cur[p] entry before it writes out[p] (they may be equal).
+RT_HD void ao_accumulate_planes_pixel(const AoTemporalPlanes& a, uint32_t x, uint32_t y) {
+  const size_t i = (size_t)y * a.W + x;
+  float g[4], m[4];
+  ld4(a.guide_cur + 4 * i, g);
+  if (g[3] == 0.0f) {
+    for (uint32_t p = 0; p < a.nplanes; ++p) a.out[p][i] = a.cur[p][i];
+    a.hist_out[i] = 0.0f;
+    return;
+  }
+  ld4(a.motion + 4 * i, m);
+  float sw = 0.0f, sh = 0.0f;
+  // The accepted taps in tap order, shifted in from the right: an accepted weight is never 0 (reproject_taps skips
+  // those), so a slot of weight 0 is an empty one; its index stays the pixel's own, an address that can be read.
+  float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, w3 = 0.0f;
+  size_t t0 = i, t1 = i, t2 = i, t3 = i;
+  if (a.hist_prev)
+    reproject_taps(a.W, a.H, x, y, g, m, a.depth_tol, a.normal_cos, a.guide_prev, [&](float w, size_t t) {
+      w0 = w1, t0 = t1, w1 = w2, t1 = t2, w2 = w3, t2 = t3, w3 = w, t3 = t;
+      sw += w;
+      sh += w * a.hist_prev[t];
+    });
+  if (sw >= 0.01f) {
+    const float n = minf(sh / sw + 1.0f, a.max_history);
+    const float al = 1.0f / n;
+    for (uint32_t p = 0; p < a.nplanes; ++p) {
+      const float* pv = a.prev[p];
+      const float cur = a.cur[p][i];
+      const float v0 = pv[t0], v1 = pv[t1], v2 = pv[t2], v3 = pv[t3];  // an empty slot's value is dropped
+      float sa = 0.0f;
+      sa = w0 != 0.0f ? sa + w0 * v0 : sa;
+      sa = w1 != 0.0f ? sa + w1 * v1 : sa;
+      sa = w2 != 0.0f ? sa + w2 * v2 : sa;
+      sa = w3 != 0.0f ? sa + w3 * v3 : sa;
+      const float av = sa / sw;
+      a.out[p][i] = n == 1.0f ? cur : av + al * (cur - av);  // n == 1: as ao_accumulate_pixel
+    }
+    a.hist_out[i] = n;
+  } else {
+    for (uint32_t p = 0; p < a.nplanes; ++p) a.out[p][i] = a.cur[p][i];
+    a.hist_out[i] = 1.0f;
+  }
+}
+
+// atrous_pixel's plane-independent half for a pixel with guide g (g[3] != 0): the 25 weights in tap order (dy outer, dx
+// inner), bit k = (dy + 2) * 5 + dx + 2 of `mask` set for every tap atrous_pixel does not skip (a tap of weight 0 is
+// not a skipped one), and their sum sw. tap(dx, dy, q) gives the tap's guide entry, false outside the frame. The loops
+// unroll fully, so w is indexed by constants only and lives in registers.
+template <typename Tap>
+RT_HD void atrous_planes_weights(const float g[4], uint32_t s, float depth_tol, float normal_cos, Tap tap, float w[25],
+                                 uint32_t& mask, float& sw) {
+  const V3 gn = v3(g[0], g[1], g[2]);
+  const float zden = (depth_tol * g[3]) * (float)s;
+  const float nden = 1.0f - normal_cos;
+  mask = 0u;
+  sw = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int dy = -2; dy <= 2; ++dy) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dx = -2; dx <= 2; ++dx) {
+      const int k = (dy + 2) * 5 + dx + 2;
+      float q[4], wk = 0.0f;
+      bool on = tap(dx, dy, q);
+      if (on) {
+        wk = atrous_h(dy) * atrous_h(dx);
+        if (dx != 0 || dy != 0) {
+          on = q[3] != 0.0f;
+          if (on) {
+            const float wz = maxf(0.0f, 1.0f - fabsf(q[3] - g[3]) / zden);
+            const float wn = minf(1.0f, maxf(0.0f, (dot(gn, v3(q[0], q[1], q[2])) - normal_cos) / nden));
+            const float e = wz * wn;
+            wk = wk * (e * e);
+          }
+        }
+      }
+      w[k] = wk;  // written once, outside the branches: w stays 25 registers (a skipped tap's entry is never used)
+      if (on) {
+        mask |= 1u << k;
+        sw += wk;
+      }
+    }
+  }
+}
+
+// atrous_pixel's per-plane half: sa over the unmasked taps in tap order, then sa / sw. val(dx, dy, on) gives the plane's
+// value at the tap when `on`; for a skipped tap (on false) it must not read the tap and may return anything: the value
+// is dropped, not multiplied by a zero. (The device forms read an address that is always theirs to read instead: the
+// 25 values are fetched first and summed afterwards, so that the loads are in flight together.)
+template <typename Val>
+RT_HD float atrous_planes_value(const float w[25], uint32_t mask, float sw, Val val) {
+  float v[25];
+#if defined(__HIP_DEVICE_COMPILE__)
+  // The mask stays one register: without this the compiler splits it into 25 flags and hoists the 25 tap addresses
+  // they select out of the plane loop, four times the registers the loop needs.
+  asm volatile("" : "+v"(mask));
+#pragma unroll
+#endif
+  for (int k = 0; k < 25; ++k) v[k] = val(k % 5 - 2, k / 5 - 2, (mask & (1u << k)) != 0u);
+#if defined(__HIP_DEVICE_COMPILE__)
+  // Empty statements that pin the loads above them: left alone, the compiler moves each load under a branch on its
+  // mask bit, and a plane's 25 loads then wait for one another.
+#pragma unroll
+  for (int k = 0; k < 25; ++k) asm volatile("" : "+v"(v[k]));
+#endif
+  float sa = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int k = 0; k < 25; ++k) sa = (mask & (1u << k)) != 0u ? sa + w[k] * v[k] : sa;  // dy outer, dx inner
+  return sa / sw;
+}
+
+// One iteration's values of a pixel with guide g (g[3] != 0) for nplanes planes: the weights once, then every plane's
+// value. val(p, dx, dy, on): plane p's input at the tap, as atrous_planes_value's; put(p, v): its output. The plane loop
+// is uniform.
+template <typename Tap, typename Val, typename Put>
+RT_HD void atrous_planes_pixel(const float g[4], uint32_t s, float depth_tol, float normal_cos, uint32_t nplanes,
+                               Tap tap, Val val, Put put) {
+  float w[25], sw;
+  uint32_t mask;
+  atrous_planes_weights(g, s, depth_tol, normal_cos, tap, w, mask, sw);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (uint32_t p = 0; p < nplanes; ++p)
+    put(p, atrous_planes_value(w, mask, sw, [&](int dx, int dy, bool on) { return val(p, dx, dy, on); }));
+}
+
+// ------------------------------------------------------------------------------------------
 // Radiance filter (rt_radiance_accumulate, rt_radiance_atrous): the AO filter's pair for planes of
 // 4-float entries (a reflection plane: mean colour and mean distance), with luminance moments kept by the temporal
 // pass and a luminance weight scaled by their variance in the blur. The AO section's arithmetic rule holds;

@@ -239,6 +239,20 @@ enum { kAtrousAuto = 0, kAtrousDirect = 1, kAtrousLds = 2 };
 hipError_t launch_ao_atrous(uint32_t W, uint32_t H, uint32_t s, float depth_tol, float normal_cos, const float* in,
                             const float* guide, float* out, int form, hipStream_t stream);
 
+// --- The AO filter over several planes (rt_denoise.hip) ------------------------
+// One launch per pass whatever the plane count: the tables of plane pointers ride in the kernel argument.
+hipError_t launch_ao_accumulate_planes(const AoTemporalPlanes& a, hipStream_t stream);
+// One a-trous iteration of step s from in[p] to out[p], p < nplanes, under one guide.
+struct AtrousPlanes {
+  uint32_t W, H, s, nplanes;
+  float depth_tol, normal_cos;
+  const float* guide;
+  const float* in[kMaxFilterPlanes];
+  float* out[kMaxFilterPlanes];
+};
+// form: launch_ao_atrous's constants; kAtrousAuto picks per step by this filter's own measurement.
+hipError_t launch_ao_atrous_planes(const AtrousPlanes& a, int form, hipStream_t stream);
+
 // --- Radiance filter (rt_denoise.hip) -----------------------------------------
 // The AO filter's pair for planes of 4-float entries; per-pixel arithmetic in rt_device.hpp, shared with the host twins.
 hipError_t launch_radiance_accumulate(const RadTemporal& a, hipStream_t stream);
