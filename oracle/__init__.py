@@ -50,6 +50,7 @@ _SIGS = [
     ("oracle_render_split", _I, [_P, _FP, ctypes.POINTER(oracle_light), _U32, _FP, _I, _I, _U32, _U32, _P, _U32, _P,
                                  _P, _I, _P, _I, _I, _I]),
     ("oracle_trace_rays", _I, [_P, _P, _U32, _U32, _P, _P, _I, _P]),
+    ("oracle_trace_rays_packet", _I, [_P, _P, _U32, _U32, _P, _P]),
     ("oracle_raster", _I, [_P, _P, _P, _P, _U32, _P, _P, _U32, _U32, _P, _P, _P]),
     ("oracle_pbr", None, [_FP, _FP, _FP, ctypes.POINTER(oracle_light), _U32, _FP, _FP]),
     ("oracle_direct", None, [_FP, _FP, ctypes.POINTER(oracle_light), _U32, _FP, _FP]),
@@ -302,3 +303,17 @@ class Scene:
                               uv.ctypes.data_as(_P), 1 if brute_force else 0, stats.ctypes.data_as(_P)):
             raise RuntimeError("oracle_trace_rays failed")
         return hits, uv, stats
+
+    def trace_rays_packet(self, rays: np.ndarray, any_hit=False, cull_back=False, cull_front=False):
+        """trace_rays through the packet emulation: every 64 consecutive rays walk as one packet (one tmin and one
+        tmax per packet). Returns (hits, uv)."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = r.shape[0]
+        hits = np.zeros((n, 4), np.uint32)
+        uv = np.zeros((n, 2), np.float32)
+        flags = (0x04 if any_hit else 0) | (0x10 if cull_back else 0) | (0x20 if cull_front else 0)
+        st = self._lib.oracle_trace_rays_packet(self._h, r.ctypes.data_as(_P), n, flags, hits.ctypes.data_as(_P),
+                                                uv.ctypes.data_as(_P))
+        if st:
+            raise RuntimeError(f"oracle_trace_rays_packet failed ({st})")
+        return hits, uv

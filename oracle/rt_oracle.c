@@ -7,7 +7,8 @@
  * with -ffp-contract=off; the only fused multiply-adds are the explicit fmaf() of the slab test.
  * The BVH is an LBVH built by the same deterministic algorithm as the device builder, so the
  * device tree can be compared node for node; the rendered image does not depend on the tree
- * (conservative culling + (t, instance, primitive) tie-break), which brute_force=1 verifies.
+ * (culling + (t, instance, primitive) tie-break), which brute_force=1 verifies on rays in general position
+ * (oslab4 has the exception).
  */
 #include "rt_oracle.h"
 
@@ -814,7 +815,10 @@ typedef struct { float t, u, v; uint32_t inst, prim; } ohit;
 
 static inline float sinv(float d) { return fabsf(d) > 1e-20f ? 1.0f / d : (d < 0.0f ? -1e20f : 1e20f); }
 
-/* slab tests of the 4 children of a node against [tmin, tbest]; +inf = missed or empty */
+/* slab tests of the 4 children of a node against [tmin, tbest]; +inf = missed or empty. The device's slab4_octant
+ * bit for bit, its two gaps on axis-aligned geometry included (rt_device.hpp: a zero-component ray in a box's max-face
+ * plane, and the absolute rounding error of o * invd): there brute_force=1 finds triangles this walk culls
+ * (tests/test_walk_bruteforce_host.py). */
 /* The slab operands are never NaN (finite origins, safe_inv never 0 or inf, +-inf planes of empty slots
  * times a finite inverse), and the sign of a zero min/max never changes a comparison or a key (keys drop the
  * sign bit), so the CPU baseline build may use plain compares (minss / maxss) instead of the libm calls
@@ -1796,6 +1800,48 @@ int oracle_trace_rays(const oracle_scene* s, const float* rays, uint32_t n, uint
   if (stats) {
     for (int q = 0; q < 6; ++q) stats[q] += st.v[q];
     for (int q = 9; q < 12; ++q) stats[q] += st.v[q];
+  }
+  return 0;
+}
+
+/* oracle_trace_rays through the packet emulation: rays [64 p, 64 p + 64) walk as one packet (the last one
+ * padded with dead lanes), the way the frame kernels' tiles do. opacket takes one [tmin, tmax] per packet, so
+ * every ray of a packet must carry its first ray's. Records as oracle_trace_rays writes them; no counters.
+ * Test infrastructure (tests/test_walk_bruteforce_host.py): the packet walk held to brute force ray by ray. */
+int oracle_trace_rays_packet(const oracle_scene* s, const float* rays, uint32_t n, uint32_t flags, uint32_t* hits,
+                             float* uv) {
+  if (!s || !s->tlas) return -1;
+  if ((flags & 0x30u) == 0x30u) return -1;
+  uint32_t maxd = 0;
+  for (int q = 0; q < s->nblas; ++q) if (s->blas[q].depth > maxd) maxd = s->blas[q].depth;
+  if ((s->tlas_max_stack + maxd) >= OPK) return -2; /* too deep for the packet walk (oracle_render_split's rule) */
+  const int any = (flags & 0x04u) != 0, cull = (flags & 0x10u) ? 1 : ((flags & 0x20u) ? -1 : 0);
+  ostats st;
+  memset(&st, 0, sizeof(st));
+  for (uint32_t base = 0; base < n; base += OPK) {
+    vec3 o[OPK], d[OPK];
+    int alive[OPK], found[OPK];
+    ohit h[OPK];
+    const float* r0 = rays + (size_t)base * 8;
+    for (int l = 0; l < OPK; ++l) {
+      const uint32_t i = base + (uint32_t)l;
+      alive[l] = i < n;
+      const float* r = alive[l] ? rays + (size_t)i * 8 : r0;
+      if (r[3] != r0[3] || r[7] != r0[7]) return -3;
+      o[l] = ld3(r); d[l] = ld3(r + 4);
+    }
+    opacket(s, o, d, r0[3], r0[7], any, cull, alive, h, found, &st);
+    for (int l = 0; l < OPK && base + (uint32_t)l < n; ++l) {
+      const uint32_t i = base + (uint32_t)l;
+      const int f = found[l];
+      float t = f ? h[l].t : r0[7];
+      uint32_t tb; memcpy(&tb, &t, 4);
+      hits[i * 4 + 0] = tb;
+      hits[i * 4 + 1] = f ? h[l].inst : 0xffffffffu;
+      hits[i * 4 + 2] = f ? h[l].prim : 0xffffffffu;
+      hits[i * 4 + 3] = f ? 1u : 0u;
+      if (uv) { uv[i * 2] = f ? h[l].u : 0.0f; uv[i * 2 + 1] = f ? h[l].v : 0.0f; }
+    }
   }
   return 0;
 }

@@ -77,6 +77,10 @@ void oracle_camera_rays(const float cb[64], uint32_t W, uint32_t H, const uint32
                         float ox, float oy, float* rays);
 int oracle_trace_rays(const oracle_scene* s, const float* rays, uint32_t n, uint32_t ray_flags, uint32_t* hits,
                       float* uv, int brute_force, uint64_t* stats);
+/* the same through the packet emulation: rays [64 p, 64 p + 64) form packet p; one [tmin, tmax] per packet
+ * (-3 otherwise), -2 when the trees are too deep for the packet walk */
+int oracle_trace_rays_packet(const oracle_scene* s, const float* rays, uint32_t n, uint32_t ray_flags, uint32_t* hits,
+                             float* uv);
 
 /* raster fallback (rt_raster_draw), rt_raster_oracle.c: draws in order, each vtx6[d] with nvtx[d]
  * {pos, normal} vertices and ntri[d] triangles (idx[d] NULL = non-indexed). rgba8 W x H x 4;

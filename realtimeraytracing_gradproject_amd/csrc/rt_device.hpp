@@ -493,8 +493,19 @@ RT_HD uint32_t unorm8(float c) {
 
 // Slab tests of the 4 children of a Bvh4Node against the ray segment [tmin, tbest], given each
 // axis's near and far planes (the ray's octant picks them: near = lo where invd >= 0, else hi).
-// tn[k] = entry distance of child k, or +inf if it is missed or empty. Conservative (tfar
-// widened by 1 + 4e-7) so BVH culling never rejects a triangle Moller-Trumbore accepts.
+// tn[k] = entry distance of child k, or +inf if it is missed or empty. tfar is widened by 1 + 4e-7, which
+// covers the RELATIVE rounding of the distances (1 / d and the fma's result) and nothing else. On the random
+// scenes, the teapot and the seam probe no brute-force test has found a triangle it culls wrongly (DESIGN §0 row
+// a13), but it is not conservative, on axis-aligned geometry above all (DESIGN §5,
+// tests/test_walk_bruteforce_host.py):
+//  * a zero direction component (safe_inv: 1e20 for both signs of zero) of a ray lying in a box's max-face plane
+//    gives far distance fma(hi, 1e20, -(o 1e20)) = 0, or the rounding error of o 1e20 with either sign, below the
+//    other axes' entry distances: the box is dropped, though both triangle tests accept the edges in that plane
+//    (the same ray in the min-face plane enters at <= 0 and is kept unless that error is positive);
+//  * noinv = -(o invd) is rounded once per ray, an ABSOLUTE error of ulp(o / d) / 2 in every distance of the axis,
+//    which no relative widening covers once |o / d| is far above t (d.y = -1e-7, o.y = 2.5: +-1 in t at t = 80).
+//    A ray in general position meets this too when |o / d| >~ 10 t on a flat box's axis and another hit lies
+//    within an ulp of t (two instances' coincident faces): it then keeps the farther of the two.
 // Bitwise equal to the min/max form of oracle oslab4: for invd > 0 the exact products lo*invd <=
 // hi*invd and the fma rounding is monotone, so fma(lo,..) <= fma(hi,..) (reversed for invd < 0;
 // safe_inv never returns 0), i.e. min/max of the two plane distances is the near/far plane.

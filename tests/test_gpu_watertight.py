@@ -3,8 +3,11 @@
 The kernels are checked against rt_host_trace_triangles — brute force over every triangle with the same
 intersection functions, itself pinned bit for bit to a numpy restatement by tests/test_watertight_host.py — so
 equality here says two things: the kernels run that arithmetic, and the BVH (its slab test, its three build
-paths' vertex-form records) never culls a triangle the test accepts. Every comparison is bit for bit; the one
-bound that is not an equality is the issue's: zero leaks on the seam probe's interior class.
+paths' vertex-form records) culls no triangle the test accepts on THESE rays, which are all in general position
+(random origins aimed at random points, the seam probe, camera rays). Axis-parallel, in-plane and tiny-component rays on
+axis-aligned geometry, where the slab cull does drop accepted triangles, are tests/test_gpu_walk_bruteforce.py's.
+Every comparison is bit for bit; the one bound that is not an equality is the issue's: zero leaks on the seam
+probe's interior class.
 """
 import os
 import subprocess
